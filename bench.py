@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the Augmented Super-Resolution hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--config {1,2,4}] [--images M]
+    python bench.py --gpus N --steps K --warmup W [--config {1,2,4}] [--images M] [--dump-outputs DIR] [--full]
 
 Workloads = BASELINE.json configs, all synthetic, inputs resident in HBM before the timed region:
   --config 1 (default, the configuration the metric is quoted on): 512x512 images, num_aug=100, angle +-0.15,
@@ -19,10 +19,15 @@ of BASELINE configs[3] (SR_single_class.py:83-134 over a fixed image set): M ima
 (ragged shards), value = M * num_aug / time.  No data-path collective; one RCCL all-gather of the per-image IoU records at
 the end (inside the timed region).
 
-Prints ONE JSON line on rank 0: metric / value, `roofline` of the dominant kernel (HIP events on the launch stream in an
-extra profiled step), `cpu_baseline` (the CPU oracle on the host cores, bounded sample), `parity` (HIP against that
-oracle sample: the "IoU delta vs ref" half of BASELINE's metric) and, on the default single-GPU run, `configs`: the same
-measurement of configs[2] and configs[4] (a few steps each) next to the headline.
+Prints ONE JSON line on rank 0: metric / value / ms_per_step of the K timed steps.  A plain run does nothing else: set-up,
+W warm-up steps, K timed steps, the line.  ``--full`` adds what takes runs of its own: `roofline` of the dominant kernel
+(HIP events on the launch stream in an extra profiled step), `cpu_baseline` (the CPU oracle on the host cores, bounded
+sample), `parity` (HIP against that oracle sample: the "IoU delta vs ref" half of BASELINE's metric) and, on a single-GPU
+run of configs[1], `exact_f32` (the same workload on exact-f32 MFMA) and `configs`: the same measurement of configs[2] and
+configs[4] (a few steps each) next to the headline.
+``--dump-outputs DIR``: rank 0 writes what the timed path returned in its last timed step -- HotPath.run_image's masks
+(standard, aug, max, mean; float32 [out, out]) and its 6 IoUs (float64) -- as DIR/<name>.npy.  Inputs and weights are
+seeded, so two builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -387,34 +392,41 @@ class Workload:
         return self.path.run_image(*a, profile=profile, **kw)
 
     def run(self, globals_):
-        """The images `globals_` in order; returns their IoU records."""
+        """The images `globals_` in order; returns their IoU records.  `self.last` keeps the whole result of the last image
+        (what run_image hands its caller), for --dump-outputs."""
         recs, args = [], self.args
+        self.last = None
+
+        def take(res):
+            self.last = res
+            return res["ious"]
+
         if self.lanes > 1:
             pending = []
             for i, g in enumerate(globals_):
                 a, kw = self._args(g)
                 pending.append(self.path.submit_lane(i % self.lanes, *a, **kw))
                 if len(pending) >= self.lanes:              # keep `lanes` images in flight, collect in submission order
-                    recs.append(pending.pop(0).result()["ious"])
+                    recs.append(take(pending.pop(0).result()))
             while pending:
-                recs.append(pending.pop(0).result()["ious"])
+                recs.append(take(pending.pop(0).result()))
             return recs
         if not args.overlap:
-            return [self.step(g)["ious"] for g in globals_]
+            return [take(self.step(g)) for g in globals_]
         pending = None
         for g in globals_:
             a, kw = self._args(g)
             h = self.path.submit_image(*a, **kw)
             if pending is not None:
-                recs.append(pending.result()["ious"])
+                recs.append(take(pending.result()))
             pending = h
         if pending is not None:
-            recs.append(pending.result()["ious"])
+            recs.append(take(pending.result()))
         return recs
 
     def close(self):
         import torch
-        self.path = self.model = self.imgs = self.gts = None
+        self.path = self.model = self.imgs = self.gts = self.last = None
         gc.collect()
         torch.cuda.empty_cache()
 
@@ -537,10 +549,22 @@ def rooflines(prof, provenance, cfg_id=1):
     return out
 
 
+def dump_outputs(res, directory):
+    """What the timed path returned for one image (HotPath.run_image's dict): the standard / aug / max / mean masks as
+    float32 [out, out] and the 6 IoUs as float64, one DIR/<name>.npy each (4 MB at 512x512)."""
+    from asr_amd.pipeline import HotPath
+    os.makedirs(directory, exist_ok=True)
+    for k in HotPath.MASK_KEYS:
+        if k in res:
+            np.save(os.path.join(directory, f"{k}_mask.npy"), res[k].cpu().numpy().astype(np.float32))
+    np.save(os.path.join(directory, "ious.npy"), np.asarray(res["ious"], dtype=np.float64))
+
+
 def measure(cfg_id, args, rank, world, dev, weights, steps, warmup, images=None, bias_shift=None, want_roofline=True,
-            want_cpu=True, dump_table=None):
+            want_cpu=True, dump_table=None, dump_dir=None):
     """One workload, timed as the contract says: W warm-up steps, a barrier + synchronize, EXACTLY K steps (or the rank's
-    shard of `images`), the all-gather, synchronize + barrier, MAX over ranks."""
+    shard of `images`), the all-gather, synchronize + barrier, MAX over ranks.  `dump_dir`: rank 0 writes the outputs of
+    its last timed step there (dump_outputs)."""
     import torch
     from asr_amd import distributed as D
     wl = Workload(cfg_id, args, rank, world, dev, weights, args.precision, bias_shift)
@@ -573,6 +597,8 @@ def measure(cfg_id, args, rank, world, dev, weights, steps, warmup, images=None,
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     elapsed = D.all_reduce_max(elapsed, dev)           # MAX over ranks
+    if rank == 0 and dump_dir:
+        dump_outputs(wl.last, dump_dir)
 
     collective = D.collective_info(dev)                 # after the timed region: one more (untimed) all-reduce
     k_rank = max(len(D.shard_indices(images, r, world)) for r in range(world)) if images is not None else steps
@@ -671,13 +697,20 @@ def main():
     ap.add_argument("--lanes", type=int, default=2, help="images in flight on alternating HIP streams, each with its own "
                     "activation pool (1 = strictly sequential; 2 = the forward pass of one image runs under the SR stage of "
                     "the other and vice versa; results are bit-identical)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-f32-line", action="store_true", help="skip the extra exact-f32 (v_mfma_f32_32x32x2_f32) measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: roofline (one profiled step), cpu_baseline + parity (the "
+                         "CPU oracle), and on a single-GPU configs[1] run exact_f32 and configs[2] / configs[4]")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without cpu_baseline / parity")
+    ap.add_argument("--no-roofline", action="store_true", help="--full without the roofline step")
+    ap.add_argument("--no-f32-line", action="store_true", help="--full without the extra exact-f32 (v_mfma_f32_32x32x2_f32) measurement")
     ap.add_argument("--no-extra-configs", action="store_true",
-                    help="skip the configs[2] / configs[4] measurements that the default single-GPU run appends")
+                    help="--full without the configs[2] / configs[4] measurements it appends on a single GPU")
     ap.add_argument("--dump-table", default=None, help="rank 0 writes the gathered [images, 6] IoU table (float64 .npy) here")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes the outputs of its last timed step (masks float32, IoUs float64) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        sys.exit(f"bench.py: --steps {args.steps}: at least one timed step")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args))
@@ -704,12 +737,14 @@ def main():
     weights = W.make_synthetic_weights(1234, 21)
     single = rank == 0 and world == 1
     out, wl = measure(args.config, args, rank, world, dev, weights, steps, args.warmup, images=args.images,
-                      want_roofline=not args.no_roofline, want_cpu=not args.no_cpu_baseline, dump_table=args.dump_table)
+                      want_roofline=args.full and not args.no_roofline, want_cpu=args.full and not args.no_cpu_baseline,
+                      dump_table=args.dump_table, dump_dir=args.dump_outputs)
     bias_shift = wl.bias_shift
     wl.close()
     del wl
 
-    if single and args.precision != "f32" and not args.no_f32_line and args.config == 1 and args.images is None:
+    if (args.full and single and args.precision != "f32" and not args.no_f32_line and args.config == 1
+            and args.images is None):
         # the same workload with every GEMM on the exact-f32 MFMA kernels, a few steps, next to the headline
         saved = args.precision
         args.precision = "f32"
@@ -723,7 +758,7 @@ def main():
         out["config"]["exact_f32_ms_per_step"] = o32["ms_per_step"]
         out["exact_f32"] = {"value": o32["value"], "unit": "augmented-copies/s", "steps": k32, "ms_per_step": o32["ms_per_step"],
                             "note": "--precision f32: every pointwise GEMM on v_mfma_f32_32x32x2_f32, same workload and lanes"}
-    if single and args.config == 1 and args.images is None and not args.no_extra_configs:
+    if args.full and single and args.config == 1 and args.images is None and not args.no_extra_configs:
         # BASELINE's other single-GPU configurations, a few steps each, each with its own roofline / cpu_baseline / parity
         out["configs"] = {}
         for cid, k in ((2, min(steps, 8)), (4, min(steps, 4))):

@@ -69,10 +69,10 @@ def test_robustness_grid_script(dev, golden_dir, tmp_path):
 
 
 def test_bench_contract_line(dev):
-    """bench.py prints ONE JSON line with the driver's keys, the roofline of the dominant kernel and the CPU baseline
+    """bench.py --full prints ONE JSON line with the driver's keys, the roofline of the dominant kernel and the CPU baseline
     (a short run: 3 steps, bounded oracle sample)."""
     import json
-    out = _run([os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2"], ROOT)
+    out = _run([os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--full"], ROOT)
     lines = [l for l in out.strip().splitlines() if l.startswith("{")]
     assert len(lines) == 1
     d = json.loads(lines[0])
@@ -155,3 +155,38 @@ def test_bench_two_rank_rehearsal_equals_single_rank(dev, tmp_path):
     assert a.shape == (6, 6) and not np.isnan(a[:, 2:]).any()
     np.testing.assert_array_equal(a, b)
     assert (a[:, 2] > 0.3).all()          # non-trivial masks (class 8 present), not 0/0
+
+
+def test_bench_plain_line_and_dumped_outputs(dev, tmp_path):
+    """A plain run prints the headline line only (roofline, cpu_baseline, parity, exact_f32 and configs are --full), and
+    --dump-outputs writes what the last timed step returned: its four masks and its IoU record, the same row as the gathered
+    table's.  Inputs and weights are seeded, so a second run with the same arguments writes the same arrays."""
+    import json
+    import numpy as np
+    bench = os.path.join(ROOT, "bench.py")
+    names = ["aug_mask.npy", "ious.npy", "max_mask.npy", "mean_mask.npy", "standard_mask.npy"]
+    runs = []
+    for i in range(2):
+        dump, table = tmp_path / f"out{i}", str(tmp_path / f"table{i}.npy")
+        out = _run([bench, "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(dump), "--dump-table", table],
+                   ROOT)
+        lines = [l for l in out.strip().splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["n_gpus"] == 1 and d["higher_is_better"] is True
+        assert d["unit"] == "augmented-copies/s" and d["metric"].endswith("@512x512") and d["dtype"].startswith("f32")
+        assert d["value"] > 50 and abs(d["value"] - 100 * 1000.0 / d["ms_per_step"]) < 1e-3 * d["value"]
+        for k in ("roofline", "cpu_baseline", "parity", "exact_f32", "configs", "overlap"):
+            assert k not in d, k
+        assert sorted(os.listdir(dump)) == names
+        arrs = {n: np.load(dump / n) for n in names}
+        for n, a in arrs.items():
+            if n == "ious.npy":
+                assert a.dtype == np.float64 and a.shape == (6,)
+            else:
+                assert a.dtype == np.float32 and a.shape == (512, 512) and set(np.unique(a)) <= {0.0, 8.0}
+        assert (arrs["aug_mask.npy"] == 8).mean() > 0.05              # class 8 present: the comparison is not vacuous
+        np.testing.assert_array_equal(arrs["ious.npy"], np.load(table)[1 + 3 - 1])   # global image of the last timed step
+        runs.append(arrs)
+    for n in names:
+        np.testing.assert_array_equal(runs[0][n], runs[1][n])

@@ -223,6 +223,32 @@ def test_bench_refuses_a_wrong_rank_count():
         assert r.returncode != 0 and "no GPU is visible" in r.stderr and "{" not in r.stdout
 
 
+def test_bench_dump_outputs_writes_float_arrays(tmp_path):
+    """bench.dump_outputs on a HotPath.run_image-shaped result: the int32 masks become float32 .npy files with the same
+    values, the IoU record a float64 one."""
+    import torch
+    import bench
+    rng = np.random.default_rng(3)
+    res = {k: torch.from_numpy(rng.choice([0, 8], size=(16, 16)).astype(np.int32)) for k in ("standard", "aug", "max", "mean")}
+    res["ious"] = np.array([0.5, 0.25, float("nan"), 1.0, 0.0, 0.125])
+    bench.dump_outputs(res, str(tmp_path / "out"))
+    assert sorted(os.listdir(tmp_path / "out")) == ["aug_mask.npy", "ious.npy", "max_mask.npy", "mean_mask.npy", "standard_mask.npy"]
+    for k in ("standard", "aug", "max", "mean"):
+        a = np.load(tmp_path / "out" / f"{k}_mask.npy")
+        assert a.dtype == np.float32 and np.array_equal(a, res[k].numpy())
+    iou = np.load(tmp_path / "out" / "ious.npy")
+    assert iou.dtype == np.float64 and np.array_equal(iou, res["ious"], equal_nan=True)
+
+
+def test_bench_refuses_zero_steps():
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "0"], capture_output=True, text=True,
+                       timeout=300)
+    assert r.returncode != 0 and "at least one timed step" in r.stderr and "{" not in r.stdout
+
+
 def test_weights_merge_by_name_skips_mismatches():
     """model.py:145 load_weights(by_name=True, skip_mismatch=True): matching variables are taken, a missing layer or a
     shape mismatch (e.g. a 5-class logits layer against a 21-class checkpoint) keeps the initial value and is reported."""

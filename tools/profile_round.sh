@@ -6,7 +6,7 @@
 #   kernel_stats_cfg2.csv / kernel_stats_cfg4.csv       the same (lanes 1) for BASELINE configs[2] and configs[4]
 #   pmc/summary.json, pmc_cfg{2,4}/summary.json         HBM bytes per launch (FETCH_SIZE / WRITE_SIZE in separate passes)
 #   pmc_sq/summary.json                                 matrix-pipe occupancy, wave-cycle split, LDS bank conflicts
-#   bench_default.json.log                              the default bench line (with its configs[2] / configs[4] objects)
+#   bench_default.json.log                              the --full bench line (with its configs[2] / configs[4] objects)
 #   csrc.sha256                                         one hash per translation unit (source + headers + flags) these summaries were
 #                                                       taken on (+ commit if given as $2): bench.py quotes a kernel family's PMC
 #                                                       figures only while ITS unit matches
@@ -51,5 +51,5 @@ if want sq; then
   rm -rf $out/pmc_sq/sq
 fi
 if want bench; then
-  python3 bench.py > $out/bench_default.json.log 2>&1; echo "bench rc=$?"; tail -1 $out/bench_default.json.log | cut -c1-300
+  python3 bench.py --full > $out/bench_default.json.log 2>&1; echo "bench rc=$?"; tail -1 $out/bench_default.json.log | cut -c1-300
 fi
