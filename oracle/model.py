@@ -1,4 +1,4 @@
-"""Layer-by-layer, UNFUSED torch-CPU float32 restatement of the reference's DeepLabV3+
+"""Layer-by-layer, UNFUSED torch-CPU float32 (or float64) restatement of the reference's DeepLabV3+
 (Xception-65, OS16; and the MobileNetV2 variant, OS8) inference graph.  TEST INFRASTRUCTURE ONLY.
 
 Follows model.py:64-147 (build_model), :149-190 (entry/middle/exit flow), :192-233 (ASPP),
@@ -34,11 +34,14 @@ class OracleDeeplabV3Plus:
     exit rates (1,2), atrous rates (6,12,18))."""
 
     def __init__(self, weights: dict, classes=21, last_activation=None, backbone="xception", OS=16, decoder="full",
-                 first_upsample_size=(128, 128), class_prediction=True):
+                 first_upsample_size=(128, 128), class_prediction=True, dtype=F32):
         """decoder: "full" (Decoder, model.py:235-259) | "dcnn" (Decoder_only_DCNN, :261-280) | "aspp"
-        (Decoder_only_ASPP, :282-294); class_prediction=False: no logits layer (model.py:100-106)."""
+        (Decoder_only_ASPP, :282-294); class_prediction=False: no logits layer (model.py:100-106).
+        dtype: the arithmetic of every layer (torch.float64: the high-precision yardstick of the model-level accuracy
+        tests; the float32 weights and images convert exactly).  Resize weights keep TF's float32 scale computation."""
         self.decoder, self.first_upsample_size, self.class_prediction = decoder, tuple(first_upsample_size), class_prediction
-        self.w = {k: torch.as_tensor(np.asarray(v, dtype=np.float32)) for k, v in weights.items()}
+        self.dtype = dtype
+        self.w = {k: torch.as_tensor(np.asarray(v, dtype=np.float32)).to(dtype) for k, v in weights.items()}
         self.classes = classes
         self.last_activation = last_activation
         self.backbone = backbone
@@ -158,7 +161,7 @@ class OracleDeeplabV3Plus:
 
     # ---- model.py:64-147 ------------------------------------------------------------------
     def forward(self, images_nhwc, final_upsample=False, return_stages=False):
-        x = torch.as_tensor(np.asarray(images_nhwc, dtype=np.float32)).permute(0, 3, 1, 2).contiguous()
+        x = torch.as_tensor(np.asarray(images_nhwc, dtype=np.float32)).to(self.dtype).permute(0, 3, 1, 2).contiguous()
         in_hw = x.shape[2:]
         stages = {}
         if self.backbone == "mobilenet":

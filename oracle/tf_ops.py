@@ -172,16 +172,17 @@ def _interp_weights(out_size, in_size):
 def resize_bilinear(images, size):
     """tf.image.resize(images, size) default method (bilinear, antialias=False).
     images [N,H,W,C] -> [N,size[0],size[1],C].  TF resize_bilinear_op compute_lerp:
-    top = tl + (tr - tl) * xl ; bottom = bl + (br - bl) * xl ; out = top + (bottom - top) * yl."""
-    img = _t(images)
+    top = tl + (tr - tl) * xl ; bottom = bl + (br - bl) * xl ; out = top + (bottom - top) * yl.
+    A float64 tensor is resized in float64 (TF's float32 lerp weights, converted exactly); anything else in float32."""
+    img = _t(images, images.dtype if isinstance(images, torch.Tensor) and images.dtype == torch.float64 else F32)
     n, h, w, c = img.shape
     ho, wo = int(size[0]), int(size[1])
     ylo, yhi, yl = _interp_weights(ho, h)
     xlo, xhi, xl = _interp_weights(wo, w)
     ylo_t, yhi_t = torch.from_numpy(ylo), torch.from_numpy(yhi)
     xlo_t, xhi_t = torch.from_numpy(xlo), torch.from_numpy(xhi)
-    yl_t = torch.from_numpy(yl).reshape(1, ho, 1, 1)
-    xl_t = torch.from_numpy(xl).reshape(1, 1, wo, 1)
+    yl_t = torch.from_numpy(yl).reshape(1, ho, 1, 1).to(img.dtype)
+    xl_t = torch.from_numpy(xl).reshape(1, 1, wo, 1).to(img.dtype)
     top_rows = img[:, ylo_t]
     bot_rows = img[:, yhi_t]
     tl = top_rows[:, :, xlo_t]

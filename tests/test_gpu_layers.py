@@ -1,14 +1,19 @@
 """GPU parity of the DeepLabV3+ layer kernels (through the C ABI) against plain torch-CPU float32 /
-float64 references of the same op.  Tolerances: f32 MFMA == k-ordered fmaf chain, so GEMM-like
-outputs are compared with rtol 1e-4 / atol 1e-4 against a float64 reference (K <= 2048, O(1)
-operands); memory-bound layers with atol 1e-5."""
+float64 references of the same op.  Tolerances: GEMM-like outputs are compared with rtol 1e-4 / atol 1e-4
+against a float64 reference (K <= 2048, O(1) operands); memory-bound layers with atol 1e-5.  The split-f16
+GEMMs are held to 4e-6 of sum |x||w|; the exact-f32 MFMA GEMM is held to bit equality with the k-ordered fmaf
+chain that tests/f32_exact.py replays (test_pwconv_split_f16_is_f32_grade; the full bit-exact and 2^k
+equivariance coverage of the exact-f32 path is in tests/test_gpu_exact_f32.py)."""
 import os
+import sys
 
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))      # tests/f32_exact.py, whatever pytest's import mode
+import f32_exact as fx  # noqa: E402
 from oracle import tf_ops
 
 pytestmark = pytest.mark.gpu
@@ -71,10 +76,16 @@ def test_pwconv_split_f16_is_f32_grade(dev, m, k, n, relu, res):
                      residual=ops.to_device(r) if res else None, f16x3=True).cpu().numpy()
     err = np.abs(got - ref) / bound
     assert err.max() <= 4e-6, err.max()
-    # the plain f32 MFMA kernel on the same data, for scale
+    # the plain f32 MFMA kernel on the same data: within the same bound, and bit for bit the fmaf chain of
+    # tests/f32_exact.py (replayed on the first and last 32 rows and 32 more, every column: the CPU replay of all M rows
+    # at K = 2048 would take minutes)
     got32 = ops.pwconv(ops.to_device(x), ops.pack_pw_weights(ops.to_device(w)), ops.to_device(b), k, n, relu=relu,
                        residual=ops.to_device(r) if res else None).cpu().numpy()
     assert (np.abs(got32 - ref) / bound).max() <= 4e-6
+    rows = np.unique(np.concatenate([np.arange(min(m, 32)), np.arange(max(m - 32, 0), m), rng.integers(0, m, 32)]))
+    exact = fx.pwconv_exact(x[rows], w, b, int(relu), r[rows] if res else None)
+    assert np.array_equal(got32[rows].view(np.uint32), exact.view(np.uint32)), \
+        f"{int((got32[rows] != exact).sum())} outputs of the exact-f32 GEMM differ from the fmaf chain"
 
 
 def test_pwconv_asymmetric_identity(dev):

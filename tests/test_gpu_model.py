@@ -20,37 +20,47 @@ def synthetic():
     return W.make_synthetic_weights(seed=1234, classes=21)
 
 
+# Model-level error against the FLOAT64 oracle, max |got - ref| / max |ref|, per GEMM arithmetic.  Measured on MI355X (seed-1234
+# synthetic Xception weights): OS 16 at 64 x 96, batch 3: f32 9.4e-7, f16x3 1.37e-6; OS 8 at 64 x 64, batch 2: f32 6.5e-7,
+# f16x3 7.7e-7 (the float32 oracle itself: 7.0e-7 / 5.0e-7).  Bounds ~4x the larger of the two measurements.
+LOGIT_BOUND = {"f32": 4e-6, "f16x3": 6e-6}
+
+
 @pytest.mark.parametrize("precision", ["f32", "f16x3"])
 def test_engine_logits_match_oracle(dev, synthetic, precision):
-    """Both GEMM arithmetics: exact-f32 MFMA and the split-f16 MFMA (f32-grade by construction)."""
+    """Both GEMM arithmetics, exact-f32 MFMA and the split-f16 MFMA, against the float64 oracle with a bound per precision
+    (LOGIT_BOUND)."""
     from asr_amd.model import DeeplabModel
     rng = np.random.default_rng(21)
     x = rng.random((3, 64, 96, 3), dtype=np.float32)
-    ref = OracleDeeplabV3Plus(synthetic).forward(x)
+    ref = OracleDeeplabV3Plus(synthetic, dtype=torch.float64).forward(x)
     model = DeeplabModel(synthetic, (64, 96, 3), 21, final_upsample=False, last_activation=None, precision=precision)
     assert model.precision == precision
     got = model.predict(x, batch_size=2)                      # 2 + 1: exercises two plans
     assert got.shape == ref.shape == (3, 16, 24, 21)
-    scale = np.abs(ref).max()
+    err = np.abs(got - ref).max() / np.abs(ref).max()
     # float32 end to end, BN folded and ReLU/Add fused: differences are rounding only
-    np.testing.assert_allclose(got, ref, rtol=0, atol=2e-4 * scale)
+    assert err <= LOGIT_BOUND[precision], err
     agree = (got.argmax(-1) == ref.argmax(-1)).mean()
     assert agree >= 0.999, agree
 
 
 def test_xception_os8_matches_oracle(dev, synthetic):
     """model.py:42-47: OS = 8 -- entry block 3 at stride 1, middle flow dilated by 2, exit flow by (2, 4), ASPP rates
-    (12, 24, 36); same weights, same decoder."""
+    (12, 24, 36); same weights, same decoder.  Both GEMM arithmetics against the float64 oracle (LOGIT_BOUND)."""
     from asr_amd.model import DeeplabModel
     rng = np.random.default_rng(23)
     x = rng.random((2, 64, 64, 3), dtype=np.float32)
-    ref, st = OracleDeeplabV3Plus(synthetic, OS=8).forward(x, return_stages=True)
+    ref, st = OracleDeeplabV3Plus(synthetic, OS=8, dtype=torch.float64).forward(x, return_stages=True)
     assert st["exit"].shape == (2, 8, 8, 2048)                       # 64 / 8
-    model = DeeplabModel(synthetic, (64, 64, 3), 21, final_upsample=False, last_activation=None, OS=8)
-    assert model.name == "DLV3Plus-xception-OS8"
-    got = model.predict(x, batch_size=2)
-    assert got.shape == ref.shape == (2, 16, 16, 21)
-    np.testing.assert_allclose(got, ref, rtol=0, atol=2e-4 * np.abs(ref).max())
+    for precision in ("f32", "f16x3"):
+        model = DeeplabModel(synthetic, (64, 64, 3), 21, final_upsample=False, last_activation=None, OS=8, precision=precision)
+        assert model.name == "DLV3Plus-xception-OS8"
+        got = model.predict(x, batch_size=2)
+        assert got.shape == ref.shape == (2, 16, 16, 21)
+        err = np.abs(got - ref).max() / np.abs(ref).max()
+        assert err <= LOGIT_BOUND[precision], (precision, err)
+        assert (got.argmax(-1) == ref.argmax(-1)).mean() >= 0.999
 
 
 @pytest.mark.parametrize("kw,name,shape", [

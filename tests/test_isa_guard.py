@@ -8,6 +8,7 @@ brings the form in, or packed-f32 of any form into a kernel that did not opt in.
 """
 import importlib.util
 import os
+import re
 
 import pytest
 
@@ -151,3 +152,80 @@ def test_the_rules_catch_a_library_that_breaks_them(guard, tmp_path):
     erratum = [(k, i) for k, i, r in bad if r.startswith("ERRATUM")]
     assert len(erratum) > 50
     assert any("sr_forward_residual_kernel" in k for k, _i in erratum)
+
+
+# ---- the exact-f32 path carries no f16 arithmetic ------------------------------------------------------------------
+# Kernel families launched by the exact-f32 entry points (precision="f32" and the range guard's fallback):
+# asr_pwconv_mfma_f32 / asr_conv3x3_mfma_f32 (pw_gemm_kernel, pack_weights_kernel), asr_conv3x3_direct_f32,
+# asr_dwconv3x3_nhwc_f32 (dw_direct / dw_stream / dw_stream_full with SPLIT = false), asr_aspp_dwconv3_nhwc_f32
+# (aspp_dw3_phase_kernel<false>), asr_gap_f32, asr_resize_bilinear_f32, the warps, asr_augment_copies_f32, the realigns and
+# asr_sr_forward_residual_f32.  Split instantiations are told apart by their template argument, never by a name prefix.
+def _split_arg_is_false(args):
+    return args[4] == "false"                    # dw_stream_full_kernel<R, S, SROWS, PF, SPLIT, ACT>
+
+
+EXACT_F32_KERNELS = {
+    "pw_gemm_kernel": None, "pack_weights_kernel": None, "conv3x3_direct_kernel": None, "dw_direct_kernel": None,
+    "dw_stream_kernel": None, "dw_stream_full_kernel": _split_arg_is_false, "aspp_dw3_phase_kernel": lambda a: a == ["false"],
+    "gap_kernel": None, "resize_bilinear_kernel": None, "resize_bilinear_x4_kernel": None, "warp_affine_kernel": None,
+    "augment_copies_kernel": None, "sr_realign_kernel": None, "sr_forward_residual_kernel": None,
+}
+def _is_f16_op(op):
+    """An f16 / bf16 conversion, arithmetic or MFMA opcode (v_cvt_*f16*, v_cvt_pk_*, *_f16, *bf16*, v_mfma_*f16*, and the mixed
+    f16/f32 fmas whose names do not say f16)."""
+    return "f16" in op or op.startswith(("v_cvt_pk_", "v_fma_mix", "v_mad_mix"))
+
+
+def _demangled_kernels(guard):
+    import shutil
+    import subprocess
+    cxxfilt = shutil.which("c++filt")
+    if cxxfilt is None:
+        pytest.skip("c++filt (binutils) not installed")
+    kernels = guard.disassemble(os.path.join(PKG, "libasr_hip.so"))
+    names = sorted(kernels)
+    plain = subprocess.run([cxxfilt], input="\n".join(names), text=True, stdout=subprocess.PIPE, check=True).stdout.splitlines()
+    return {p: kernels[n] for n, p in zip(names, plain)}
+
+
+def _family(demangled):
+    """(kernel name, [template arguments]) of a demangled symbol such as
+    'void (anonymous namespace)::dw_stream_full_kernel<1, 2, 16, 4, false, 0>((anonymous namespace)::DwArgs, int)'."""
+    m = re.search(r"::(\w+)(?:<([^<>]*)>)?\(", demangled)
+    if not m:
+        return None, []
+    return m.group(1), [a.strip() for a in m.group(2).split(",")] if m.group(2) else []
+
+
+def test_the_f16_opcode_rule_is_exact():
+    for op in ("v_cvt_f16_f32_e32", "v_cvt_f32_f16_sdwa", "v_cvt_pk_f16_f32", "v_mfma_f32_32x32x16_f16", "v_mfma_f32_16x16x32_bf16",
+               "v_fma_mix_f32", "v_pk_fma_f16", "v_add_f16_e32", "v_cvt_pk_bf16_f32", "v_dot2_f32_f16"):
+        assert _is_f16_op(op), op
+    for op in ("v_fma_f32", "v_mfma_f32_32x32x2_f32", "v_pk_fma_f32", "v_cvt_f32_i32_e32", "v_add_f32_e32", "v_pk_mov_b32",
+               "v_cvt_i32_f32_e32", "global_load_dwordx4"):
+        assert not _is_f16_op(op), op
+
+
+def test_exact_f32_kernels_have_no_f16_arithmetic_and_no_mode_write(guard):
+    """The exact-f32 kernels must be f16-free: no conversion to or from f16 / bf16, no f16 arithmetic or f16 MFMA, and no
+    MODE write (the split kernels switch the f16 overflow clamp on).  Checked on the library that was built, so a kernel
+    that quietly converts through f16 fails here before any GPU run; the split instantiations of the same templates are
+    shown to hold such instructions, so the check can see them."""
+    kernels = _demangled_kernels(guard)
+    seen, split_seen, bad = set(), set(), []
+    for name, insts in kernels.items():
+        fam, args = _family(name)
+        if fam not in EXACT_F32_KERNELS:
+            continue
+        pred = EXACT_F32_KERNELS[fam]
+        f16 = [i for i in insts if i and _is_f16_op(i.split()[0])]
+        mode = [i for i in insts if i.startswith("s_setreg")]
+        if pred is not None and not pred(args):
+            if f16 and mode:
+                split_seen.add(fam)
+            continue
+        seen.add(fam)
+        bad += [(name, i) for i in f16 + mode]
+    assert seen == set(EXACT_F32_KERNELS), f"exact-f32 kernels not found in the library: {set(EXACT_F32_KERNELS) - seen}"
+    assert split_seen == {"dw_stream_full_kernel", "aspp_dw3_phase_kernel"}, split_seen
+    assert not bad, "\n".join(f"{i}    in {n}" for n, i in bad[:20])
