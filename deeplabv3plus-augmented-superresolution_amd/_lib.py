@@ -76,6 +76,8 @@ SIGNATURES = {
     "asr_threshold_f32": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _fl, _i, _vp]),
     "asr_iou_counts_i32": (_i, [_vp, _vp, _vp, _i64, _i, _i, _i, _vp]),
     "asr_iou_counts_shared_truth_i32": (_i, [_vp, _vp, _vp, _i64, _i, _i, _i, _vp]),
+    "asr_threshold_sweep_workspace_bytes": (_sz, [_i, _i]),
+    "asr_threshold_sweep_iou_counts_f32": (_i, [_vp, _vp, _vp, _vp, _sz, _vp, _i64, _i, _i, _i, _i, _i, _vp]),
     "asr_minmax_normalize_f32": (_i, [_vp, _vp, _vp, _i64, _i, _fl, _fl, _vp]),
     "asr_standard_mask_i32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "asr_class_counts_i32": (_i, [_vp, _vp, _vp, _i64, _i, _vp]),

@@ -211,6 +211,123 @@ __global__ __launch_bounds__(256) void iou_counts_kernel(const int32_t* __restri
     }
 }
 
+// ---- threshold sweep: IoU counts of K threshold factors in one pass (threshold_tests.py:113-121) ------------------
+// counts[s][k] equals asr_threshold_f32(image_s, NULL, factors[k]) followed by asr_iou_counts_i32: the pixel is predicted
+// class_id when v > max_s * factors[k] (f32 product, strict >), else 0.  Each workgroup ranks the K thresholds in LDS
+// (ties broken by factor index, so the ranks are a permutation of 0..K-1) and for each pixel finds r = #{thresholds < v}
+// by binary search: the pixel is "on" for factor k exactly when rank[k] < r.  It bumps a histogram over (truth category,
+// r), the category being the bits truth == class_id and truth == 0 after the include_bg remap; the finalize kernel turns
+// the histograms into counts through per-rank prefix sums.  A negative maximum reverses the threshold order against the
+// factor order; ranking the thresholds themselves covers that.  NaN inputs keep every index in range but are not exact.
+constexpr int kSweepMaxFactors = 256;
+constexpr int kSweepCats = 4;
+
+// th[k] = mx * factors[k], sorted[rank[k]] = th[k]; every thread of the block takes part
+__device__ __forceinline__ void sweep_rank(const float* __restrict__ factors, float mx, int K, float* __restrict__ th,
+                                           int* __restrict__ rank, float* __restrict__ sorted) {
+    for (int k = threadIdx.x; k < K; k += blockDim.x) th[k] = mx * factors[k];
+    __syncthreads();
+    for (int k = threadIdx.x; k < K; k += blockDim.x) {
+        const float t = th[k];
+        int r = 0;
+        for (int j = 0; j < K; ++j) r += (th[j] < t) || (th[j] == t && j < k);
+        r = r < K ? r : K - 1;                         // only NaN thresholds could break the permutation; keep it in range
+        rank[k] = r;
+        sorted[r] = t;
+    }
+    __syncthreads();
+}
+
+__global__ __launch_bounds__(256) void threshold_sweep_hist_kernel(const float* __restrict__ img, const int32_t* __restrict__ truth,
+                                                                   const float* __restrict__ factors,
+                                                                   const float* __restrict__ seg_minmax,
+                                                                   unsigned long long* __restrict__ hist, int64_t per_seg,
+                                                                   int64_t truth_stride, int K, int class_id, int include_bg) {
+    __shared__ float th[kSweepMaxFactors], sorted[kSweepMaxFactors];
+    __shared__ int rank[kSweepMaxFactors];
+    __shared__ unsigned int sub[4][kSweepCats * (kSweepMaxFactors + 1)];     // one sub-histogram per wave
+    const int seg = blockIdx.y;
+    const int bins = kSweepCats * (K + 1);
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    for (int i = threadIdx.x; i < 4 * kSweepCats * (kSweepMaxFactors + 1); i += 256) (&sub[0][0])[i] = 0u;
+    sweep_rank(factors, seg_minmax[seg * 2 + 1], K, th, rank, sorted);
+    const float* p = img + (int64_t)seg * per_seg;
+    const int32_t* t = truth + (int64_t)seg * truth_stride;              // truth_stride 0: one label map for every image
+    unsigned int* h = sub[wave];
+    // the trip count is uniform over the workgroup, so every lane of a wave reaches the shuffle below together
+    for (int64_t i0 = (int64_t)blockIdx.x * 256; i0 < per_seg; i0 += (int64_t)gridDim.x * 256) {
+        const int64_t i = i0 + threadIdx.x;
+        int key = -1;
+        if (i < per_seg) {
+            const float v = p[i];
+            int lo = 0, hi = K;
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if (sorted[mid] < v) lo = mid + 1; else hi = mid;
+            }
+            int tv = t[i];
+            if (include_bg && tv != class_id) tv = 0;  // utils.py:188-190
+            const int cat = (tv == class_id ? 1 : 0) | (tv == 0 ? 2 : 0);
+            key = cat * (K + 1) + lo;
+        }
+        // most pixels of a wave share one bin (r == 0 on the background): the lanes of lane 0's bin add once, by popcount
+        const int lead = __shfl(key, 0, 64);
+        const unsigned long long same = __ballot(key == lead);
+        if (key == lead) {
+            if (key >= 0 && lane == __ffsll((long long)same) - 1) atomicAdd(h + key, (unsigned int)__popcll(same));
+        } else if (key >= 0) {
+            atomicAdd(h + key, 1u);
+        }
+    }
+    __syncthreads();
+    unsigned long long* g = hist + (int64_t)seg * bins;
+    for (int b = threadIdx.x; b < bins; b += 256) {
+        const unsigned long long v = (unsigned long long)sub[0][b] + sub[1][b] + sub[2][b] + sub[3][b];
+        if (v) atomicAdd(g + b, v);
+    }
+}
+
+// one workgroup per image, one thread per factor: the pixels of category c that are "off" for factor k are those with
+// r <= rank[k] (a prefix of the histogram), the others are "on"
+__global__ __launch_bounds__(256) void threshold_sweep_finalize_kernel(const float* __restrict__ factors,
+                                                                       const float* __restrict__ seg_minmax,
+                                                                       const unsigned long long* __restrict__ hist,
+                                                                       long long* __restrict__ counts, int K, int class_id) {
+    __shared__ float th[kSweepMaxFactors], sorted[kSweepMaxFactors];
+    __shared__ int rank[kSweepMaxFactors];
+    __shared__ unsigned long long pre[kSweepCats * (kSweepMaxFactors + 1)];
+    const int seg = blockIdx.x;
+    const int bins = kSweepCats * (K + 1);
+    const unsigned long long* hs = hist + (int64_t)seg * bins;
+    for (int b = threadIdx.x; b < bins; b += 256) pre[b] = hs[b];
+    sweep_rank(factors, seg_minmax[seg * 2 + 1], K, th, rank, sorted);     // (its barriers also publish pre[])
+    if (threadIdx.x < kSweepCats) {                                        // inclusive prefix sums, one category per thread
+        unsigned long long run = 0;
+        for (int r = 0; r <= K; ++r) {
+            run += pre[threadIdx.x * (K + 1) + r];
+            pre[threadIdx.x * (K + 1) + r] = run;
+        }
+    }
+    __syncthreads();
+    // what the thresholded mask holds: class_id when on, 0 when off (class_id == 0: always 0)
+    const bool on_c = true, on_b = class_id == 0, off_c = class_id == 0, off_b = true;
+    for (int k = threadIdx.x; k < K; k += 256) {
+        const int q = rank[k];
+        unsigned long long ic = 0, uc = 0, ib = 0, ub = 0;
+        for (int cat = 0; cat < kSweepCats; ++cat) {
+            const unsigned long long off = pre[cat * (K + 1) + q];
+            const unsigned long long on = pre[cat * (K + 1) + K] - off;
+            const bool tc = cat & 1, tb = (cat >> 1) & 1;
+            ic += (tc && on_c ? on : 0) + (tc && off_c ? off : 0);
+            uc += (tc || on_c ? on : 0) + (tc || off_c ? off : 0);
+            ib += (tb && on_b ? on : 0) + (tb && off_b ? off : 0);
+            ub += (tb || on_b ? on : 0) + (tb || off_b ? off : 0);
+        }
+        long long* o = counts + ((int64_t)seg * K + k) * 4;
+        o[0] = (long long)ic; o[1] = (long long)uc; o[2] = (long long)ib; o[3] = (long long)ub;
+    }
+}
+
 // ---- per-label counts for Mean_IOU (utils.py:151-177) -----------------------------------------------------------
 // counts[seg][0][l] = |truth == l|, [1][l] = |pred == l|, [2][l] = |truth == l & pred == l| for labels 0..255
 // (union = [0] + [1] - [2]); labels outside 0..255 are not counted.
@@ -387,6 +504,47 @@ extern "C" int asr_iou_counts_shared_truth_i32(const int32_t* truth, const int32
                                                int num_preds, int class_id, int include_bg, asr_stream_t stream) {
     return iou_counts_common("asr_iou_counts_shared_truth_i32", truth, preds, counts, pixels, 0, num_preds, class_id,
                              include_bg, stream);
+}
+
+extern "C" size_t asr_threshold_sweep_workspace_bytes(int segments, int num_factors) {
+    if (segments <= 0 || num_factors <= 0) return 0;
+    return sizeof(unsigned long long) * kSweepCats * (size_t)(num_factors + 1) * (size_t)segments +
+           sizeof(float) * 2 * (size_t)segments;
+}
+
+extern "C" int asr_threshold_sweep_iou_counts_f32(const float* images, const int32_t* truth, const float* factors,
+                                                  void* workspace, size_t workspace_bytes, int64_t* counts,
+                                                  int64_t per_segment, int segments, int num_factors, int shared_truth,
+                                                  int class_id, int include_bg, asr_stream_t stream) {
+    ASR_REQUIRE(images && truth && factors && workspace && counts, "asr_threshold_sweep_iou_counts_f32: null pointer");
+    ASR_REQUIRE(per_segment > 0 && segments > 0 && segments <= 65535,
+                "asr_threshold_sweep_iou_counts_f32: bad shape (per_segment=%lld, segments=%d; at most 65535 segments)",
+                (long long)per_segment, segments);
+    ASR_REQUIRE(num_factors >= 1 && num_factors <= kSweepMaxFactors,
+                "asr_threshold_sweep_iou_counts_f32: %d threshold factors (1..%d)", num_factors, kSweepMaxFactors);
+    const size_t need = asr_threshold_sweep_workspace_bytes(segments, num_factors);
+    if (workspace_bytes < need) {
+        asr_set_error("asr_threshold_sweep_iou_counts_f32: workspace of %zu bytes, %zu needed", workspace_bytes, need);
+        return ASR_ERR_WORKSPACE;
+    }
+    hipStream_t s = asr_stream(stream);
+    auto* hist = reinterpret_cast<unsigned long long*>(workspace);
+    const size_t hist_bytes = sizeof(unsigned long long) * kSweepCats * (size_t)(num_factors + 1) * (size_t)segments;
+    float* minmax = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + hist_bytes);
+    int rc = asr_minmax_f32(images, minmax, per_segment, segments, stream);
+    if (rc != ASR_OK) return rc;
+    ASR_HIP_CHECK(hipMemsetAsync(hist, 0, hist_bytes, s));
+    // 64..256 workgroups per image, fewer per image as the images get more: each one flushes its own histogram
+    int per_image = 1024 / segments;
+    per_image = per_image < 64 ? 64 : (per_image > 256 ? 256 : per_image);
+    const int grid = stream_grid(per_segment) > per_image ? per_image : stream_grid(per_segment);
+    hipLaunchKernelGGL(threshold_sweep_hist_kernel, dim3(grid, segments), dim3(256), 0, s, images, truth, factors, minmax, hist,
+                       per_segment, shared_truth ? (int64_t)0 : per_segment, num_factors, class_id, include_bg);
+    ASR_LAUNCH_CHECK();
+    hipLaunchKernelGGL(threshold_sweep_finalize_kernel, dim3(segments), dim3(256), 0, s, factors, minmax, hist,
+                       reinterpret_cast<long long*>(counts), num_factors, class_id);
+    ASR_LAUNCH_CHECK();
+    return ASR_OK;
 }
 
 extern "C" int asr_minmax_normalize_f32(const float* x, float* out, float* minmax_ws, int64_t per_segment, int segments,

@@ -380,6 +380,36 @@ def iou_counts(truth, pred, class_id, include_bg=False, segments=1):
     return counts
 
 
+MAX_SWEEP_FACTORS = 256
+
+
+def threshold_sweep_iou_counts(images, truth, factors, class_id, include_bg=False):
+    """images [S, ...] float32 -> int64 [S, K, 4]: counts[s, k] = iou_counts(truth_s, threshold(images[s], class_id,
+    th_factor=factors[k])) for every factor, in one pass over the images (asr_threshold_sweep_iou_counts_f32).  truth: int32
+    with the pixel count of ONE image (shared by all) or of all S images (one label map each)."""
+    s = images.shape[0] if images.dim() > 1 else 1
+    per = images.numel() // s if s else 0
+    if s == 0 or per == 0 or per * s != images.numel():
+        raise AsrError("threshold_sweep_iou_counts: images must be a non-empty [S, ...] stack")
+    if truth.numel() == per:
+        shared = 1
+    elif truth.numel() == per * s:
+        shared = 0
+    else:
+        raise AsrError(f"threshold_sweep_iou_counts: truth has {truth.numel()} pixels, expected {per} or {per * s}")
+    f = to_device(np.asarray(factors, dtype=np.float32).reshape(-1), device=images.device)
+    k = f.numel()
+    if not 1 <= k <= MAX_SWEEP_FACTORS:
+        raise AsrError(f"threshold_sweep_iou_counts: {k} threshold factors (1..{MAX_SWEEP_FACTORS})")
+    lib = _lib.load()
+    ws_bytes = lib.asr_threshold_sweep_workspace_bytes(s, k)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=images.device)
+    counts = torch.empty((s, k, 4), dtype=torch.int64, device=images.device)
+    call("asr_threshold_sweep_iou_counts_f32", ptr(images), ptr(truth, torch.int32), ptr(f), ptr(ws, torch.uint8), ws_bytes,
+         ptr(counts, torch.int64), per, s, k, shared, int(class_id), int(bool(include_bg)), stream_ptr())
+    return counts
+
+
 # ---------------------------------------------------------------------------------------------
 # model layers
 # ---------------------------------------------------------------------------------------------

@@ -124,6 +124,21 @@ def threshold_image(image, th_value, th_factor=.15, th_mask=None):
     return out if was_tensor else out.cpu().numpy()
 
 
+def threshold_sweep_IoU(true_image, image, class_id, th_factors, include_bg=False):
+    """float64 [K]: the single-class IoU of ``image`` thresholded at each factor of ``th_factors`` (threshold_tests.py:113-121),
+    i.e. ``[compute_IoU(true_image, threshold_image(image, class_id, th_factor=f), class_id=class_id, include_bg=include_bg)
+    for f in th_factors]``, from one pass over the image for all factors (asr_threshold_sweep_iou_counts_f32)."""
+    from ..utils import _as_label_tensor, iou_from_counts
+    dev = _lib.require_gpu()
+    img = image if isinstance(image, torch.Tensor) else torch.as_tensor(np.asarray(image, dtype=np.float32))
+    img = img.to(device=dev, dtype=torch.float32).contiguous().reshape(1, -1)
+    truth = _as_label_tensor(true_image, dev)
+    if truth.numel() != img.numel():
+        raise ValueError(f"expected {img.numel()} pixels in the label map, got {truth.numel()}")
+    counts = ops.threshold_sweep_iou_counts(img, truth, th_factors, class_id, include_bg=include_bg).cpu().numpy()[0]
+    return np.array([iou_from_counts(c, include_bg) for c in counts], dtype=np.float64)
+
+
 # ---- interchange file (augmentation_utils.py:117-136 writer, superres_utils.py:154-210 reader) -------
 def save_SR_data(path_without_ext, class_masks, max_masks, angles, shifts, filename, mode, angle_max, shift_max, ext=None):
     ext = ext or DATA_EXT

@@ -230,6 +230,19 @@ int asr_iou_counts_i32(const int32_t* truth, const int32_t* pred, int64_t* count
 int asr_iou_counts_shared_truth_i32(const int32_t* truth, const int32_t* preds, int64_t* counts, int64_t pixels, int num_preds,
                                     int class_id, int include_bg, asr_stream_t stream);
 
+/* Threshold sweep (threshold_tests.py:113-121): for S images [segments, per_segment] and K = num_factors threshold factors
+ * [K] (device floats, any order, repeats allowed), counts[s][k] = {inter_c, union_c, inter_bg, union_bg} equals, bit for bit,
+ * asr_threshold_f32(image_s, NULL, factors[k], class_id) followed by asr_iou_counts_i32(truth_s, ., class_id, include_bg):
+ * the threshold is the f32 product max(image_s) * factors[k] and the comparison is strict.  truth: [per_segment] shared by
+ * every image (shared_truth != 0) or [segments, per_segment].  One pass over the images for all K factors; exact for
+ * finite images.  1 <= K <= 256, segments <= 65535.  workspace: asr_threshold_sweep_workspace_bytes(segments, K) bytes
+ * (histograms + per-image extrema), fully rewritten by each call. */
+size_t asr_threshold_sweep_workspace_bytes(int segments, int num_factors);
+int asr_threshold_sweep_iou_counts_f32(const float* images, const int32_t* truth, const float* factors, void* workspace,
+                                       size_t workspace_bytes, int64_t* counts, int64_t per_segment, int segments,
+                                       int num_factors, int shared_truth, int class_id, int include_bg,
+                                       asr_stream_t stream);
+
 /* min_max_normalization of whole stacks with their own global extrema, as load_SR_data applies it to the argmax / slice_max
  * masks of an image (superres_utils.py:56-62, 183-206): per segment out = new_min + ((x - min) * (new_max - new_min)) /
  * (max - min, or 1 when they are equal).  minmax_ws: [segments, 2] floats of scratch (receives the extrema). */
