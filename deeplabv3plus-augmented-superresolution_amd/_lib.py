@@ -32,6 +32,9 @@ _i = C.c_int
 _i64 = C.c_int64
 _fl = C.c_float
 _sz = C.c_size_t
+_ip = C.POINTER(C.c_int)         # host int arrays read during the call (class sets)
+MAX_CLASS_SET = 32               # ASR_MAX_CLASS_SET
+OPM_MODES = {"argmax": 0, "slice": 1, "slice_max": 2}     # ASR_OPM_*
 
 OPT_ADAM, OPT_SGD, OPT_ADAGRAD, OPT_ADADELTA, OPT_ADAMAX = 0, 1, 2, 3, 4
 PRIOR_TV, PRIOR_BTV = 0, 1
@@ -80,6 +83,10 @@ SIGNATURES = {
     "asr_threshold_sweep_iou_counts_f32": (_i, [_vp, _vp, _vp, _vp, _sz, _vp, _i64, _i, _i, _i, _i, _i, _vp]),
     "asr_minmax_normalize_f32": (_i, [_vp, _vp, _vp, _i64, _i, _fl, _fl, _vp]),
     "asr_standard_mask_i32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "asr_opm_classes_f32": (_i, [_vp, _ip, _i, _i, _vp, _vp, _vp, _i, _i64, _i, _i64, _fl, _fl, _vp]),
+    "asr_threshold_classes_f32": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _fl, _ip, _vp]),
+    "asr_iou_counts_classes_i32": (_i, [_vp, _vp, _vp, _i64, _i, _i, _ip, _i, _vp]),
+    "asr_standard_mask_classes_i32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _ip, _i, _vp]),
     "asr_class_counts_i32": (_i, [_vp, _vp, _vp, _i64, _i, _vp]),
     "asr_pwconv_packed_floats": (_sz, [_i, _i]),
     "asr_pwconv_pack_weights_f32": (_i, [_vp, _vp, _i, _i, _vp]),

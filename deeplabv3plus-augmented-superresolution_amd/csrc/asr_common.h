@@ -64,6 +64,29 @@ static inline hipStream_t asr_stream(asr_stream_t s) { return reinterpret_cast<h
 
 static inline int64_t asr_cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// ---- class sets of the *_classes entry points --------------------------------------------------
+// K distinct class ids, copied from the caller's host array into a kernel argument (wave-uniform, read with scalar loads).
+struct AsrClassSet {
+    int n;
+    int id[ASR_MAX_CLASS_SET];
+};
+
+// Checks and copies a caller's set before any launch: 1 <= K <= ASR_MAX_CLASS_SET, ids distinct, each in [0, classes)
+// (classes <= 0: any id >= 0).  ASR_OK or ASR_ERR_INVALID_ARG with a message naming `fn`.
+static inline int asr_class_set(const char* fn, const int* ids, int K, int classes, AsrClassSet* set) {
+    ASR_REQUIRE(ids, "%s: null class id array", fn);
+    ASR_REQUIRE(K >= 1 && K <= ASR_MAX_CLASS_SET, "%s: %d class ids (1..%d)", fn, K, ASR_MAX_CLASS_SET);
+    set->n = K;
+    for (int k = 0; k < K; ++k) {
+        ASR_REQUIRE(ids[k] >= 0 && (classes <= 0 || ids[k] < classes), "%s: class id %d out of range [0, %d)", fn, ids[k],
+                    classes);
+        for (int j = 0; j < k; ++j) ASR_REQUIRE(ids[j] != ids[k], "%s: class id %d given twice", fn, ids[k]);
+        set->id[k] = ids[k];
+    }
+    for (int k = K; k < ASR_MAX_CLASS_SET; ++k) set->id[k] = -1;
+    return ASR_OK;
+}
+
 // ---- device helpers -------------------------------------------------------------------
 #ifdef __HIPCC__
 

@@ -501,11 +501,8 @@ __global__ __launch_bounds__(256) void resize_bilinear_x4_kernel(const float* __
 // Standard-output mask (generate_standard_output.py:52-65 with the model's final Resizing, model.py:108-111): bilinear
 // upsample of one logits map (half-pixel, the arithmetic of resize_bilinear_kernel), argmax over the classes (first
 // maximum), keep class_id else 0 -- one pass, the upsampled logits never exist.
-__global__ __launch_bounds__(256) void standard_mask_kernel(const float* __restrict__ logits, int* __restrict__ out, int h_in,
-                                                            int w_in, int classes, int h_out, int w_out, float scale_y,
-                                                            float scale_x, int class_id) {
-    const int ox = blockIdx.x * 256 + threadIdx.x, oy = blockIdx.y;
-    if (ox >= w_out) return;
+__device__ __forceinline__ int upsampled_argmax(const float* __restrict__ logits, int h_in, int w_in, int classes, float scale_y,
+                                                float scale_x, int ox, int oy) {
     const float py = ((float)oy + 0.5f) * scale_y - 0.5f, px = ((float)ox + 0.5f) * scale_x - 0.5f;
     const float fy = floorf(py), fx = floorf(px);
     const int ylo = max((int)fy, 0), yhi = min((int)ceilf(py), h_in - 1);
@@ -523,7 +520,28 @@ __global__ __launch_bounds__(256) void standard_mask_kernel(const float* __restr
         const float v = top + (bot - top) * ty;
         if (c == 0 || v > best) { best = v; arg = c; }
     }
+    return arg;
+}
+
+__global__ __launch_bounds__(256) void standard_mask_kernel(const float* __restrict__ logits, int* __restrict__ out, int h_in,
+                                                            int w_in, int classes, int h_out, int w_out, float scale_y,
+                                                            float scale_x, int class_id) {
+    const int ox = blockIdx.x * 256 + threadIdx.x, oy = blockIdx.y;
+    if (ox >= w_out) return;
+    const int arg = upsampled_argmax(logits, h_in, w_in, classes, scale_y, scale_x, ox, oy);
     out[(long long)oy * w_out + ox] = (arg == class_id) ? class_id : 0;
+}
+
+// The same for a class set (asr_standard_mask_classes_i32): one upsample + argmax per output pixel, K masks
+// [K, h_out, w_out].  Kept in this unit so that the interpolation compiles exactly as standard_mask_kernel's does.
+__global__ __launch_bounds__(256) void standard_mask_classes_kernel(const float* __restrict__ logits, int* __restrict__ out,
+                                                                    int h_in, int w_in, int classes, int h_out, int w_out,
+                                                                    float scale_y, float scale_x, AsrClassSet set) {
+    const int ox = blockIdx.x * 256 + threadIdx.x, oy = blockIdx.y;
+    if (ox >= w_out) return;
+    const int arg = upsampled_argmax(logits, h_in, w_in, classes, scale_y, scale_x, ox, oy);
+    const long long plane = (long long)h_out * w_out, o = (long long)oy * w_out + ox;
+    for (int k = 0; k < set.n; ++k) out[k * plane + o] = (arg == set.id[k]) ? set.id[k] : 0;
 }
 
 int cap_grid(long long total) {
@@ -637,6 +655,21 @@ extern "C" int asr_standard_mask_i32(const float* logits, int32_t* mask, int h_i
     const float sy = (float)h_in / (float)h_out, sx = (float)w_in / (float)w_out;
     hipLaunchKernelGGL(standard_mask_kernel, dim3((unsigned)asr_cdiv(w_out, 256), (unsigned)h_out), dim3(256), 0, asr_stream(stream),
                        logits, mask, h_in, w_in, classes, h_out, w_out, sy, sx, class_id);
+    ASR_LAUNCH_CHECK();
+    return ASR_OK;
+}
+
+extern "C" int asr_standard_mask_classes_i32(const float* logits0, int32_t* masks, int h_in, int w_in, int classes, int h_out,
+                                             int w_out, const int* ids, int K, asr_stream_t stream) {
+    AsrClassSet set;
+    const int rc = asr_class_set("asr_standard_mask_classes_i32", ids, K, classes, &set);
+    if (rc != ASR_OK) return rc;
+    ASR_REQUIRE(logits0 && masks, "asr_standard_mask_classes_i32: null pointer");
+    ASR_REQUIRE(h_in > 0 && w_in > 0 && classes > 0 && h_out > 0 && w_out > 0 && h_out <= 65535,
+                "asr_standard_mask_classes_i32: bad shape");
+    const float sy = (float)h_in / (float)h_out, sx = (float)w_in / (float)w_out;
+    hipLaunchKernelGGL(standard_mask_classes_kernel, dim3((unsigned)asr_cdiv(w_out, 256), (unsigned)h_out), dim3(256), 0,
+                       asr_stream(stream), logits0, masks, h_in, w_in, classes, h_out, w_out, sy, sx, set);
     ASR_LAUNCH_CHECK();
     return ASR_OK;
 }

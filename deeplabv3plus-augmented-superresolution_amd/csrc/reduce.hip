@@ -144,6 +144,57 @@ __global__ __launch_bounds__(256) void opm_slice_kernel(const float* __restrict_
     }
 }
 
+// ---- OPM of a class set (asr_opm_classes_f32) ---------------------------------------------------------------------
+// Each pixel's row is read once -- through LDS like argmax_kernel when it fits (STAGED), else straight from global memory --
+// and every class of the set gets the statements of its single-class kernel on it: argmax_row once per pixel, then one
+// compare per class (opm_argmax_kernel); opm_slice_kernel's per-copy constants and expression (SLICE, one copy per grid
+// row); opm_slice_max_kernel's fold over the other classes, in the same order, once per class (SLICE_MAX).  Plane k of the
+// output lies class_stride floats after plane k-1.  argmax / slice_max launch one "copy" of all pixels.
+template <int MODE, bool STAGED>
+__global__ __launch_bounds__(256) void opm_classes_kernel(const float* __restrict__ logits, float* __restrict__ cls,
+                                                          float* __restrict__ mx, const float* __restrict__ seg_minmax,
+                                                          int64_t per_copy, int classes, int64_t class_stride, AsrClassSet set,
+                                                          float new_min, float new_max) {
+    __shared__ float tile[STAGED ? 256 * kMaxStageClasses : 1];
+    const int copy = blockIdx.y;
+    const float* base = logits + (int64_t)copy * per_copy * classes;
+    const int64_t o0 = (int64_t)copy * per_copy;
+    float mn = 0.0f, den = 1.0f, span = 0.0f;
+    if (MODE == ASR_OPM_SLICE) {
+        mn = seg_minmax[copy * 2 + 0];
+        const float mxv = seg_minmax[copy * 2 + 1];
+        den = ((mxv - mn) != 0.0f) ? (mxv - mn) : 1.0f;
+        span = new_max - new_min;
+    }
+    for (int64_t first = (int64_t)blockIdx.x * 256; first < per_copy; first += (int64_t)gridDim.x * 256) {
+        const int64_t p = first + threadIdx.x;
+        const float* row = STAGED ? stage_rows(base, first, per_copy, classes, tile) : base + p * classes;
+        if (p < per_copy) {
+            float* c = cls + o0 + p;
+            if (MODE == ASR_OPM_ARGMAX) {
+                const int arg = argmax_row(row, classes);
+                for (int k = 0; k < set.n; ++k) c[k * class_stride] = (arg == set.id[k]) ? (float)set.id[k] : 0.0f;
+            } else if (MODE == ASR_OPM_SLICE) {
+                for (int k = 0; k < set.n; ++k) {
+                    const float num = (row[set.id[k]] - mn) * span;
+                    c[k * class_stride] = new_min + num / den;
+                }
+            } else {
+                float* m = mx + o0 + p;
+                for (int k = 0; k < set.n; ++k) {
+                    const int id = set.id[k];
+                    float best = -INFINITY;
+                    for (int j = 0; j < classes; ++j)
+                        if (j != id) best = fmaxf(best, row[j]);
+                    c[k * class_stride] = row[id];
+                    m[k * class_stride] = best;
+                }
+            }
+        }
+        if (STAGED) __syncthreads();
+    }
+}
+
 // ---- min_max_normalization of a stack with its own global minimum / maximum (load_SR_data, superres_utils.py:183-206) ----
 __global__ __launch_bounds__(256) void minmax_normalize_kernel(const float* __restrict__ x, float* __restrict__ out,
                                                                const float* __restrict__ seg_minmax, int64_t per_seg,
@@ -159,10 +210,9 @@ __global__ __launch_bounds__(256) void minmax_normalize_kernel(const float* __re
 }
 
 // ---- threshold_image -----------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void threshold_kernel(const float* __restrict__ img, const float* __restrict__ th_mask,
-                                                        const float* __restrict__ seg_minmax, int32_t* __restrict__ out,
-                                                        int64_t per_seg, float th_factor, int th_value) {
-    const int seg = blockIdx.y;
+__device__ __forceinline__ void threshold_segment(const float* __restrict__ img, const float* __restrict__ th_mask,
+                                                  const float* __restrict__ seg_minmax, int32_t* __restrict__ out,
+                                                  int64_t per_seg, float th_factor, int th_value, int seg) {
     const float* p = img + (int64_t)seg * per_seg;
     int32_t* o = out + (int64_t)seg * per_seg;
     if (th_mask) {
@@ -174,6 +224,19 @@ __global__ __launch_bounds__(256) void threshold_kernel(const float* __restrict_
         for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < per_seg; i += (int64_t)gridDim.x * 256)
             o[i] = (p[i] > th) ? th_value : 0;
     }
+}
+
+__global__ __launch_bounds__(256) void threshold_kernel(const float* __restrict__ img, const float* __restrict__ th_mask,
+                                                        const float* __restrict__ seg_minmax, int32_t* __restrict__ out,
+                                                        int64_t per_seg, float th_factor, int th_value) {
+    threshold_segment(img, th_mask, seg_minmax, out, per_seg, th_factor, th_value, blockIdx.y);
+}
+
+// segment k is thresholded to values.id[k] (asr_threshold_classes_f32)
+__global__ __launch_bounds__(256) void threshold_classes_kernel(const float* __restrict__ img, const float* __restrict__ th_mask,
+                                                                const float* __restrict__ seg_minmax, int32_t* __restrict__ out,
+                                                                int64_t per_seg, float th_factor, AsrClassSet values) {
+    threshold_segment(img, th_mask, seg_minmax, out, per_seg, th_factor, values.id[blockIdx.y], blockIdx.y);
 }
 
 // ---- IoU counts: counts[seg] = {inter_c, union_c, inter_bg, union_bg} ------------------------------
@@ -208,6 +271,49 @@ __global__ __launch_bounds__(256) void iou_counts_kernel(const int32_t* __restri
         const unsigned long long v = (unsigned long long)part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] +
                                      part[3][threadIdx.x];
         if (v) atomicAdd(counts + seg * 4 + threadIdx.x, v);
+    }
+}
+
+// ---- IoU counts of a class set: K classes x M masks against one label map, in one pass over it ---------------------
+// Each thread loads its truth pixel once; for every (class k, mask m) a wave counts the four predicates of iou_counts_kernel
+// by ballot and its lane 0 adds them to the wave's own LDS row (no atomics inside the workgroup).  Out-of-range lanes take
+// part in the ballots with every predicate false: the trip count is uniform over the workgroup.
+constexpr int kMaxIouMasks = 8;
+
+__global__ __launch_bounds__(256) void iou_counts_classes_kernel(const int32_t* __restrict__ truth, const int32_t* __restrict__ preds,
+                                                                 unsigned long long* __restrict__ counts, int64_t pixels, int M,
+                                                                 AsrClassSet set, int include_bg) {
+    __shared__ unsigned int part[4][ASR_MAX_CLASS_SET * kMaxIouMasks * 4];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int slots = set.n * M * 4;
+    for (int s = lane; s < slots; s += 64) part[wave][s] = 0u;
+    __syncthreads();
+    unsigned int* acc = part[wave];
+    for (int64_t i0 = (int64_t)blockIdx.x * 256; i0 < pixels; i0 += (int64_t)gridDim.x * 256) {
+        const int64_t i = i0 + threadIdx.x;
+        const bool in = i < pixels;
+        const int t0 = in ? truth[i] : 0;
+        for (int k = 0; k < set.n; ++k) {
+            const int id = set.id[k];
+            int tv = t0;
+            if (include_bg && tv != id) tv = 0;  // utils.py:188-190
+            const bool tc = in && tv == id, tb = in && tv == 0;
+            for (int m = 0; m < M; ++m) {
+                const int pv = in ? preds[((int64_t)k * M + m) * pixels + i] : 0;
+                const bool pc = in && pv == id, pb = in && pv == 0;
+                const unsigned int ic = __popcll(__ballot(tc && pc)), uc = __popcll(__ballot(tc || pc));
+                const unsigned int ib = __popcll(__ballot(tb && pb)), ub = __popcll(__ballot(tb || pb));
+                if (lane == 0) {
+                    unsigned int* a = acc + (k * M + m) * 4;
+                    a[0] += ic; a[1] += uc; a[2] += ib; a[3] += ub;
+                }
+            }
+        }
+    }
+    __syncthreads();
+    for (int s = threadIdx.x; s < slots; s += 256) {
+        const unsigned long long v = (unsigned long long)part[0][s] + part[1][s] + part[2][s] + part[3][s];
+        if (v) atomicAdd(counts + s, v);
     }
 }
 
@@ -504,6 +610,82 @@ extern "C" int asr_iou_counts_shared_truth_i32(const int32_t* truth, const int32
                                                int num_preds, int class_id, int include_bg, asr_stream_t stream) {
     return iou_counts_common("asr_iou_counts_shared_truth_i32", truth, preds, counts, pixels, 0, num_preds, class_id,
                              include_bg, stream);
+}
+
+extern "C" int asr_opm_classes_f32(const float* logits, const int* ids, int K, int mode, float* class_masks, float* max_masks,
+                                   float* minmax_ws, int copies, int64_t pixels_per_copy, int classes, int64_t class_stride,
+                                   float new_min, float new_max, asr_stream_t stream) {
+    AsrClassSet set;
+    int rc = asr_class_set("asr_opm_classes_f32", ids, K, classes, &set);
+    if (rc != ASR_OK) return rc;
+    ASR_REQUIRE(logits && class_masks, "asr_opm_classes_f32: null pointer");
+    ASR_REQUIRE(mode == ASR_OPM_ARGMAX || mode == ASR_OPM_SLICE || mode == ASR_OPM_SLICE_MAX,
+                "asr_opm_classes_f32: mode %d (0 argmax, 1 slice, 2 slice_max)", mode);
+    ASR_REQUIRE(copies > 0 && copies <= 65535 && pixels_per_copy > 0 && classes > 0, "asr_opm_classes_f32: bad shape");
+    const int64_t pixels = (int64_t)copies * pixels_per_copy;
+    ASR_REQUIRE(K == 1 || class_stride >= pixels, "asr_opm_classes_f32: class_stride %lld < %lld pixels (planes would overlap)",
+                (long long)class_stride, (long long)pixels);
+    hipStream_t s = asr_stream(stream);
+    const bool staged = classes <= kMaxStageClasses;
+#define ASR_OPM_CLASSES_LAUNCH(M, grid, per, ws)                                                                              \
+    do {                                                                                                                    \
+        if (staged)                                                                                                         \
+            hipLaunchKernelGGL((opm_classes_kernel<M, true>), grid, dim3(256), 0, s, logits, class_masks, max_masks, ws, per, \
+                               classes, class_stride, set, new_min, new_max);                                               \
+        else                                                                                                                \
+            hipLaunchKernelGGL((opm_classes_kernel<M, false>), grid, dim3(256), 0, s, logits, class_masks, max_masks, ws,     \
+                               per, classes, class_stride, set, new_min, new_max);                                          \
+    } while (0)
+    if (mode == ASR_OPM_ARGMAX) {
+        ASR_OPM_CLASSES_LAUNCH(ASR_OPM_ARGMAX, dim3(stream_grid(pixels)), pixels, nullptr);
+    } else if (mode == ASR_OPM_SLICE_MAX) {
+        ASR_REQUIRE(max_masks && classes > 1, "asr_opm_classes_f32: slice_max needs max_masks and classes > 1");
+        ASR_OPM_CLASSES_LAUNCH(ASR_OPM_SLICE_MAX, dim3(stream_grid(pixels)), pixels, nullptr);
+    } else {
+        ASR_REQUIRE(minmax_ws, "asr_opm_classes_f32: slice needs minmax_ws");
+        rc = asr_minmax_f32(logits, minmax_ws, pixels_per_copy * classes, copies, stream);     // once for all K classes
+        if (rc != ASR_OK) return rc;
+        ASR_OPM_CLASSES_LAUNCH(ASR_OPM_SLICE, dim3(stream_grid(pixels_per_copy), copies), pixels_per_copy, minmax_ws);
+    }
+#undef ASR_OPM_CLASSES_LAUNCH
+    ASR_LAUNCH_CHECK();
+    return ASR_OK;
+}
+
+extern "C" int asr_threshold_classes_f32(const float* image, const float* th_mask, float* minmax_ws, int32_t* out,
+                                         int64_t per_segment, int K, float th_factor, const int* th_values,
+                                         asr_stream_t stream) {
+    AsrClassSet values;
+    int rc = asr_class_set("asr_threshold_classes_f32", th_values, K, 0, &values);
+    if (rc != ASR_OK) return rc;
+    ASR_REQUIRE(image && out, "asr_threshold_classes_f32: null pointer");
+    ASR_REQUIRE(per_segment > 0, "asr_threshold_classes_f32: bad shape");
+    if (!th_mask) {
+        ASR_REQUIRE(minmax_ws, "asr_threshold_classes_f32: minmax workspace required without th_mask");
+        rc = asr_minmax_f32(image, minmax_ws, per_segment, K, stream);
+        if (rc != ASR_OK) return rc;
+    }
+    hipLaunchKernelGGL(threshold_classes_kernel, dim3(stream_grid(per_segment), K), dim3(256), 0, asr_stream(stream), image,
+                       th_mask, minmax_ws, out, per_segment, th_factor, values);
+    ASR_LAUNCH_CHECK();
+    return ASR_OK;
+}
+
+extern "C" int asr_iou_counts_classes_i32(const int32_t* truth, const int32_t* preds, int64_t* counts, int64_t pixels, int K,
+                                          int M, const int* ids, int include_bg, asr_stream_t stream) {
+    AsrClassSet set;
+    int rc = asr_class_set("asr_iou_counts_classes_i32", ids, K, 0, &set);
+    if (rc != ASR_OK) return rc;
+    ASR_REQUIRE(truth && preds && counts, "asr_iou_counts_classes_i32: null pointer");
+    ASR_REQUIRE(pixels > 0 && M >= 1 && M <= kMaxIouMasks, "asr_iou_counts_classes_i32: bad shape (pixels=%lld, M=%d; 1..%d masks)",
+                (long long)pixels, M, kMaxIouMasks);
+    hipStream_t s = asr_stream(stream);
+    ASR_HIP_CHECK(hipMemsetAsync(counts, 0, sizeof(int64_t) * 4 * (size_t)K * (size_t)M, s));
+    const int grid = stream_grid(pixels) > 128 ? 128 : stream_grid(pixels);
+    hipLaunchKernelGGL(iou_counts_classes_kernel, dim3(grid), dim3(256), 0, s, truth, preds,
+                       reinterpret_cast<unsigned long long*>(counts), pixels, M, set, include_bg);
+    ASR_LAUNCH_CHECK();
+    return ASR_OK;
 }
 
 extern "C" size_t asr_threshold_sweep_workspace_bytes(int segments, int num_factors) {

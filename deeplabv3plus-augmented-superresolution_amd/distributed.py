@@ -104,6 +104,20 @@ def adam_start_step(image_index, num_iter, mode="argmax"):
     return image_index * num_iter * (2 if mode == "slice_max" else 1)
 
 
+def solves_per_image(mode):
+    """Adam solves the reference runs per image and class: the class map, plus the max map in slice_max mode."""
+    return 2 if mode == "slice_max" else 1
+
+
+def adam_class_starts(presence, num_iter, mode="argmax"):
+    """presence [images, K] bool (image g's ground truth holds class k) -> int64 [images, K]: the global Adam ``iterations``
+    before class k's solve of image g in a per-class run over the images that hold k (SR_single_class.py over the filtered
+    list): num_iter * solves_per_image(mode) * #{images before g that hold k}."""
+    p = np.asarray(presence, dtype=np.int64)
+    before = np.cumsum(p, axis=0) - p
+    return before * (num_iter * solves_per_image(mode))
+
+
 def all_gather_rows(local_indices, local_rows, num_rows, width, device=None):
     """local_rows: [n_local, width] float64 rows of the global indices local_indices.  Returns the full
     [num_rows, width] table (NaN where no rank reported) on every rank via ONE all_gather of equal-sized slots."""

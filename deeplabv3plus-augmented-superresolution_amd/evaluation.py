@@ -84,6 +84,105 @@ def evaluate_precomputed(sr, paths, gt_dir, standard_dir=None, num_aug=100, clas
     return D.all_gather_iou(mine, records, len(paths)), valid
 
 
+CLASS_CSV_COLUMNS = ("aug_iou_multiple", "standard_iou_multiple", "aug_iou_single", "standard_iou_single", "max_iou",
+                     "mean_iou")
+# CSV column -> distributed.IOU_FIELDS entry ("multiple" = include_bg=True)
+_CSV_FIELD = {"aug_iou_multiple": "aug_bg", "standard_iou_multiple": "standard_bg", "aug_iou_single": "aug_single",
+              "standard_iou_single": "standard_single", "max_iou": "max", "mean_iou": "mean"}
+
+
+def load_label_map(path, img_size):
+    """A ground-truth PNG nearest-resized to img_size, as everywhere -> int32 [H, W] label map (host only)."""
+    return load_image(path, image_size=img_size, normalize=False, is_png=True, resize_method="nearest")[..., 0].astype(np.int32)
+
+
+def classes_of(label_map, class_ids):
+    """The classes of an image: the labels of its ground truth that lie in class_ids, in class_ids' order; 0 (background)
+    and 255 (void) never count."""
+    present = set(int(v) for v in np.unique(np.asarray(label_map)))
+    return [int(c) for c in class_ids if int(c) not in (0, 255) and int(c) in present]
+
+
+def class_presence(gt_paths, class_ids, img_size):
+    """bool [images, K]: image g's ground truth holds class_ids[k] (classes_of)."""
+    out = np.zeros((len(gt_paths), len(class_ids)), dtype=bool)
+    for g, p in enumerate(gt_paths):
+        held = set(classes_of(load_label_map(p, img_size), class_ids))
+        out[g] = [int(c) in held for c in class_ids]
+    return out
+
+
+def evaluate_classes(path, image_paths, gt_paths, class_ids=tuple(range(1, 21)), num_aug=100, angle_max=0.3, shift_max=30,
+                     img_size=(512, 512), rank=0, world=1, seed=1234, sr_types=("aug", "max", "mean")):
+    """Per-class evaluation of a set of images with one forward pass per image (HotPath.run_image_classes).  Returns
+    (table, presence): table [images, K, 6] float64 in distributed.IOU_FIELDS order, NaN where image g's ground truth does
+    not hold class_ids[k]; presence [images, K] bool.  An image whose ground truth holds none of the classes is skipped.
+
+    Draws: image g gets draw g of distributed.replay_augmentation_stream over the WHOLE list, and that one draw serves every
+    class of the image.  A reference per-class run draws along its own filtered list, so each class's numbers equal a
+    per-class run fed these draws, not the reference scripts' draws.
+    Adam: class c of image g starts at num_iter * solves_per_image(mode) * #{images before g whose ground truth holds c}
+    -- the counter a per-class SR_single_class run over the filtered list reaches.  Every rank reads all label maps to know
+    it, so the one all-gather of the results is the only collective."""
+    from .superresolution_scripts.augmentation_utils import _image_to_device
+    from . import ops
+    import torch
+    class_ids = [int(c) for c in class_ids]
+    if any(c in (0, 255) for c in class_ids) or len(set(class_ids)) != len(class_ids):
+        raise ValueError(f"class_ids must be distinct and exclude 0 (background) and 255 (void), got {class_ids}")
+    n_img, k_set = len(image_paths), len(class_ids)
+    if len(gt_paths) != n_img:
+        raise ValueError(f"{n_img} images but {len(gt_paths)} ground truths")
+    presence = class_presence(gt_paths, class_ids, img_size)
+    starts = D.adam_class_starts(presence, path.sr.num_iter, path.mode)
+    params = D.replay_augmentation_stream(n_img, num_aug, angle_max, shift_max, seed=seed)
+    mine = D.shard_indices(n_img, rank, world)
+    rows = []
+    for g in mine:
+        rec = np.full((k_set, len(D.IOU_FIELDS)), np.nan)
+        held = [c for c, p in zip(class_ids, presence[g]) if p]
+        if held:
+            image = _image_to_device(load_image(image_paths[g], image_size=img_size, normalize=True))
+            gt = ops.to_device(load_label_map(gt_paths[g], img_size), torch.int32, device=image.device)
+            angles, shifts = params[g]
+            res = path.run_image_classes(image, angles, shifts, held, gt_dev=gt, sr_types=sr_types,
+                                         adam_starts={c: int(starts[g, class_ids.index(c)]) for c in held})
+            for c in held:
+                rec[class_ids.index(c)] = res[c]["ious"]
+        else:
+            print(f"Image: {image_paths[g]} holds none of the classes, skipping...")
+        rows.append(rec.reshape(-1))
+    width = k_set * len(D.IOU_FIELDS)
+    table = D.all_gather_rows(mine, np.asarray(rows).reshape(len(mine), width), n_img, width)
+    return table.reshape(n_img, k_set, len(D.IOU_FIELDS)), presence
+
+
+def class_rows(table, presence, class_ids):
+    """The rows of the per-class CSV: for each class held by at least one image, ("Class c", the six column means, number of
+    images).  Each mean is np.mean over the images that hold c (a NaN IoU propagates, as in SR_single_class.py)."""
+    table = np.asarray(table, dtype=np.float64)
+    presence = np.asarray(presence, dtype=bool)
+    out = []
+    for k, c in enumerate(class_ids):
+        sel = presence[:, k]
+        if not sel.any():
+            continue
+        vals = table[sel, k]
+        out.append((f"Class {int(c)}", [float(np.mean(vals[:, D.IOU_FIELDS.index(_CSV_FIELD[col])]))
+                                        for col in CLASS_CSV_COLUMNS], int(sel.sum())))
+    return out
+
+
+def write_class_csv(path, rows):
+    """The reference's final_validations layout (every field quoted), plus the column n_images."""
+    import csv
+    with open(path, "w", newline="") as fh:
+        wr = csv.writer(fh, quoting=csv.QUOTE_ALL, lineterminator="\n")
+        wr.writerow(("Name",) + CLASS_CSV_COLUMNS + ("n_images",))
+        for name, means, count in rows:
+            wr.writerow([name] + [repr(v) for v in means] + [str(count)])
+
+
 def valid_rows(table, valid=None):
     """Rows of the images that were evaluated: by the explicit mask evaluate_precomputed returns; without one, every row
     that is not all-NaN (a table from elsewhere)."""

@@ -380,6 +380,99 @@ def iou_counts(truth, pred, class_id, include_bg=False, segments=1):
     return counts
 
 
+# ---------------------------------------------------------------------------------------------
+# class sets: K classes of one image, each equal bit for bit to its single-class call
+# ---------------------------------------------------------------------------------------------
+def class_set(class_ids):
+    """Host int array of a class set for the *_classes entry points (the library checks count, range and repeats)."""
+    ids = [int(c) for c in np.asarray(class_ids, dtype=np.int64).reshape(-1)]
+    return (C.c_int * max(len(ids), 1))(*ids), len(ids)
+
+
+def _planes(out, k, plane_shape, dtype, device, name):
+    """[K, *plane_shape] destination: a new tensor, or a view whose planes are each contiguous and lie a uniform stride
+    apart (rows [i, i+b) of per-class [K, N, h, w] stacks).  Returns (tensor, element stride between planes)."""
+    if out is None:
+        out = torch.empty((k,) + tuple(plane_shape), dtype=dtype, device=device)
+    if tuple(out.shape) != (k,) + tuple(plane_shape) or out.dtype != dtype or not out.is_cuda:
+        raise AsrError(f"{name}: out must be a {dtype} device tensor of shape {(k,) + tuple(plane_shape)}, got "
+                       f"{out.dtype} {tuple(out.shape)}")
+    if not out[0].is_contiguous() or (k > 1 and out.stride(0) < out[0].numel()):
+        raise AsrError(f"{name}: every plane of out must be contiguous and the planes must not overlap")
+    return out, (out.stride(0) if k > 1 else out[0].numel())
+
+
+def opm_classes(logits, class_ids, mode, out=None, out_max=None, new_min=0.0, new_max=1.0):
+    """logits [N,h,w,C] -> (class masks [K,N,h,w], max masks [K,N,h,w] | None): plane k equals opm_argmax / opm_slice /
+    opm_slice_max of class_ids[k], from one read of the logits.  out / out_max may be views of rows of larger stacks."""
+    if mode not in _lib.OPM_MODES:
+        raise AsrError(f"opm_classes: mode must be one of {sorted(_lib.OPM_MODES)}, got {mode!r}")
+    if logits.dim() < 2 or not logits.is_contiguous():
+        raise AsrError("opm_classes: logits must be a contiguous [N, ..., C] tensor")
+    ids, k = class_set(class_ids)
+    classes = logits.shape[-1]
+    n = logits.shape[0]
+    per_copy = logits.numel() // (n * classes)
+    plane = tuple(logits.shape[:-1])
+    cls, stride = _planes(out, k, plane, f32, logits.device, "opm_classes")
+    mx = None
+    if mode == "slice_max":
+        mx, stride_max = _planes(out_max, k, plane, f32, logits.device, "opm_classes")
+        if stride_max != stride:
+            raise AsrError("opm_classes: out and out_max must have the same plane stride")
+    ws = torch.empty((n, 2), dtype=f32, device=logits.device) if mode == "slice" else None
+    call("asr_opm_classes_f32", ptr(logits), ids, k, _lib.OPM_MODES[mode], cls.data_ptr(),
+         mx.data_ptr() if mx is not None else None, ptr(ws, allow_none=True), n, per_copy, classes, stride, float(new_min),
+         float(new_max), stream_ptr())
+    return cls, mx
+
+
+def threshold_classes(image, class_ids, th_factor=0.15, th_mask=None, out=None):
+    """image [K, ...]: segment k thresholded like threshold(image[k], class_ids[k], th_factor, th_mask[k]) -> int32 [K, ...]."""
+    ids, k = class_set(class_ids)
+    if image.shape[0] != k or image.numel() % k:
+        raise AsrError(f"threshold_classes: image must have one segment per class ({k}), got {tuple(image.shape)}")
+    per = image.numel() // k
+    if out is None:
+        out = torch.empty(image.shape, dtype=torch.int32, device=image.device)
+    elif out.numel() != image.numel():
+        raise AsrError("threshold_classes: out size mismatch")
+    if th_mask is not None and th_mask.shape != image.shape:
+        raise AsrError("threshold_classes: th_mask shape mismatch")
+    ws = torch.empty((k, 2), dtype=f32, device=image.device)
+    call("asr_threshold_classes_f32", ptr(image), ptr(th_mask, allow_none=True), ptr(ws), ptr(out, torch.int32), per, k,
+         float(np.float32(th_factor)), ids, stream_ptr())
+    return out
+
+
+def iou_counts_classes(truth, preds, class_ids, include_bg=False):
+    """preds [K, M, ...] int32 (the M masks of class_ids[k] in row k) against ONE int32 label map -> int64 [K, M, 4]."""
+    ids, k = class_set(class_ids)
+    if preds.dim() < 2 or preds.shape[0] != k:
+        raise AsrError(f"iou_counts_classes: preds must be [K={k}, M, ...], got {tuple(preds.shape)}")
+    m = preds.shape[1]
+    per = preds.numel() // (k * m) if m else 0
+    if per == 0 or truth.numel() != per:
+        raise AsrError("iou_counts_classes: size mismatch")
+    counts = torch.empty((k, m, 4), dtype=torch.int64, device=truth.device)
+    call("asr_iou_counts_classes_i32", ptr(truth, torch.int32), ptr(preds, torch.int32), ptr(counts, torch.int64), per, k, m,
+         ids, int(bool(include_bg)), stream_ptr())
+    return counts
+
+
+def standard_mask_classes(logits0, out_hw, class_ids, out=None):
+    """logits0 [h,w,C] -> int32 masks [K,H,W], mask k = standard_mask(logits0, out_hw, class_ids[k])."""
+    h, w, c = logits0.shape
+    ids, k = class_set(class_ids)
+    if out is None:
+        out = torch.empty((k,) + tuple(out_hw), dtype=torch.int32, device=logits0.device)
+    elif tuple(out.shape) != (k,) + tuple(out_hw):
+        raise AsrError(f"standard_mask_classes: out must be {(k,) + tuple(out_hw)}, got {tuple(out.shape)}")
+    call("asr_standard_mask_classes_i32", ptr(logits0), ptr(out, torch.int32), h, w, c, int(out_hw[0]), int(out_hw[1]), ids, k,
+         stream_ptr())
+    return out
+
+
 MAX_SWEEP_FACTORS = 256
 
 

@@ -162,6 +162,100 @@ class HotPath:
             done.record(stream)
         return _Pending(self, res, done, keep=(y, ymax, gt_dev, image_dev))
 
+    # ---- class sets: several classes of one image from ONE forward pass --------------------------------------------------
+    def run_image_classes(self, image_dev, angles, shifts, class_ids, gt_dev=None, adam_starts=None,
+                          sr_types=("aug", "max", "mean"), want_standard=True, profile=None):
+        """run_image for every class of `class_ids` (K distinct ids, K <= 32) with one pass of the N copies through the model.
+        Returns {class_id: dict}, each dict equal bit for bit to HotPath(model, sr, class_id=c, mode, th_factor,
+        batch_size).run_image(image_dev, angles, shifts, gt_dev, adam_start=adam_starts[c], sr_types=sr_types,
+        want_standard=want_standard) -- the classes keep the reference's single-class meaning; nothing is fused.
+
+        adam_starts: {class_id: global Adam step counter before that class's solve} (a slice_max class's max-map solve
+        starts num_iter later, as run_image's second solve does); the counter is left as it was.  None: the classes count
+        as consecutive run_image calls in the order of class_ids, from the current counter, which advances past them."""
+        ids = [int(c) for c in class_ids]
+        k_set = len(ids)
+        sr = self.sr
+        solves = 2 if self.mode == "slice_max" else 1
+        if adam_starts is None:
+            it0 = sr.optimizer.optimizer.iterations if sr.optimizer is not None else 0
+            starts = [it0 + j * solves * sr.num_iter for j in range(k_set)]
+        else:
+            starts = [int(adam_starts[c]) for c in ids]
+        # stage 1: augment -> forward per batch -> OPM of every class into [K, N, h, w] stacks
+        out_hw = sr.output_size
+        n = len(angles)
+        h, w, _ = image_dev.shape
+        eng = self.model.engine
+        bs = min(self.batch_size, n)
+        masks = torch.empty((len(self.MASK_KEYS), k_set) + tuple(out_hw), dtype=torch.int32, device=image_dev.device)
+        have = []
+        y = ymax = None
+        for i in range(0, n, bs):
+            k = min(bs, n - i)
+            copies = au.augment_on_device(image_dev, angles[i:i + k], shifts[i:i + k], out=eng.input_view(k, h, w, 0))
+            preds = self.model.predict_device(copies, batch_size=k, profile=profile, clone=False)
+            if y is None:
+                y = torch.empty((k_set, n) + tuple(preds.shape[1:3]), dtype=torch.float32, device=image_dev.device)
+                ymax = torch.empty_like(y) if self.mode == "slice_max" else None
+            if i == 0 and want_standard:
+                ops.standard_mask_classes(self.model.logits_of(preds, 0).contiguous(), out_hw, ids, out=masks[0])
+                have.append("standard")
+            au.output_processing_classes(preds, ids, self.mode, out=y[:, i:i + k],
+                                         out_max=ymax[:, i:i + k] if ymax is not None else None)
+            del copies, preds
+        if self.mode != "slice":            # load_SR_data's normalisation, per class stack
+            y = ops.minmax_normalize(y, segments=k_set, new_min=0.0, new_max=1.0)
+            if ymax is not None:
+                ymax = ops.minmax_normalize(ymax, segments=k_set, new_min=0.0, new_max=1.0)
+        # stage 2: the K classes as a batch of the existing solver / realign, then K-class threshold and IoU counts
+        if profile is not None:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+        fshifts = self._sr_frame(image_dev, shifts)
+        a = np.repeat(np.asarray(angles, dtype=np.float32)[None], k_set, axis=0)
+        s = np.repeat(np.asarray(fshifts, dtype=np.float32)[None], k_set, axis=0)
+        both = None
+        if "max" in sr_types and "mean" in sr_types:
+            both = (sr.realign_batch(y, a, s, "both"), sr.realign_batch(ymax, a, s, "both") if ymax is not None else None)
+        for t in sr_types:
+            if t == "aug":
+                tgt, _ = sr.augmented_superresolution_classes(y, angles, fshifts, starts)
+                tmax = (sr.augmented_superresolution_classes(ymax, angles, fshifts, [st + sr.num_iter for st in starts])[0]
+                        if ymax is not None else None)
+            elif both is not None:
+                j = 0 if t == "max" else 1
+                tgt, tmax = both[0][j], (both[1][j] if both[1] is not None else None)
+            else:
+                tgt = sr.realign_batch(y, a, s, t)
+                tmax = sr.realign_batch(ymax, a, s, t) if ymax is not None else None
+            row = masks[self.MASK_KEYS.index(t)]
+            if tmax is not None:
+                ops.threshold_classes(tgt, ids, th_mask=tmax, out=row)
+            else:
+                ops.threshold_classes(tgt, ids, th_factor=self.th_factor, out=row)
+            have.append(t)
+        if adam_starts is None and "aug" in sr_types and sr.optimizer is not None:
+            sr.optimizer.optimizer.iterations = starts[-1] + solves * sr.num_iter
+        keys = [key for key in self.MASK_KEYS if key in have]
+        counts = None
+        if gt_dev is not None:
+            gt = gt_dev if gt_dev.dtype == torch.int32 else gt_dev.to(torch.int32)
+            preds = masks[[self.MASK_KEYS.index(key) for key in keys]].transpose(0, 1).contiguous()     # [K, M, H, W]
+            counts = ops.iou_counts_classes(gt.contiguous(), preds, ids, include_bg=True)
+        if profile is not None:
+            e1.record()
+            torch.cuda.synchronize()
+            profile["_sr_stage_ms"] = profile.get("_sr_stage_ms", 0.0) + e0.elapsed_time(e1)
+        counts = counts.cpu().numpy() if counts is not None else None
+        out = {}
+        for j, c in enumerate(ids):
+            res = {key: masks[self.MASK_KEYS.index(key), j] for key in keys}
+            if counts is not None:
+                res["ious"] = self._ious_from_counts(keys, counts[j])
+            out[c] = res
+        return out
+
     def _finish(self, res):
         res.pop("_masks", None)          # the rows stay alive through the per-key views
         if "_iou_counts" in res:

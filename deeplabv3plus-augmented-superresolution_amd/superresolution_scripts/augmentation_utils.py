@@ -76,6 +76,14 @@ def output_processing(predictions, filter_class_id, mode, out=None, out_max=None
     return ops.opm_argmax(predictions, filter_class_id, out=out), None        # any other string = argmax, like the reference
 
 
+def output_processing_classes(predictions, class_ids, mode, out=None, out_max=None):
+    """output_processing for a set of classes from one read of the predictions: [N,h,w,C] device tensor ->
+    (class_masks [K,N,h,w], max_masks [K,N,h,w] | None); plane k equals output_processing(predictions, class_ids[k], mode)
+    bit for bit.  out / out_max: optional [K,N,h,w] destinations (views of rows of per-class stacks allowed)."""
+    mode = mode if mode in ("slice", "slice_max") else "argmax"              # any other string = argmax, like the reference
+    return ops.opm_classes(predictions.contiguous(), class_ids, mode, out=out, out_max=out_max)
+
+
 def feature_maps_on_device(image_dev, model, filter_class_id, mode, angles, shifts, batch_size=16, profile=None):
     """augment -> model -> OPM entirely on the device.  Returns (class_masks, max_masks) [N,h,w]."""
     copies = augment_on_device(image_dev, angles, shifts)

@@ -146,6 +146,35 @@ class Superresolution:
         """copies [B,N,h,w] device tensor, angles [B,N], shifts [B,N,2] -> (device [B,H,W], [B] losses).
         The global Adam step counter advances image by image (reference order), the device then
         iterates all images together."""
+        return self._solve_batch(copies, angles, shifts,
+                                 lambda b: np.stack([self.optimizer.schedule_alphas(self.num_iter) for _ in range(b)], axis=1))
+
+    def augmented_superresolution_classes(self, copies, angles, shifts, start_steps):
+        """The copies of K classes of ONE image in one batched solve: copies [K,N,h,w] device tensor, angles [N], shifts [N,2]
+        (the image's transforms, repeated for every class), start_steps [K] -> (device [K,H,W], [K] losses).  Class k's
+        step scalars are those of a solve that starts at the global step counter start_steps[k]; the counter itself is left
+        as it was (the caller decides what the classes' solves count as).  copy_dropout uses the object's frozen mask."""
+        if self.optimizer is None:
+            raise Exception("You must provide an instance of the Optimizer class to compute the augmented SR")
+        k = copies.shape[0]
+        starts = [int(s) for s in start_steps]
+        if len(starts) != k:
+            raise ValueError(f"{k} classes of copies but {len(starts)} start steps")
+        state = self.optimizer.optimizer
+        saved = state.iterations
+        columns = []
+        try:
+            for s in starts:
+                state.iterations = s
+                columns.append(self.optimizer.schedule_alphas(self.num_iter))
+        finally:
+            state.iterations = saved
+        a = np.repeat(np.asarray(angles, dtype=np.float32)[None], k, axis=0)
+        s = np.repeat(np.asarray(shifts, dtype=np.float32)[None], k, axis=0)
+        return self._solve_batch(copies, a, s, lambda b: np.stack(columns, axis=1).reshape(self.num_iter, b))
+
+    def _solve_batch(self, copies, angles, shifts, make_alphas):
+        """The batched solve; make_alphas(B) -> float32 [num_iter, B] step scalars."""
         if self.optimizer is None:
             raise Exception("You must provide an instance of the Optimizer class to compute the augmented SR")
         dev = copies.device
@@ -162,7 +191,7 @@ class Superresolution:
             angles, shifts = np.asarray(angles)[:, mask], np.asarray(shifts)[:, mask]
         rot, tr = self._transforms(angles, shifts, dev)
         irot, itr = self._transforms(angles, shifts, dev, inverse=True)
-        alphas = np.stack([self.optimizer.schedule_alphas(self.num_iter) for _ in range(b)], axis=1)  # [iter, B]
+        alphas = make_alphas(b)                                                                # [iter, B]
         if self.num_iter == 0:
             return x, [None] * b
         state = self.optimizer.optimizer

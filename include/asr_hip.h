@@ -255,6 +255,38 @@ int asr_minmax_normalize_f32(const float* x, float* out, float* minmax_ws, int64
 int asr_standard_mask_i32(const float* logits, int32_t* mask, int h_in, int w_in, int classes, int h_out, int w_out, int class_id,
                           asr_stream_t stream);
 
+/* --- class sets: several classes of one image from one forward pass ----------------------------------------------
+ * Each entry point below takes K distinct class ids `ids` (a HOST int array, read during the call; 1 <= K <=
+ * ASR_MAX_CLASS_SET, every id in [0, classes)) and equals, bit for bit, K calls of its single-class counterpart, one per
+ * id, while reading its input once.  A bad set (K out of range, an id twice, an id out of range) returns
+ * ASR_ERR_INVALID_ARG before any launch.  Each class keeps the reference's single-class meaning: nothing here fuses the
+ * classes into one label map. */
+#define ASR_MAX_CLASS_SET 32
+#define ASR_OPM_ARGMAX 0
+#define ASR_OPM_SLICE 1
+#define ASR_OPM_SLICE_MAX 2
+/* OPM of mode ASR_OPM_* for K classes: plane k, at class_masks + k * class_stride (and max_masks + k * class_stride,
+ * slice_max only), holds [copies * pixels_per_copy] floats equal to asr_opm_argmax_f32 / asr_opm_slice_f32 /
+ * asr_opm_slice_max_f32 for ids[k] (class_stride >= copies * pixels_per_copy when K > 1: a forward batch can fill rows of
+ * per-class [K, N, h, w] stacks).  minmax_ws: [copies, 2] floats, slice only (the per-copy extrema, computed once). */
+int asr_opm_classes_f32(const float* logits, const int* ids, int K, int mode, float* class_masks, float* max_masks,
+                        float* minmax_ws, int copies, int64_t pixels_per_copy, int classes, int64_t class_stride,
+                        float new_min, float new_max, asr_stream_t stream);
+
+/* asr_threshold_f32 on K segments [K, per_segment] with th_value = th_values[k] on segment k (th_values: K distinct
+ * ids >= 0).  minmax_ws: [K, 2] floats, needed when th_mask == NULL. */
+int asr_threshold_classes_f32(const float* image, const float* th_mask, float* minmax_ws, int32_t* out, int64_t per_segment,
+                              int K, float th_factor, const int* th_values, asr_stream_t stream);
+
+/* asr_iou_counts_shared_truth_i32 for K classes in one pass over the label map: preds [K, M, pixels] (the M masks of class
+ * ids[k] in row k; 1 <= M <= 8), counts [K, M, 4] int64 (zeroed by the call).  Ids may be any value >= 0 here. */
+int asr_iou_counts_classes_i32(const int32_t* truth, const int32_t* preds, int64_t* counts, int64_t pixels, int K, int M,
+                               const int* ids, int include_bg, asr_stream_t stream);
+
+/* asr_standard_mask_i32 for K classes: one bilinear upsample + argmax per output pixel, masks [K, h_out, w_out]. */
+int asr_standard_mask_classes_i32(const float* logits0, int32_t* masks, int h_in, int w_in, int classes, int h_out,
+                                  int w_out, const int* ids, int K, asr_stream_t stream);
+
 /* Per-label pixel counts for the multi-class Mean_IOU (utils.py:151-177, compute_IoU(class_id=None)):
  * counts[seg][0][l] = |truth == l|, counts[seg][1][l] = |pred == l|, counts[seg][2][l] = |truth == l and pred == l|,
  * l = 0..255 (int64, zeroed by the call); IoU_l = c2 / (c0 + c1 - c2). */
