@@ -87,6 +87,8 @@ SIGNATURES = {
     "asr_threshold_classes_f32": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _fl, _ip, _vp]),
     "asr_iou_counts_classes_i32": (_i, [_vp, _vp, _vp, _i64, _i, _i, _ip, _i, _vp]),
     "asr_standard_mask_classes_i32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _ip, _i, _vp]),
+    "asr_fuse_labels_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _fl, _ip, _i, _vp]),
+    "asr_standard_labels_i32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _ip, _i, _vp]),
     "asr_class_counts_i32": (_i, [_vp, _vp, _vp, _i64, _i, _vp]),
     "asr_pwconv_packed_floats": (_sz, [_i, _i]),
     "asr_pwconv_pack_weights_f32": (_i, [_vp, _vp, _i, _i, _vp]),

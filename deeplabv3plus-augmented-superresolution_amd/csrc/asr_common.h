@@ -87,6 +87,14 @@ static inline int asr_class_set(const char* fn, const int* ids, int K, int class
     return ASR_OK;
 }
 
+// The set of a label map (asr_fuse_labels_f32, asr_standard_labels_i32): a class set without 0, the label of "no class".
+static inline int asr_label_set(const char* fn, const int* ids, int K, int classes, AsrClassSet* set) {
+    const int rc = asr_class_set(fn, ids, K, classes, set);
+    if (rc != ASR_OK) return rc;
+    for (int k = 0; k < K; ++k) ASR_REQUIRE(ids[k] != 0, "%s: class id 0 is the fallback label, never a candidate", fn);
+    return ASR_OK;
+}
+
 // ---- device helpers -------------------------------------------------------------------
 #ifdef __HIPCC__
 

@@ -544,6 +544,19 @@ __global__ __launch_bounds__(256) void standard_mask_classes_kernel(const float*
     for (int k = 0; k < set.n; ++k) out[k * plane + o] = (arg == set.id[k]) ? set.id[k] : 0;
 }
 
+// The standard label map of a class set (asr_standard_labels_i32): the same upsample + argmax, the winner kept when it is in
+// the set, else 0 -- the sum of standard_mask_classes_kernel's K masks, written once.
+__global__ __launch_bounds__(256) void standard_labels_kernel(const float* __restrict__ logits, int* __restrict__ out, int h_in,
+                                                              int w_in, int classes, int h_out, int w_out, float scale_y,
+                                                              float scale_x, AsrClassSet set) {
+    const int ox = blockIdx.x * 256 + threadIdx.x, oy = blockIdx.y;
+    if (ox >= w_out) return;
+    const int arg = upsampled_argmax(logits, h_in, w_in, classes, scale_y, scale_x, ox, oy);
+    int lab = 0;
+    for (int k = 0; k < set.n; ++k) lab = (arg == set.id[k]) ? arg : lab;
+    out[(long long)oy * w_out + ox] = lab;
+}
+
 int cap_grid(long long total) {
     const long long g = asr_cdiv(total, 256);
     return (int)(g < 8192 ? (g > 0 ? g : 1) : 8192);
@@ -670,6 +683,21 @@ extern "C" int asr_standard_mask_classes_i32(const float* logits0, int32_t* mask
     const float sy = (float)h_in / (float)h_out, sx = (float)w_in / (float)w_out;
     hipLaunchKernelGGL(standard_mask_classes_kernel, dim3((unsigned)asr_cdiv(w_out, 256), (unsigned)h_out), dim3(256), 0,
                        asr_stream(stream), logits0, masks, h_in, w_in, classes, h_out, w_out, sy, sx, set);
+    ASR_LAUNCH_CHECK();
+    return ASR_OK;
+}
+
+extern "C" int asr_standard_labels_i32(const float* logits0, int32_t* labels, int h_in, int w_in, int classes, int h_out, int w_out,
+                                       const int* ids, int K, asr_stream_t stream) {
+    AsrClassSet set;
+    const int rc = asr_label_set("asr_standard_labels_i32", ids, K, classes, &set);
+    if (rc != ASR_OK) return rc;
+    ASR_REQUIRE(logits0 && labels, "asr_standard_labels_i32: null pointer");
+    ASR_REQUIRE(h_in > 0 && w_in > 0 && classes > 0 && h_out > 0 && w_out > 0 && h_out <= 65535,
+                "asr_standard_labels_i32: bad shape");
+    const float sy = (float)h_in / (float)h_out, sx = (float)w_in / (float)w_out;
+    hipLaunchKernelGGL(standard_labels_kernel, dim3((unsigned)asr_cdiv(w_out, 256), (unsigned)h_out), dim3(256), 0,
+                       asr_stream(stream), logits0, labels, h_in, w_in, classes, h_out, w_out, sy, sx, set);
     ASR_LAUNCH_CHECK();
     return ASR_OK;
 }

@@ -456,6 +456,79 @@ __global__ __launch_bounds__(256) void class_counts_kernel(const int32_t* __rest
         if (hist[i]) atomicAdd(counts + (int64_t)seg * 768 + i, (unsigned long long)hist[i]);
 }
 
+// ---- label fusion: K per-class SR outputs of one image -> one label map (asr_fuse_labels_f32) ----------------------------
+// Class k passes at a pixel exactly when its single-class mask is set there -- threshold_segment's own comparisons: s > max_k *
+// th_factor (the f32 product, kept in LDS per class), or s >= m against its max map -- and the passing class with the greatest
+// rank value (s, or the one f32 subtraction s - m) labels the pixel; the strict > below leaves equal values (-0.0 == +0.0 among
+// them) to the lowest k, and 0 stays where no class passes.  Every plane is read once, four classes' loads in flight per
+// thread.  With a ground truth the same pass counts what class_counts_kernel counts on the label it has just written: a
+// wave's lanes that share lane 0's label (the background, mostly) add once by popcount, the others one by one, into a
+// workgroup histogram in LDS that leaves through one 64-bit atomic per non-empty bin.  Out-of-range lanes carry key -1; the trip
+// count is uniform over the workgroup, so every lane reaches the shuffles together.
+__device__ __forceinline__ void label_hist_add(unsigned int* __restrict__ h, int key, int lane) {
+    const int lead = __shfl(key, 0, 64);
+    const unsigned long long same = __ballot(key == lead);
+    if (key == lead) {
+        if (key >= 0 && lane == __ffsll((long long)same) - 1) atomicAdd(h + key, (unsigned int)__popcll(same));
+    } else if (key >= 0) {
+        atomicAdd(h + key, 1u);
+    }
+}
+
+template <bool HAS_MAX, bool HAS_TRUTH>
+__global__ __launch_bounds__(256) void fuse_labels_kernel(const float* __restrict__ scores, const float* __restrict__ maxs,
+                                                          const float* __restrict__ seg_minmax, const int32_t* __restrict__ truth,
+                                                          int32_t* __restrict__ labels, unsigned long long* __restrict__ counts,
+                                                          int64_t pixels, float th_factor, AsrClassSet set) {
+    __shared__ float th[ASR_MAX_CLASS_SET];
+    __shared__ unsigned int hist[HAS_TRUTH ? 3 * 256 : 1];
+    const int K = set.n;
+    if (!HAS_MAX && (int)threadIdx.x < K) th[threadIdx.x] = seg_minmax[threadIdx.x * 2 + 1] * th_factor;
+    if (HAS_TRUTH)
+        for (int i = threadIdx.x; i < 3 * 256; i += 256) hist[i] = 0u;
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    for (int64_t i0 = (int64_t)blockIdx.x * 256; i0 < pixels; i0 += (int64_t)gridDim.x * 256) {
+        const int64_t i = i0 + threadIdx.x;
+        const bool in = i < pixels;
+        int lab = 0;
+        if (in) {
+            float best = 0.0f;
+            bool have = false;
+            for (int k0 = 0; k0 < K; k0 += 4) {
+                float s[4], m[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const bool live = k0 + j < K;
+                    s[j] = live ? scores[(int64_t)(k0 + j) * pixels + i] : 0.0f;
+                    m[j] = (HAS_MAX && live) ? maxs[(int64_t)(k0 + j) * pixels + i] : 0.0f;
+                }
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    if (k0 + j < K) {
+                        const bool pass = HAS_MAX ? (s[j] >= m[j]) : (s[j] > th[k0 + j]);
+                        const float r = HAS_MAX ? s[j] - m[j] : s[j];
+                        if (pass && (!have || r > best)) { best = r; have = true; lab = set.id[k0 + j]; }
+                    }
+                }
+            }
+            labels[i] = lab;
+        }
+        if (HAS_TRUTH) {
+            const int tv = in ? truth[i] : -1;
+            const bool t_ok = in && tv >= 0 && tv < 256, p_ok = in && lab < 256;          // (lab >= 0 always)
+            label_hist_add(hist, t_ok ? tv : -1, lane);
+            label_hist_add(hist + 256, p_ok ? lab : -1, lane);
+            label_hist_add(hist + 512, (t_ok && tv == lab) ? tv : -1, lane);
+        }
+    }
+    if (HAS_TRUTH) {
+        __syncthreads();
+        for (int b = threadIdx.x; b < 3 * 256; b += 256)
+            if (hist[b]) atomicAdd(counts + b, (unsigned long long)hist[b]);
+    }
+}
+
 // ---- last_activation: softmax / sigmoid over the class axis (model.py:124-125) ----------------------
 __device__ __forceinline__ void activate_row(const float* row, float* o, int classes, int kind) {     // o may be row
     if (kind == 1) {                       // softmax: exp(x - max) / sum
@@ -684,6 +757,37 @@ extern "C" int asr_iou_counts_classes_i32(const int32_t* truth, const int32_t* p
     const int grid = stream_grid(pixels) > 128 ? 128 : stream_grid(pixels);
     hipLaunchKernelGGL(iou_counts_classes_kernel, dim3(grid), dim3(256), 0, s, truth, preds,
                        reinterpret_cast<unsigned long long*>(counts), pixels, M, set, include_bg);
+    ASR_LAUNCH_CHECK();
+    return ASR_OK;
+}
+
+extern "C" int asr_fuse_labels_f32(const float* scores, const float* max_scores, float* minmax_ws, const int32_t* truth,
+                                   int32_t* labels, int64_t* counts, int64_t pixels, int K, float th_factor, const int* ids,
+                                   int classes, asr_stream_t stream) {
+    AsrClassSet set;
+    int rc = asr_label_set("asr_fuse_labels_f32", ids, K, classes, &set);
+    if (rc != ASR_OK) return rc;
+    ASR_REQUIRE(scores && labels, "asr_fuse_labels_f32: null pointer");
+    ASR_REQUIRE(pixels > 0, "asr_fuse_labels_f32: bad shape");
+    ASR_REQUIRE(!truth == !counts, "asr_fuse_labels_f32: truth and counts go together (both or neither)");
+    hipStream_t s = asr_stream(stream);
+    if (!max_scores) {
+        ASR_REQUIRE(minmax_ws, "asr_fuse_labels_f32: minmax workspace required without max_scores");
+        rc = asr_minmax_f32(scores, minmax_ws, pixels, K, stream);
+        if (rc != ASR_OK) return rc;
+    }
+    if (counts) ASR_HIP_CHECK(hipMemsetAsync(counts, 0, sizeof(int64_t) * 768, s));
+    const int grid = stream_grid(pixels) > 1024 ? 1024 : stream_grid(pixels);
+    auto* c = reinterpret_cast<unsigned long long*>(counts);
+#define ASR_FUSE_LAUNCH(MX, TR) \
+    hipLaunchKernelGGL((fuse_labels_kernel<MX, TR>), dim3(grid), dim3(256), 0, s, scores, max_scores, minmax_ws, truth, labels, c, \
+                       pixels, th_factor, set)
+    if (max_scores) {
+        if (truth) ASR_FUSE_LAUNCH(true, true); else ASR_FUSE_LAUNCH(true, false);
+    } else {
+        if (truth) ASR_FUSE_LAUNCH(false, true); else ASR_FUSE_LAUNCH(false, false);
+    }
+#undef ASR_FUSE_LAUNCH
     ASR_LAUNCH_CHECK();
     return ASR_OK;
 }

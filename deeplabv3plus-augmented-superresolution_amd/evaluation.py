@@ -183,6 +183,105 @@ def write_class_csv(path, rows):
             wr.writerow([name] + [repr(v) for v in means] + [str(count)])
 
 
+# ---- label maps: one fused label map per image and SR type, scored with the multi-class Mean_IOU ------------------------
+LABELMAP_KEYS = ("standard", "aug", "max", "mean")
+LABELMAP_CSV_COLUMNS = ("standard_iou", "aug_iou", "max_iou", "mean_iou")
+
+
+def gather_labelmap_records(local_indices, local_miou, local_counts, num_images):
+    """The one collective of evaluate_labelmaps.  local_miou: [n_local, 4] per-image Mean_IOU (LABELMAP_KEYS order);
+    local_counts: [n_local, 4, 3, 256] integer counts.  Returns on every rank (rows [num_images, 4] float64, NaN rows where
+    no rank reported; summed counts [4, 3, 256] int64).  The counts travel as float64 in the same all-gather as the rows:
+    exact below 2^53 pixels per bin."""
+    m = len(LABELMAP_KEYS)
+    n_local = len(local_indices)
+    rec = np.empty((n_local, m + m * 768), dtype=np.float64)
+    if n_local:
+        rec[:, :m] = np.asarray(local_miou, dtype=np.float64).reshape(n_local, m)
+        rec[:, m:] = np.asarray(local_counts, dtype=np.int64).reshape(n_local, m * 768)
+    table = D.all_gather_rows(local_indices, rec, num_images, m + m * 768)
+    counts = np.nan_to_num(table[:, m:]).astype(np.int64).reshape(num_images, m, 3, 256)
+    return table[:, :m], counts.sum(axis=0)
+
+
+def label_ious(counts):
+    """counts [3, 256] -> {label: inter / union} for the labels the ground truth holds, void (255) removed."""
+    c = np.asarray(counts, dtype=np.int64)
+    return {l: float(np.float64(c[2, l]) / np.float64(c[0, l] + c[1, l] - c[2, l])) for l in range(255) if c[0, l] > 0}
+
+
+def dataset_miou(counts):
+    """The dataset-level VOC mIoU: per-label IoU from the counts summed over the images, mean over the labels present
+    (utils.mean_iou_from_counts on the sum); NaN when the ground truths hold no label."""
+    from .utils import mean_iou_from_counts
+    return mean_iou_from_counts(counts)
+
+
+def evaluate_labelmaps(path, image_paths, gt_paths, class_ids=tuple(range(1, 21)), num_aug=100, angle_max=0.3, shift_max=30,
+                       img_size=(512, 512), rank=0, world=1, seed=1234, sr_types=("aug", "max", "mean"), prune=True,
+                       save_dir=None):
+    """One fused label map per image and SR type (HotPath.run_image_labels) and its score.  Returns (rows, counts) on every
+    rank: rows [images, 4] per-image Mean_IOU in LABELMAP_KEYS order (the reference's per-image-then-mean convention; NaN for
+    an SR type that was not asked for), counts [4, 3, 256] int64 summed over the images (dataset_miou, label_ious).
+
+    The class set is the SAME for every image and is never read from the ground truth, so a class that is not in an image
+    can be predicted there and costs IoU.  Draws: image g gets draw g of distributed.replay_augmentation_stream over the
+    whole list, as evaluate_classes.  Adam: every image counts as holding every class, so class c of image g starts at
+    num_iter * solves_per_image(mode) * g -- evaluate_classes's rule with an all-true presence -- whatever the sharding and
+    whatever pruning leaves out.  One all-gather at the end.  save_dir: the label maps as <stem>_<key>.png (8-bit)."""
+    from .superresolution_scripts.augmentation_utils import _image_to_device
+    from . import ops
+    import torch
+    class_ids = [int(c) for c in class_ids]
+    if any(c in (0, 255) for c in class_ids) or len(set(class_ids)) != len(class_ids):
+        raise ValueError(f"class_ids must be distinct and exclude 0 (background) and 255 (void), got {class_ids}")
+    n_img = len(image_paths)
+    if len(gt_paths) != n_img:
+        raise ValueError(f"{n_img} images but {len(gt_paths)} ground truths")
+    starts = D.adam_class_starts(np.ones((n_img, len(class_ids)), dtype=bool), path.sr.num_iter, path.mode)
+    params = D.replay_augmentation_stream(n_img, num_aug, angle_max, shift_max, seed=seed)
+    mine = D.shard_indices(n_img, rank, world)
+    if save_dir:
+        os.makedirs(save_dir, exist_ok=True)
+    mious, counts = [], []
+    for g in mine:
+        image = _image_to_device(load_image(image_paths[g], image_size=img_size, normalize=True))
+        gt = ops.to_device(load_label_map(gt_paths[g], img_size), torch.int32, device=image.device)
+        angles, shifts = params[g]
+        res = path.run_image_labels(image, angles, shifts, class_ids, gt_dev=gt, sr_types=sr_types, prune=prune,
+                                    adam_starts={c: int(starts[g, k]) for k, c in enumerate(class_ids)})
+        mious.append([res["Mean_IOU"].get(key, np.nan) for key in LABELMAP_KEYS])
+        counts.append([res["counts"].get(key, np.zeros((3, 256), np.int64)) for key in LABELMAP_KEYS])
+        if save_dir:
+            from PIL import Image
+            stem = os.path.splitext(os.path.basename(image_paths[g]))[0]
+            for key in LABELMAP_KEYS:
+                if key in res:
+                    Image.fromarray(res[key].cpu().numpy().astype(np.uint8), mode="L").save(
+                        os.path.join(save_dir, f"{stem}_{key}.png"))
+    return gather_labelmap_records(mine, mious, counts, n_img)
+
+
+def write_labelmap_csv(path, counts, rows):
+    """One row per label the ground truths hold ("Label l": its IoU from the summed counts for standard / aug / max / mean,
+    n = its ground-truth pixels), then both means: "dataset_mIoU" (dataset_miou of each column) and "mean_image_mIoU"
+    (np.mean of the per-image Mean_IOU rows; a NaN image propagates, as in the reference), n = number of images.  The column
+    of a label map that was not produced (all-zero counts) is nan throughout."""
+    import csv
+    counts = np.asarray(counts, dtype=np.int64)
+    rows = np.asarray(rows, dtype=np.float64).reshape(-1, len(LABELMAP_KEYS))
+    per = [label_ious(counts[j]) for j in range(len(LABELMAP_KEYS))]
+    truth = counts[:, 0].max(axis=0)              # a label map that was not asked for carries all-zero counts: its cells are nan
+    with open(path, "w", newline="") as fh:
+        wr = csv.writer(fh, quoting=csv.QUOTE_ALL, lineterminator="\n")
+        wr.writerow(("Name",) + LABELMAP_CSV_COLUMNS + ("n",))
+        for l in sorted(l for l in range(255) if truth[l] > 0):
+            wr.writerow([f"Label {l}"] + [repr(p.get(l, float("nan"))) for p in per] + [str(int(truth[l]))])
+        wr.writerow(["dataset_mIoU"] + [repr(dataset_miou(counts[j])) for j in range(len(LABELMAP_KEYS))] + [str(len(rows))])
+        wr.writerow(["mean_image_mIoU"] + [repr(float(np.mean(rows[:, j]))) if len(rows) else "nan"
+                                           for j in range(len(LABELMAP_KEYS))] + [str(len(rows))])
+
+
 def valid_rows(table, valid=None):
     """Rows of the images that were evaluated: by the explicit mask evaluate_precomputed returns; without one, every row
     that is not all-NaN (a table from elsewhere)."""

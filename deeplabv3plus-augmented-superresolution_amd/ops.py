@@ -473,6 +473,52 @@ def standard_mask_classes(logits0, out_hw, class_ids, out=None):
     return out
 
 
+# ---------------------------------------------------------------------------------------------
+# label maps: the K single-class results of one image fused into one label map
+# ---------------------------------------------------------------------------------------------
+def fuse_labels(scores, class_ids, th_factor=0.15, max_scores=None, truth=None, out=None, classes=0):
+    """scores [K, ...] float32 (plane k: the SR output of class_ids[k]) -> int32 label map [...]: class_ids[k*] where k* is
+    the class with the greatest rank value among those whose single-class mask is set at the pixel (scores[k] > th_factor *
+    max(scores[k]) ranked by scores[k]; with max_scores [K, ...]: scores[k] >= max_scores[k] ranked by their difference), the
+    lowest k on equal values, 0 where none passes (asr_fuse_labels_f32).  truth (int32 label map): returns (labels, int64
+    [3, 256] counts equal to class_counts(truth, labels)[0]) from the same pass; else (labels, None).  Ids lie in
+    [1, classes) (classes = 0: any id >= 1)."""
+    ids, k = class_set(class_ids)
+    if scores.dim() < 2 or scores.shape[0] != k:
+        raise AsrError(f"fuse_labels: scores must have one plane per class ({k}), got {tuple(scores.shape)}")
+    per = scores.numel() // k
+    if max_scores is not None and max_scores.shape != scores.shape:
+        raise AsrError("fuse_labels: max_scores shape mismatch")
+    if out is None:
+        out = torch.empty(tuple(scores.shape[1:]), dtype=torch.int32, device=scores.device)
+    elif out.numel() != per:
+        raise AsrError("fuse_labels: out size mismatch")
+    counts = None
+    if truth is not None:
+        if truth.numel() != per:
+            raise AsrError(f"fuse_labels: truth has {truth.numel()} pixels, expected {per}")
+        counts = torch.empty((3, 256), dtype=torch.int64, device=scores.device)
+    ws = torch.empty((k, 2), dtype=f32, device=scores.device) if max_scores is None else None
+    call("asr_fuse_labels_f32", ptr(scores), ptr(max_scores, allow_none=True), ptr(ws, allow_none=True),
+         ptr(truth, torch.int32, allow_none=True), ptr(out, torch.int32), ptr(counts, torch.int64, allow_none=True), per, k,
+         float(np.float32(th_factor)), ids, int(classes), stream_ptr())
+    return out, counts
+
+
+def standard_labels(logits0, out_hw, class_ids, out=None):
+    """logits0 [h,w,C] -> int32 label map [H,W]: the upsampled argmax where it is one of class_ids, else 0 -- the sum of
+    standard_mask_classes' K masks (asr_standard_labels_i32)."""
+    h, w, c = logits0.shape
+    ids, k = class_set(class_ids)
+    if out is None:
+        out = torch.empty(tuple(out_hw), dtype=torch.int32, device=logits0.device)
+    elif tuple(out.shape) != tuple(out_hw):
+        raise AsrError(f"standard_labels: out must be {tuple(out_hw)}, got {tuple(out.shape)}")
+    call("asr_standard_labels_i32", ptr(logits0), ptr(out, torch.int32), h, w, c, int(out_hw[0]), int(out_hw[1]), ids, k,
+         stream_ptr())
+    return out
+
+
 MAX_SWEEP_FACTORS = 256
 
 

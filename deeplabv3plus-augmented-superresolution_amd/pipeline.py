@@ -14,7 +14,7 @@ import torch
 
 from . import ops
 from .superresolution_scripts import augmentation_utils as au
-from .utils import iou_from_counts
+from .utils import iou_from_counts, mean_iou_from_counts
 
 
 class HotPath:
@@ -163,33 +163,24 @@ class HotPath:
         return _Pending(self, res, done, keep=(y, ymax, gt_dev, image_dev))
 
     # ---- class sets: several classes of one image from ONE forward pass --------------------------------------------------
-    def run_image_classes(self, image_dev, angles, shifts, class_ids, gt_dev=None, adam_starts=None,
-                          sr_types=("aug", "max", "mean"), want_standard=True, profile=None):
-        """run_image for every class of `class_ids` (K distinct ids, K <= 32) with one pass of the N copies through the model.
-        Returns {class_id: dict}, each dict equal bit for bit to HotPath(model, sr, class_id=c, mode, th_factor,
-        batch_size).run_image(image_dev, angles, shifts, gt_dev, adam_start=adam_starts[c], sr_types=sr_types,
-        want_standard=want_standard) -- the classes keep the reference's single-class meaning; nothing is fused.
-
-        adam_starts: {class_id: global Adam step counter before that class's solve} (a slice_max class's max-map solve
-        starts num_iter later, as run_image's second solve does); the counter is left as it was.  None: the classes count
-        as consecutive run_image calls in the order of class_ids, from the current counter, which advances past them."""
-        ids = [int(c) for c in class_ids]
-        k_set = len(ids)
+    def _class_starts(self, ids, adam_starts):
+        """Global Adam step counter before each class's solve: adam_starts[c], or consecutive solves in the order of ids
+        from the current counter."""
         sr = self.sr
         solves = 2 if self.mode == "slice_max" else 1
         if adam_starts is None:
             it0 = sr.optimizer.optimizer.iterations if sr.optimizer is not None else 0
-            starts = [it0 + j * solves * sr.num_iter for j in range(k_set)]
-        else:
-            starts = [int(adam_starts[c]) for c in ids]
-        # stage 1: augment -> forward per batch -> OPM of every class into [K, N, h, w] stacks
-        out_hw = sr.output_size
+            return [it0 + j * solves * sr.num_iter for j in range(len(ids))]
+        return [int(adam_starts[c]) for c in ids]
+
+    def _classes_stage_model(self, image_dev, angles, shifts, ids, profile, standard):
+        """Stage 1 of a class set: augment -> forward per batch -> OPM of every class into raw [K, N, h, w] stacks (y, ymax).
+        standard: None, or a function of copy 0's logits [h, w, C] (the standard masks / label map are made from them)."""
+        k_set = len(ids)
         n = len(angles)
         h, w, _ = image_dev.shape
         eng = self.model.engine
         bs = min(self.batch_size, n)
-        masks = torch.empty((len(self.MASK_KEYS), k_set) + tuple(out_hw), dtype=torch.int32, device=image_dev.device)
-        have = []
         y = ymax = None
         for i in range(0, n, bs):
             k = min(bs, n - i)
@@ -198,21 +189,27 @@ class HotPath:
             if y is None:
                 y = torch.empty((k_set, n) + tuple(preds.shape[1:3]), dtype=torch.float32, device=image_dev.device)
                 ymax = torch.empty_like(y) if self.mode == "slice_max" else None
-            if i == 0 and want_standard:
-                ops.standard_mask_classes(self.model.logits_of(preds, 0).contiguous(), out_hw, ids, out=masks[0])
-                have.append("standard")
+            if i == 0 and standard is not None:
+                standard(self.model.logits_of(preds, 0).contiguous())
             au.output_processing_classes(preds, ids, self.mode, out=y[:, i:i + k],
                                          out_max=ymax[:, i:i + k] if ymax is not None else None)
             del copies, preds
-        if self.mode != "slice":            # load_SR_data's normalisation, per class stack
+        return y, ymax
+
+    def _classes_normalise(self, y, ymax):
+        """load_SR_data's normalisation, per class stack (not in slice mode)."""
+        if self.mode != "slice":
+            k_set = y.shape[0]
             y = ops.minmax_normalize(y, segments=k_set, new_min=0.0, new_max=1.0)
             if ymax is not None:
                 ymax = ops.minmax_normalize(ymax, segments=k_set, new_min=0.0, new_max=1.0)
-        # stage 2: the K classes as a batch of the existing solver / realign, then K-class threshold and IoU counts
-        if profile is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-        fshifts = self._sr_frame(image_dev, shifts)
+        return y, ymax
+
+    def _classes_scores(self, y, ymax, angles, fshifts, starts, sr_types):
+        """Stage 2 of a class set up to the SR outputs: yields (t, scores [K, H, W], max-map scores [K, H, W] | None) for each
+        SR type, the K classes as a batch of the existing solver / realign."""
+        sr = self.sr
+        k_set = y.shape[0]
         a = np.repeat(np.asarray(angles, dtype=np.float32)[None], k_set, axis=0)
         s = np.repeat(np.asarray(fshifts, dtype=np.float32)[None], k_set, axis=0)
         both = None
@@ -229,6 +226,39 @@ class HotPath:
             else:
                 tgt = sr.realign_batch(y, a, s, t)
                 tmax = sr.realign_batch(ymax, a, s, t) if ymax is not None else None
+            yield t, tgt, tmax
+
+    def run_image_classes(self, image_dev, angles, shifts, class_ids, gt_dev=None, adam_starts=None,
+                          sr_types=("aug", "max", "mean"), want_standard=True, profile=None):
+        """run_image for every class of `class_ids` (K distinct ids, K <= 32) with one pass of the N copies through the model.
+        Returns {class_id: dict}, each dict equal bit for bit to HotPath(model, sr, class_id=c, mode, th_factor,
+        batch_size).run_image(image_dev, angles, shifts, gt_dev, adam_start=adam_starts[c], sr_types=sr_types,
+        want_standard=want_standard) -- the classes keep the reference's single-class meaning; run_image_labels fuses them.
+
+        adam_starts: {class_id: global Adam step counter before that class's solve} (a slice_max class's max-map solve
+        starts num_iter later, as run_image's second solve does); the counter is left as it was.  None: the classes count
+        as consecutive run_image calls in the order of class_ids, from the current counter, which advances past them."""
+        ids = [int(c) for c in class_ids]
+        k_set = len(ids)
+        sr = self.sr
+        solves = 2 if self.mode == "slice_max" else 1
+        starts = self._class_starts(ids, adam_starts)
+        # stage 1: augment -> forward per batch -> OPM of every class into [K, N, h, w] stacks
+        out_hw = sr.output_size
+        masks = torch.empty((len(self.MASK_KEYS), k_set) + tuple(out_hw), dtype=torch.int32, device=image_dev.device)
+        have = []
+
+        def standard(logits0):
+            ops.standard_mask_classes(logits0, out_hw, ids, out=masks[0])
+            have.append("standard")
+
+        y, ymax = self._classes_stage_model(image_dev, angles, shifts, ids, profile, standard if want_standard else None)
+        y, ymax = self._classes_normalise(y, ymax)
+        # stage 2: the K classes as a batch of the existing solver / realign, then K-class threshold and IoU counts
+        if profile is not None:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+        for t, tgt, tmax in self._classes_scores(y, ymax, angles, self._sr_frame(image_dev, shifts), starts, sr_types):
             row = masks[self.MASK_KEYS.index(t)]
             if tmax is not None:
                 ops.threshold_classes(tgt, ids, th_mask=tmax, out=row)
@@ -255,6 +285,102 @@ class HotPath:
                 res["ious"] = self._ious_from_counts(keys, counts[j])
             out[c] = res
         return out
+
+    # ---- label maps: the classes of an image fused into one label map per SR type, and its Mean_IOU -----------------------
+    def run_image_labels(self, image_dev, angles, shifts, class_ids=range(1, 21), gt_dev=None, adam_starts=None,
+                         sr_types=("aug", "max", "mean"), want_standard=True, prune=True, profile=None, keep_scores=False):
+        """One label map per SR type from one forward pass: stage 1 and the solves are run_image_classes's; stage 2 ends in the
+        fusion kernel (ops.fuse_labels) instead of K thresholds.  class_ids: K <= 32 distinct ids, none 0 (the label of "no
+        class").  At each pixel the label is the class whose single-class mask is set there and whose SR output is greatest
+        (slice_max: greatest margin over its max map's SR output), the first of class_ids on equal values, 0 where no mask
+        is set; the standard label map is the upsampled argmax of copy 0 where it is in class_ids, else 0.
+
+        Returns a dict: "standard" / "aug" / "max" / "mean" -> device int32 [H, W] (those asked for); with gt_dev also
+        "counts" {key: int64 [3, 256] numpy, ops.class_counts of the map against gt_dev} and "Mean_IOU" {key: float,
+        utils.mean_iou_from_counts}; "solved_ids": the classes that went through the solver; with keep_scores "scores"
+        {t: (S [K', H, W], Smax [K', H, W] | None)}, the tensors the fusion read, plane j belonging to solved_ids[j].
+
+        prune (argmax OPM only): a class that wins no pixel of any copy has an all-zero stack; its solve stays at zero
+        whatever the update rule or prior (zero data, zero gradient, zero step) and its mask is empty, so it is left out of
+        the normalisation, the solver, the realign and the fusion.  The K raw maxima (the min/max kernel that the
+        normalisation runs, here ahead of it) are read once on the host to know them: one synchronisation after the
+        forward pass.  The label maps, the counts and the Adam bookkeeping are those of
+        prune=False bit for bit.  The slice and slice_max stacks are dense: prune does nothing there.
+        adam_starts: as run_image_classes; a class's start counts ALL requested ids in order, pruned or not, and with None
+        the counter advances past all of them.  Zero classes left is legal: every SR label map is 0."""
+        ids = [int(c) for c in class_ids]
+        if any(c == 0 for c in ids):
+            raise ValueError(f"class id 0 is the fallback label, never a candidate: {ids}")
+        unknown = [t for t in sr_types if t not in ("aug", "max", "mean")]
+        if unknown:
+            raise ValueError(f"sr_types may hold aug, max and mean, got {unknown}")
+        sr_types = [t for t in ("aug", "max", "mean") if t in sr_types]
+        if not sr_types and not want_standard:
+            raise ValueError("no label map asked for: sr_types holds none of aug / max / mean and want_standard is False")
+        sr = self.sr
+        solves = 2 if self.mode == "slice_max" else 1
+        starts = self._class_starts(ids, adam_starts)
+        out_hw = sr.output_size
+        dev = image_dev.device
+        keys = (["standard"] if want_standard else []) + sr_types
+        maps = torch.empty((len(keys),) + tuple(out_hw), dtype=torch.int32, device=dev)
+        classes = getattr(self.model, "classes", 0)
+
+        def standard(logits0):
+            ops.standard_labels(logits0, out_hw, ids, out=maps[0])
+
+        y, ymax = self._classes_stage_model(image_dev, angles, shifts, ids, profile, standard if want_standard else None)
+        kept = list(range(len(ids)))
+        if prune and self.mode == "argmax":
+            # raw argmax stacks hold ids[k] where the class wins and 0 elsewhere: a maximum of 0 is a class that never wins
+            mx = ops.minmax(y, segments=len(ids))[:, 1].cpu().numpy()
+            kept = [k for k in kept if mx[k] != 0.0]
+            if len(kept) < len(ids):
+                y = y[kept].contiguous() if kept else None
+        solved = [ids[k] for k in kept]
+        if kept:
+            y, ymax = self._classes_normalise(y, ymax)
+        if profile is not None:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+        gt = None
+        counts = None
+        if gt_dev is not None:
+            gt = (gt_dev if gt_dev.dtype == torch.int32 else gt_dev.to(torch.int32)).contiguous()
+            counts = torch.empty((len(keys), 3, 256), dtype=torch.int64, device=dev)
+            if want_standard:
+                counts[0] = ops.class_counts(gt, maps[0])[0]
+        scores = {}
+        if kept:
+            for t, tgt, tmax in self._classes_scores(y, ymax, angles, self._sr_frame(image_dev, shifts),
+                                                     [starts[k] for k in kept], sr_types):
+                j = keys.index(t)
+                _, c = ops.fuse_labels(tgt, solved, th_factor=self.th_factor, max_scores=tmax, truth=gt, out=maps[j],
+                                       classes=classes)
+                if c is not None:
+                    counts[j] = c
+                if keep_scores:
+                    scores[t] = (tgt, tmax)
+        elif sr_types:
+            first = keys.index(sr_types[0])
+            maps[first:].zero_()
+            if gt is not None:
+                counts[first:] = ops.class_counts(gt, maps[first])[0]          # one count serves every (equal) zero map
+        if adam_starts is None and "aug" in sr_types and sr.optimizer is not None and ids:
+            sr.optimizer.optimizer.iterations = starts[-1] + solves * sr.num_iter
+        if profile is not None:
+            e1.record()
+            torch.cuda.synchronize()
+            profile["_sr_stage_ms"] = profile.get("_sr_stage_ms", 0.0) + e0.elapsed_time(e1)
+        res = {key: maps[j] for j, key in enumerate(keys)}
+        res["solved_ids"] = solved
+        if counts is not None:
+            host = counts.cpu().numpy()
+            res["counts"] = {key: host[j] for j, key in enumerate(keys)}
+            res["Mean_IOU"] = {key: mean_iou_from_counts(host[j]) for j, key in enumerate(keys)}
+        if keep_scores:
+            res["scores"] = scores
+        return res
 
     def _finish(self, res):
         res.pop("_masks", None)          # the rows stay alive through the per-key views

@@ -259,8 +259,8 @@ int asr_standard_mask_i32(const float* logits, int32_t* mask, int h_in, int w_in
  * Each entry point below takes K distinct class ids `ids` (a HOST int array, read during the call; 1 <= K <=
  * ASR_MAX_CLASS_SET, every id in [0, classes)) and equals, bit for bit, K calls of its single-class counterpart, one per
  * id, while reading its input once.  A bad set (K out of range, an id twice, an id out of range) returns
- * ASR_ERR_INVALID_ARG before any launch.  Each class keeps the reference's single-class meaning: nothing here fuses the
- * classes into one label map. */
+ * ASR_ERR_INVALID_ARG before any launch.  Each class keeps the reference's single-class meaning; the label-map entry
+ * points further down fuse the classes into one label map. */
 #define ASR_MAX_CLASS_SET 32
 #define ASR_OPM_ARGMAX 0
 #define ASR_OPM_SLICE 1
@@ -286,6 +286,31 @@ int asr_iou_counts_classes_i32(const int32_t* truth, const int32_t* preds, int64
 /* asr_standard_mask_i32 for K classes: one bilinear upsample + argmax per output pixel, masks [K, h_out, w_out]. */
 int asr_standard_mask_classes_i32(const float* logits0, int32_t* masks, int h_in, int w_in, int classes, int h_out,
                                   int w_out, const int* ids, int K, asr_stream_t stream);
+
+/* --- label maps: the K single-class results of one image fused into one int32 label map ---------------------------
+ * ids: K distinct class ids, a HOST int array as above, each in [1, classes) (classes <= 0: any id >= 1); 0 is the label
+ * of "no class" and never a candidate.  A bad set returns ASR_ERR_INVALID_ARG before any launch.
+ *
+ * Label fusion of one SR type.  scores [K, pixels]: plane k is the float32 SR output S_k of class ids[k], the tensor
+ * asr_threshold_classes_f32 would threshold; max_scores [K, pixels] or NULL: the SR outputs Smax_k of the classes' max maps
+ * (slice_max).  Class k PASSES at pixel p exactly when its single-class mask is set there: S_k(p) > th_factor * max(S_k)
+ * (f32 product, strict, as asr_threshold_f32), or with max_scores S_k(p) >= Smax_k(p).  Its rank value is r_k(p) = S_k(p),
+ * or with max_scores the single f32 subtraction S_k(p) - Smax_k(p).  labels[p] = ids[k*], k* the passing class with the
+ * greatest r_k(p), equal values (-0.0 == +0.0 among them) going to the lowest k; labels[p] = 0 when no class passes.
+ * Inputs are finite.  Hence labels[p] = c != 0 implies that the single-class mask of c is set at p, labels[p] = 0 exactly
+ * when no mask is set, and with K = 1 the label map is the single-class mask, bit for bit.
+ * minmax_ws: [K, 2] floats of scratch, needed when max_scores == NULL (the per-plane extrema, asr_minmax_f32).
+ * truth / counts: both NULL, or a label map [pixels] and int64 [3, 256]: the same pass then leaves in counts what
+ * asr_class_counts_i32(truth, labels) would (zeroed by the call), so the label map is not read back for scoring. */
+int asr_fuse_labels_f32(const float* scores, const float* max_scores, float* minmax_ws, const int32_t* truth, int32_t* labels,
+                        int64_t* counts, int64_t pixels, int K, float th_factor, const int* ids, int classes,
+                        asr_stream_t stream);
+
+/* The standard label map of the same class set: bilinear upsample + argmax of the un-augmented copy's logits (exactly
+ * asr_standard_mask_classes_i32's), the winner kept when it is one of ids, else 0 -- bit for bit the sum over k of that
+ * entry point's K masks, one int32 [h_out, w_out] written once. */
+int asr_standard_labels_i32(const float* logits0, int32_t* labels, int h_in, int w_in, int classes, int h_out, int w_out,
+                            const int* ids, int K, asr_stream_t stream);
 
 /* Per-label pixel counts for the multi-class Mean_IOU (utils.py:151-177, compute_IoU(class_id=None)):
  * counts[seg][0][l] = |truth == l|, counts[seg][1][l] = |pred == l|, counts[seg][2][l] = |truth == l and pred == l|,

@@ -1,14 +1,15 @@
 #!/usr/bin/env python3
-"""Per-class validation table in one run: every image goes through DeepLabV3+ ONCE for all the classes its ground truth
-holds (HotPath.run_image_classes), where the reference runs generate_augmented_copies.py + SR_single_class.py once per class.
-Writes the reference's experiments_data/final_validations/*.csv layout ("Name", the six IoU means, one "Class c" row per
-class found in at least one image) plus a column n_images.
+"""One label map per image and its mean IoU: every image goes through DeepLabV3+ ONCE, the classes of --class_ids are solved
+from that pass (those that win no pixel of any copy are left out, which changes no result: argmax mode) and fused into one
+label map per SR type (HotPath.run_image_labels; the rule is in include/asr_hip.h at asr_fuse_labels_f32).  The class set is
+the same for every image and is never read from the ground truth, so a class predicted where it is absent costs IoU.
 
-Each class keeps the reference's single-class meaning (scripts/validate_labelmap.py fuses them into label maps).  One augmentation draw
-serves all classes of an image: image g gets draw g of the seeded stream over the whole --images list, where a reference
-per-class run draws along its own filtered list -- so each row equals a per-class run FED THE SAME DRAWS.  The Adam step
-counter of class c on image g is what a per-class run over the images holding c reaches (asr_amd.evaluation.evaluate_classes).
-With one process per GPU (torch.distributed.run) images are dealt round-robin over the ranks; one all-gather at the end."""
+Writes a CSV with one row per label the ground truths hold (its IoU from the counts summed over the images, for the standard,
+augmented, max and mean label maps) and both means: "dataset_mIoU", the VOC convention (mean over labels of the IoUs from the
+summed counts), and "mean_image_mIoU", the reference's (np.mean of the per-image Mean_IOU).  Void (255) never counts.
+--save_dir: the label maps as <image stem>_<standard|aug|max|mean>.png.  Draws and Adam step counters as validate_classes.py
+(image g gets draw g of the seeded stream; class c of image g starts where g earlier solves of c leave the counter).  With one
+process per GPU (torch.distributed.run) images are dealt round-robin over the ranks; one all-gather at the end."""
 import argparse
 import os
 import sys
@@ -36,16 +37,18 @@ parser.add_argument("--weights", default=None, help="local Keras .h5 checkpoint 
 parser.add_argument("--th_factor", type=float, default=0.65)
 parser.add_argument("--num_iter", type=int, default=300)
 parser.add_argument("--class_ids", type=int, nargs="+", default=list(range(1, 21)),
-                    help="classes to evaluate (0 and 255 never count)")
-parser.add_argument("--out", default=os.path.join(ROOT, "data", "superres_root", "class_validation.csv"),
+                    help="the class set of every image (0 and 255 are never candidates)")
+parser.add_argument("--out", default=os.path.join(ROOT, "data", "superres_root", "labelmap_validation.csv"),
                     help="CSV file to write")
+parser.add_argument("--save_dir", default=None, help="folder for the label maps as PNG (not written when omitted)")
+parser.add_argument("--no_prune", action="store_true", help="solve every class, also those that win no pixel (same results)")
 
 
 def main():
     args = parser.parse_args()
     import torch
     from asr_amd import distributed as D
-    from asr_amd.evaluation import class_rows, evaluate_classes, write_class_csv
+    from asr_amd.evaluation import LABELMAP_KEYS, dataset_miou, evaluate_labelmaps, write_labelmap_csv
     from asr_amd.model import DeeplabV3Plus
     from asr_amd.pipeline import HotPath
     from asr_amd.superresolution_scripts.optimizer import Optimizer
@@ -66,14 +69,14 @@ def main():
                          lambda_L1=HYPER["lambda_L1"], num_iter=args.num_iter, num_aug=args.num_aug, optimizer=opt,
                          feature_size=(feat, feat), output_size=IMG_SIZE)
     path = HotPath(model, sr, mode=args.mode, th_factor=args.th_factor, batch_size=BATCH_SIZE)
-    table, presence = evaluate_classes(path, paths, gts, class_ids, num_aug=args.num_aug, angle_max=args.angle_max,
-                                       shift_max=args.shift_max, img_size=IMG_SIZE, rank=rank, world=world, seed=SEED)
+    rows, counts = evaluate_labelmaps(path, paths, gts, class_ids, num_aug=args.num_aug, angle_max=args.angle_max,
+                                      shift_max=args.shift_max, img_size=IMG_SIZE, rank=rank, world=world, seed=SEED,
+                                      prune=not args.no_prune, save_dir=args.save_dir)
     if rank == 0:
-        rows = class_rows(table, presence, class_ids)
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        write_class_csv(args.out, rows)
-        for name, means, count in rows:
-            print(f"{name} ({count} images): " + ", ".join(f"{m:.4f}" for m in means))
+        write_labelmap_csv(args.out, counts, rows)
+        for j, key in enumerate(LABELMAP_KEYS):
+            print(f"{key}: dataset mIoU {dataset_miou(counts[j]):.4f}, mean of per-image Mean_IOU {float(rows[:, j].mean()):.4f}")
         print(f"Wrote {args.out}")
     if world > 1:
         torch.distributed.barrier()
