@@ -529,6 +529,146 @@ __global__ __launch_bounds__(256) void fuse_labels_kernel(const float* __restric
     }
 }
 
+// ---- trimap: squared distance to the nearest ground-truth label boundary (asr_boundary_dist2_u16) --------------------------
+// A workgroup owns a 64-column x kDistRows-row output tile.  The strip it needs is the tile's rows +- r_max and the three
+// 64-column words x0 - 64 .. x0 + 127 (r_max <= 64).  Phase 1: a wave walks down a word column of the strip holding the pixel
+// above / at / below in registers, and one ballot per row packs the boundary predicate of its 64 pixels into a 64-bit word in
+// LDS (pixels outside the image give 0 and are never a "different" neighbour).  Phase 2: every strip row gets, for each of the
+// tile's 64 columns, the horizontal distance to the nearest set bit (two 64-bit windows ending / starting at the column, clz
+// and ctz; 0..64, 255 = none) as one byte in LDS.  Phase 3: d2 = min over dy of dx(y + dy)^2 + dy^2, walking dy outwards
+// from 0 and stopping once dy^2 alone is no better than the running minimum (which starts at r_max^2 + 1).  Integer throughout.
+constexpr int kDistRows = 32;
+constexpr int kDistMaxR = 64;
+constexpr int kDistStrip = kDistRows + 2 * kDistMaxR;
+
+__global__ __launch_bounds__(256) void boundary_dist2_kernel(const int32_t* __restrict__ truth, uint16_t* __restrict__ dist2,
+                                                             int h, int w, int r) {
+    __shared__ unsigned long long bits[kDistStrip * 3];
+    __shared__ unsigned char dxs[kDistStrip * 64];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int x0 = blockIdx.x * 64, y0 = blockIdx.y * kDistRows;
+    const int32_t* t = truth + (int64_t)blockIdx.z * h * w;
+    uint16_t* o = dist2 + (int64_t)blockIdx.z * h * w;
+    const int strip = kDistRows + 2 * r;                        // strip row s is image row y0 - r + s
+    // phase 1: wave `wave` takes the strip rows [s_lo, s_hi) of each word column
+    const int per_wave = (strip + 3) >> 2;
+    const int s_lo = wave * per_wave, s_hi = min(strip, s_lo + per_wave);
+    for (int k = 0; k < 3; ++k) {
+        const int c = x0 - 64 + 64 * k + lane;
+        const bool col_in = c >= 0 && c < w;
+        auto at = [&](int y, int cc) { return (y >= 0 && y < h && cc >= 0 && cc < w) ? t[(int64_t)y * w + cc] : 0; };
+        int y = y0 - r + s_lo;
+        int up = at(y - 1, c), cur = at(y, c);
+        for (int s = s_lo; s < s_hi; ++s, ++y) {                // (s_lo, s_hi are wave-uniform: every lane reaches the ballot)
+            const int down = at(y + 1, c);
+            const bool in = col_in && y >= 0 && y < h;
+            const bool edge = in && ((y > 0 && up != cur) || (y + 1 < h && down != cur) || (c > 0 && at(y, c - 1) != cur) ||
+                                     (c + 1 < w && at(y, c + 1) != cur));
+            const unsigned long long word = __ballot(edge);
+            if (lane == 0) bits[s * 3 + k] = word;
+            up = cur;
+            cur = down;
+        }
+    }
+    __syncthreads();
+    // phase 2: column j of the tile sits at bit j of the middle word; L holds the 64 bits ending at it, R the 64 starting at it
+    for (int i = threadIdx.x; i < strip * 64; i += 256) {
+        const int s = i >> 6, j = i & 63;
+        const unsigned long long w0 = bits[s * 3], w1 = bits[s * 3 + 1], w2 = bits[s * 3 + 2];
+        const unsigned long long L = (w1 << (63 - j)) | ((w0 >> j) >> 1);
+        const unsigned long long R = (w1 >> j) | ((w2 << (63 - j)) << 1);
+        int dl = 255, dr = 255;
+        if (L) dl = __clzll((long long)L); else if ((w0 >> j) & 1ull) dl = 64;
+        if (R) dr = __ffsll((long long)R) - 1; else if ((w2 >> j) & 1ull) dr = 64;
+        dxs[i] = (unsigned char)min(dl, dr);
+    }
+    __syncthreads();
+    // phase 3
+    const int r2 = r * r;
+    for (int row = wave; row < kDistRows; row += 4) {
+        const int y = y0 + row, x = x0 + lane;
+        if (y >= h) break;
+        int best = r2 + 1;
+        const int sc = row + r;
+        for (int dy = 0; dy <= r && dy * dy < best; ++dy) {
+            const int a = dxs[(sc - dy) * 64 + lane], b = dxs[(sc + dy) * 64 + lane];
+            const int m = min(a, b);
+            if (m != 255) best = min(best, m * m + dy * dy);
+        }
+        if (x < w) o[(int64_t)y * w + x] = (uint16_t)(best <= r2 ? best : 0xFFFF);
+    }
+}
+
+// ---- trimap: per-label counts inside nested boundary bands (asr_band_class_counts_i32) -----------------------------------
+// The distinct requested widths, ascending, are u_0 < ... < u_{U-1}.  A pixel's rank is the first i with d2 <= u_i^2 (none: the
+// pixel is in no band); it is added once, as class_counts_kernel would add it, into row `rank` of a [U][3][256] workgroup
+// histogram (label_hist_add: the lanes that share lane 0's bin add once).  Grid row p scores prediction p.  The rank
+// histograms are summed into the first U of the B width slots of counts[p]; the finalize kernel then turns each bin's U rank
+// values into prefix sums and writes the B cumulative counts in the caller's width order, in place (a thread owns one bin of
+// one prediction in every slot, and reads all of it before it writes).
+constexpr int kBandMaxWidths = 16;
+constexpr int kBandMaxPreds = 8;
+
+struct AsrBandSet {
+    int n;                              // B: widths as the caller gave them
+    int u;                              // U: distinct widths
+    int w2[kBandMaxWidths];             // u_i^2, ascending
+    int slot[kBandMaxWidths];           // widths[b] == u_{slot[b]}
+};
+
+__global__ __launch_bounds__(256) void band_hist_kernel(const int32_t* __restrict__ truth, const int32_t* __restrict__ preds,
+                                                        const uint16_t* __restrict__ dist2,
+                                                        unsigned long long* __restrict__ counts, int64_t pixels,
+                                                        int ignore_label, AsrBandSet set) {
+    extern __shared__ unsigned int band_hist[];                 // [U][3][256]
+    const int bins = set.u * 768;
+    for (int i = threadIdx.x; i < bins; i += 256) band_hist[i] = 0u;
+    __syncthreads();
+    const int32_t* q = preds + (int64_t)blockIdx.y * pixels;
+    const int lane = threadIdx.x & 63;
+    // the trip count is uniform over the workgroup, so every lane of a wave reaches the ballots together
+    for (int64_t i0 = (int64_t)blockIdx.x * 256; i0 < pixels; i0 += (int64_t)gridDim.x * 256) {
+        const int64_t i = i0 + threadIdx.x;
+        int rank = -1, tv = -1;
+        if (i < pixels) {
+            const int d2 = dist2[i];
+            tv = truth[i];
+            if (tv != ignore_label)
+                for (int k = set.u - 1; k >= 0; --k) rank = d2 <= set.w2[k] ? k : rank;
+        }
+        if (__ballot(rank >= 0) == 0ull) continue;             // wave-uniform: most waves lie outside every band
+        const int pv = rank >= 0 ? q[i] : -1;
+        const bool t_ok = rank >= 0 && tv >= 0 && tv < 256, p_ok = rank >= 0 && pv >= 0 && pv < 256;
+        const int base = (rank >= 0 ? rank : 0) * 768;         // label_hist_add compares keys: the rank goes into the key
+        label_hist_add(band_hist, t_ok ? base + tv : -1, lane);
+        label_hist_add(band_hist, p_ok ? base + 256 + pv : -1, lane);
+        label_hist_add(band_hist, (t_ok && tv == pv) ? base + 512 + tv : -1, lane);
+    }
+    __syncthreads();
+    unsigned long long* g = counts + (int64_t)blockIdx.y * set.n * 768;
+    for (int b = threadIdx.x; b < bins; b += 256)
+        if (band_hist[b]) atomicAdd(g + b, (unsigned long long)band_hist[b]);
+}
+
+__global__ __launch_bounds__(256) void band_finalize_kernel(long long* __restrict__ counts, int num_preds, AsrBandSet set) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= num_preds * 768) return;
+    long long* c = counts + (int64_t)(i / 768) * set.n * 768 + (i % 768);
+    long long pre[kBandMaxWidths];
+    long long run = 0;
+#pragma unroll
+    for (int k = 0; k < kBandMaxWidths; ++k) {
+        if (k < set.u) run += c[(int64_t)k * 768];
+        pre[k] = run;
+    }
+    for (int b = 0; b < set.n; ++b) {
+        long long v = 0;
+#pragma unroll
+        for (int k = 0; k < kBandMaxWidths; ++k) v = (set.slot[b] == k) ? pre[k] : v;     // (no dynamic register indexing)
+        c[(int64_t)b * 768] = v;
+    }
+}
+
 // ---- last_activation: softmax / sigmoid over the class axis (model.py:124-125) ----------------------
 __device__ __forceinline__ void activate_row(const float* row, float* o, int classes, int kind) {     // o may be row
     if (kind == 1) {                       // softmax: exp(x - max) / sum
@@ -867,6 +1007,54 @@ extern "C" int asr_class_activation_f32(const float* logits, float* out, int64_t
     else
         hipLaunchKernelGGL(class_activation_direct_kernel, dim3(stream_grid(pixels)), dim3(256), 0, asr_stream(stream), logits, out,
                            pixels, classes, kind);
+    ASR_LAUNCH_CHECK();
+    return ASR_OK;
+}
+
+extern "C" int asr_boundary_dist2_u16(const int32_t* truth, uint16_t* dist2, int segments, int h, int w, int r_max,
+                                      asr_stream_t stream) {
+    ASR_REQUIRE(truth && dist2, "asr_boundary_dist2_u16: null pointer");
+    ASR_REQUIRE(segments > 0 && segments <= 65535 && h >= 1 && w >= 1 && h <= (1 << 20) && w <= (1 << 20),
+                "asr_boundary_dist2_u16: bad shape (segments=%d h=%d w=%d; 1..65535 segments, sides 1..2^20)", segments, h, w);
+    ASR_REQUIRE(r_max >= 1 && r_max <= kDistMaxR, "asr_boundary_dist2_u16: r_max %d (1..%d)", r_max, kDistMaxR);
+    hipLaunchKernelGGL(boundary_dist2_kernel, dim3((unsigned)asr_cdiv(w, 64), (unsigned)asr_cdiv(h, kDistRows), (unsigned)segments),
+                       dim3(256), 0, asr_stream(stream), truth, dist2, h, w, r_max);
+    ASR_LAUNCH_CHECK();
+    return ASR_OK;
+}
+
+extern "C" int asr_band_class_counts_i32(const int32_t* truth, const int32_t* preds, const uint16_t* dist2, const int* widths,
+                                         int64_t* counts, int64_t pixels, int num_preds, int num_widths, int r_max,
+                                         int ignore_label, asr_stream_t stream) {
+    ASR_REQUIRE(truth && preds && dist2 && counts, "asr_band_class_counts_i32: null pointer");
+    ASR_REQUIRE(widths, "asr_band_class_counts_i32: null width array");
+    ASR_REQUIRE(pixels > 0, "asr_band_class_counts_i32: bad shape (pixels=%lld)", (long long)pixels);
+    ASR_REQUIRE(num_preds >= 1 && num_preds <= kBandMaxPreds, "asr_band_class_counts_i32: %d predictions (1..%d)", num_preds,
+                kBandMaxPreds);
+    ASR_REQUIRE(num_widths >= 1 && num_widths <= kBandMaxWidths, "asr_band_class_counts_i32: %d widths (1..%d)", num_widths,
+                kBandMaxWidths);
+    ASR_REQUIRE(r_max >= 1 && r_max <= kDistMaxR, "asr_band_class_counts_i32: r_max %d (1..%d)", r_max, kDistMaxR);
+    AsrBandSet set = {};
+    set.n = num_widths;
+    for (int b = 0; b < num_widths; ++b) {
+        ASR_REQUIRE(widths[b] >= 1 && widths[b] <= kDistMaxR, "asr_band_class_counts_i32: width %d out of range (1..%d)",
+                    widths[b], kDistMaxR);
+        ASR_REQUIRE(widths[b] <= r_max, "asr_band_class_counts_i32: width %d > r_max %d of the distance map", widths[b], r_max);
+    }
+    for (int v = 1; v <= kDistMaxR; ++v) {                      // the distinct widths, ascending
+        bool used = false;
+        for (int b = 0; b < num_widths; ++b)
+            if (widths[b] == v) { set.slot[b] = set.u; used = true; }
+        if (used) set.w2[set.u++] = v * v;
+    }
+    hipStream_t s = asr_stream(stream);
+    ASR_HIP_CHECK(hipMemsetAsync(counts, 0, sizeof(int64_t) * 768 * (size_t)num_preds * (size_t)num_widths, s));
+    const int grid = stream_grid(pixels) > 64 ? 64 : stream_grid(pixels);
+    hipLaunchKernelGGL(band_hist_kernel, dim3(grid, num_preds), dim3(256), sizeof(unsigned int) * 768 * (size_t)set.u, s, truth,
+                       preds, dist2, reinterpret_cast<unsigned long long*>(counts), pixels, ignore_label, set);
+    ASR_LAUNCH_CHECK();
+    hipLaunchKernelGGL(band_finalize_kernel, dim3((unsigned)asr_cdiv((int64_t)num_preds * 768, 256)), dim3(256), 0, s,
+                       reinterpret_cast<long long*>(counts), num_preds, set);
     ASR_LAUNCH_CHECK();
     return ASR_OK;
 }

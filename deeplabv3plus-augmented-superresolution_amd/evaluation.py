@@ -188,20 +188,33 @@ LABELMAP_KEYS = ("standard", "aug", "max", "mean")
 LABELMAP_CSV_COLUMNS = ("standard_iou", "aug_iou", "max_iou", "mean_iou")
 
 
-def gather_labelmap_records(local_indices, local_miou, local_counts, num_images):
+def gather_labelmap_records(local_indices, local_miou, local_counts, num_images, local_band_miou=None,
+                            local_band_counts=None, num_widths=0):
     """The one collective of evaluate_labelmaps.  local_miou: [n_local, 4] per-image Mean_IOU (LABELMAP_KEYS order);
     local_counts: [n_local, 4, 3, 256] integer counts.  Returns on every rank (rows [num_images, 4] float64, NaN rows where
     no rank reported; summed counts [4, 3, 256] int64).  The counts travel as float64 in the same all-gather as the rows:
-    exact below 2^53 pixels per bin."""
+    exact below 2^53 pixels per bin.
+
+    num_widths = B > 0: the trimap records ride in the same all-gather -- local_band_miou [n_local, 4, B], local_band_counts
+    [n_local, 4, B, 3, 256] -- and the result is (rows, counts, band_rows [num_images, 4, B], band_counts [4, B, 3, 256])."""
     m = len(LABELMAP_KEYS)
+    b = int(num_widths)
     n_local = len(local_indices)
-    rec = np.empty((n_local, m + m * 768), dtype=np.float64)
+    base = m + m * 768
+    width = base + m * b + m * b * 768
+    rec = np.empty((n_local, width), dtype=np.float64)
     if n_local:
         rec[:, :m] = np.asarray(local_miou, dtype=np.float64).reshape(n_local, m)
-        rec[:, m:] = np.asarray(local_counts, dtype=np.int64).reshape(n_local, m * 768)
-    table = D.all_gather_rows(local_indices, rec, num_images, m + m * 768)
-    counts = np.nan_to_num(table[:, m:]).astype(np.int64).reshape(num_images, m, 3, 256)
-    return table[:, :m], counts.sum(axis=0)
+        rec[:, m:base] = np.asarray(local_counts, dtype=np.int64).reshape(n_local, m * 768)
+        if b:
+            rec[:, base:base + m * b] = np.asarray(local_band_miou, dtype=np.float64).reshape(n_local, m * b)
+            rec[:, base + m * b:] = np.asarray(local_band_counts, dtype=np.int64).reshape(n_local, m * b * 768)
+    table = D.all_gather_rows(local_indices, rec, num_images, width)
+    counts = np.nan_to_num(table[:, m:base]).astype(np.int64).reshape(num_images, m, 3, 256)
+    if not b:
+        return table[:, :m], counts.sum(axis=0)
+    band_counts = np.nan_to_num(table[:, base + m * b:]).astype(np.int64).reshape(num_images, m, b, 3, 256)
+    return table[:, :m], counts.sum(axis=0), table[:, base:base + m * b].reshape(num_images, m, b), band_counts.sum(axis=0)
 
 
 def label_ious(counts):
@@ -219,7 +232,7 @@ def dataset_miou(counts):
 
 def evaluate_labelmaps(path, image_paths, gt_paths, class_ids=tuple(range(1, 21)), num_aug=100, angle_max=0.3, shift_max=30,
                        img_size=(512, 512), rank=0, world=1, seed=1234, sr_types=("aug", "max", "mean"), prune=True,
-                       save_dir=None):
+                       save_dir=None, band_widths=None, band_ignore_label=255):
     """One fused label map per image and SR type (HotPath.run_image_labels) and its score.  Returns (rows, counts) on every
     rank: rows [images, 4] per-image Mean_IOU in LABELMAP_KEYS order (the reference's per-image-then-mean convention; NaN for
     an SR type that was not asked for), counts [4, 3, 256] int64 summed over the images (dataset_miou, label_ious).
@@ -228,7 +241,12 @@ def evaluate_labelmaps(path, image_paths, gt_paths, class_ids=tuple(range(1, 21)
     can be predicted there and costs IoU.  Draws: image g gets draw g of distributed.replay_augmentation_stream over the
     whole list, as evaluate_classes.  Adam: every image counts as holding every class, so class c of image g starts at
     num_iter * solves_per_image(mode) * g -- evaluate_classes's rule with an all-true presence -- whatever the sharding and
-    whatever pruning leaves out.  One all-gather at the end.  save_dir: the label maps as <stem>_<key>.png (8-bit)."""
+    whatever pruning leaves out.  One all-gather at the end.  save_dir: the label maps as <stem>_<key>.png (8-bit).
+
+    band_widths (B integers in [1, 64]): the same loop also collects each label map's trimap counts (run_image_labels'
+    band_widths / band_ignore_label) and the return value is (rows, counts, band_rows, band_counts): band_rows [images, 4, B]
+    per-image Mean_IOU inside each band, band_counts [4, B, 3, 256] int64 summed over the images, both NaN / zero for a label
+    map that was not asked for.  They travel in the same all-gather."""
     from .superresolution_scripts.augmentation_utils import _image_to_device
     from . import ops
     import torch
@@ -243,15 +261,21 @@ def evaluate_labelmaps(path, image_paths, gt_paths, class_ids=tuple(range(1, 21)
     mine = D.shard_indices(n_img, rank, world)
     if save_dir:
         os.makedirs(save_dir, exist_ok=True)
-    mious, counts = [], []
+    bands = ops.check_band_widths(band_widths) if band_widths is not None else None
+    n_b = len(bands) if bands else 0
+    mious, counts, band_mious, band_counts = [], [], [], []
     for g in mine:
         image = _image_to_device(load_image(image_paths[g], image_size=img_size, normalize=True))
         gt = ops.to_device(load_label_map(gt_paths[g], img_size), torch.int32, device=image.device)
         angles, shifts = params[g]
+        extra = dict(band_widths=bands, band_ignore_label=band_ignore_label) if bands else {}
         res = path.run_image_labels(image, angles, shifts, class_ids, gt_dev=gt, sr_types=sr_types, prune=prune,
-                                    adam_starts={c: int(starts[g, k]) for k, c in enumerate(class_ids)})
+                                    adam_starts={c: int(starts[g, k]) for k, c in enumerate(class_ids)}, **extra)
         mious.append([res["Mean_IOU"].get(key, np.nan) for key in LABELMAP_KEYS])
         counts.append([res["counts"].get(key, np.zeros((3, 256), np.int64)) for key in LABELMAP_KEYS])
+        if bands:
+            band_mious.append([res["band_Mean_IOU"].get(key, np.full(n_b, np.nan)) for key in LABELMAP_KEYS])
+            band_counts.append([res["band_counts"].get(key, np.zeros((n_b, 3, 256), np.int64)) for key in LABELMAP_KEYS])
         if save_dir:
             from PIL import Image
             stem = os.path.splitext(os.path.basename(image_paths[g]))[0]
@@ -259,7 +283,9 @@ def evaluate_labelmaps(path, image_paths, gt_paths, class_ids=tuple(range(1, 21)
                 if key in res:
                     Image.fromarray(res[key].cpu().numpy().astype(np.uint8), mode="L").save(
                         os.path.join(save_dir, f"{stem}_{key}.png"))
-    return gather_labelmap_records(mine, mious, counts, n_img)
+    if not bands:
+        return gather_labelmap_records(mine, mious, counts, n_img)
+    return gather_labelmap_records(mine, mious, counts, n_img, band_mious, band_counts, n_b)
 
 
 def write_labelmap_csv(path, counts, rows):
@@ -280,6 +306,42 @@ def write_labelmap_csv(path, counts, rows):
         wr.writerow(["dataset_mIoU"] + [repr(dataset_miou(counts[j])) for j in range(len(LABELMAP_KEYS))] + [str(len(rows))])
         wr.writerow(["mean_image_mIoU"] + [repr(float(np.mean(rows[:, j]))) if len(rows) else "nan"
                                            for j in range(len(LABELMAP_KEYS))] + [str(len(rows))])
+
+
+TRIMAP_CSV_COLUMNS = tuple(f"{key}_{kind}" for key in LABELMAP_KEYS for kind in ("band_mIoU", "band_mean_image_mIoU"))
+
+
+def write_trimap_csv(path, widths, band_counts, band_rows, counts=None, ignore_label=255):
+    """One row per band width ("w=<width>", in the caller's order).  For standard / aug / max / mean: "<key>_band_mIoU", the
+    dataset mIoU inside the band (dataset_miou of band_counts [4, B, 3, 256], the counts summed over the images), and
+    "<key>_band_mean_image_mIoU", np.mean of the per-image band Mean_IOU (band_rows [images, 4, B]; a NaN image propagates).
+    "band_pixels": the ground-truth pixels counted in the band (labels 0..255, the ignored label never among them);
+    "band_share": that number over the counted ground-truth pixels of the whole images -- from counts [4, 3, 256], the
+    whole-image counts write_labelmap_csv takes, with ignore_label's pixels (-1 or None: none) taken out; nan without counts.
+    The columns of a label map that was not produced (all-zero counts) are nan.  n = number of images."""
+    import csv
+    ws = [int(v) for v in widths]
+    m = len(LABELMAP_KEYS)
+    band_counts = np.asarray(band_counts, dtype=np.int64).reshape(m, len(ws), 3, 256)
+    band_rows = np.asarray(band_rows, dtype=np.float64).reshape(-1, m, len(ws))
+    total = None
+    if counts is not None:
+        truth = np.asarray(counts, dtype=np.int64).reshape(m, 3, 256)[:, 0].max(axis=0).copy()
+        if ignore_label is not None and 0 <= int(ignore_label) <= 255:
+            truth[int(ignore_label)] = 0
+        total = int(truth.sum())
+    with open(path, "w", newline="") as fh:
+        wr = csv.writer(fh, quoting=csv.QUOTE_ALL, lineterminator="\n")
+        wr.writerow(("Name",) + TRIMAP_CSV_COLUMNS + ("band_pixels", "band_share", "n"))
+        for b, width in enumerate(ws):
+            cells = []
+            for j in range(m):
+                made = bool(band_counts[j].any())           # a label map that was not asked for carries all-zero counts
+                cells.append(repr(dataset_miou(band_counts[j, b])) if made else "nan")
+                cells.append(repr(float(np.mean(band_rows[:, j, b]))) if made and len(band_rows) else "nan")
+            pixels = int(band_counts[:, b, 0].max(axis=0).sum())
+            share = repr(pixels / total) if total else "nan"
+            wr.writerow([f"w={width}"] + cells + [str(pixels), share, str(len(band_rows))])
 
 
 def valid_rows(table, valid=None):

@@ -237,6 +237,57 @@ def class_counts(truth, pred, segments=1):
     return out
 
 
+def check_band_widths(widths, r_max=None):
+    """The widths of a trimap as a list of ints: 1..16 of them, each in [1, 64] (and <= r_max when given); any order, repeats
+    allowed.  Host only; ValueError otherwise."""
+    try:
+        ws = [int(v) for v in widths]
+        same = all(float(v) == float(k) for v, k in zip(widths, ws))
+    except TypeError:
+        raise ValueError(f"band widths must be a sequence of integers, got {widths!r}") from None
+    if not same:
+        raise ValueError(f"band widths must be integers, got {list(widths)}")
+    if not 1 <= len(ws) <= _lib.MAX_BAND_WIDTHS:
+        raise ValueError(f"{len(ws)} band widths (1..{_lib.MAX_BAND_WIDTHS})")
+    bad = [v for v in ws if not 1 <= v <= _lib.MAX_BAND_WIDTH]
+    if bad:
+        raise ValueError(f"band widths must lie in [1, {_lib.MAX_BAND_WIDTH}], got {bad}")
+    if r_max is not None and max(ws) > int(r_max):
+        raise ValueError(f"band width {max(ws)} > r_max {int(r_max)} of the distance map")
+    return ws
+
+
+def boundary_dist2(truth, r_max, segments=1):
+    """int32 label maps [H, W] (segments == 1) or [segments, H, W] -> uint16 of the same shape: the squared distance to the
+    nearest label boundary where it is <= r_max^2, else 0xFFFF (asr_boundary_dist2_u16; 1 <= r_max <= 64)."""
+    if not ((truth.dim() == 2 and segments == 1) or (truth.dim() == 3 and truth.shape[0] == segments)):
+        raise AsrError(f"boundary_dist2: truth must be [H, W] or [{segments}, H, W], got {tuple(truth.shape)}")
+    h, w = truth.shape[-2:]
+    out = torch.empty(tuple(truth.shape), dtype=torch.uint16, device=truth.device)
+    call("asr_boundary_dist2_u16", ptr(truth, torch.int32), ptr(out, torch.uint16), segments, h, w, int(r_max), stream_ptr())
+    return out
+
+
+def band_class_counts(truth, preds, dist2, widths, r_max, ignore_label=255, out=None):
+    """One int32 truth and its dist2 (boundary_dist2 with this r_max), P <= 8 int32 predictions [P, ...] of the same size ->
+    int64 [P, B, 3, 256]: class_counts restricted to the pixels within widths[b] of a label boundary whose truth is not
+    ignore_label (-1: none), in the caller's width order (asr_band_class_counts_i32).  out: a contiguous int64 tensor of
+    that size to write into."""
+    ws = list(widths)
+    per = truth.numel()
+    p = preds.numel() // per if per else 0
+    if per == 0 or p * per != preds.numel() or dist2.numel() != per:
+        raise AsrError("band_class_counts: truth / preds / dist2 size mismatch")
+    if out is None:
+        out = torch.empty((p, len(ws), 3, 256), dtype=torch.int64, device=truth.device)
+    elif out.numel() != p * len(ws) * 768:
+        raise AsrError("band_class_counts: out size mismatch")
+    arr = (C.c_int * max(len(ws), 1))(*[int(v) for v in ws])
+    call("asr_band_class_counts_i32", ptr(truth, torch.int32), ptr(preds, torch.int32), ptr(dist2, torch.uint16), arr,
+         ptr(out, torch.int64), per, p, len(ws), int(r_max), int(ignore_label), stream_ptr())
+    return out.view(p, len(ws), 3, 256)
+
+
 def realign(y, trans_tf, rot_tf, out_hw, mode):
     """mode "max" | "mean" -> [B,H,W]; "both" -> (max, mean) from one pass over the copies."""
     if y.dim() != 4:

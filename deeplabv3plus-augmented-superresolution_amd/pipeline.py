@@ -288,7 +288,8 @@ class HotPath:
 
     # ---- label maps: the classes of an image fused into one label map per SR type, and its Mean_IOU -----------------------
     def run_image_labels(self, image_dev, angles, shifts, class_ids=range(1, 21), gt_dev=None, adam_starts=None,
-                         sr_types=("aug", "max", "mean"), want_standard=True, prune=True, profile=None, keep_scores=False):
+                         sr_types=("aug", "max", "mean"), want_standard=True, prune=True, profile=None, keep_scores=False,
+                         band_widths=None, band_ignore_label=255):
         """One label map per SR type from one forward pass: stage 1 and the solves are run_image_classes's; stage 2 ends in the
         fusion kernel (ops.fuse_labels) instead of K thresholds.  class_ids: K <= 32 distinct ids, none 0 (the label of "no
         class").  At each pixel the label is the class whose single-class mask is set there and whose SR output is greatest
@@ -307,8 +308,15 @@ class HotPath:
         forward pass.  The label maps, the counts and the Adam bookkeeping are those of
         prune=False bit for bit.  The slice and slice_max stacks are dense: prune does nothing there.
         adam_starts: as run_image_classes; a class's start counts ALL requested ids in order, pruned or not, and with None
-        the counter advances past all of them.  Zero classes left is legal: every SR label map is 0."""
+        the counter advances past all of them.  Zero classes left is legal: every SR label map is 0.
+
+        band_widths (with gt_dev; 1..16 integers in [1, 64]): the trimap of include/asr_hip.h.  The result gains "band_counts"
+        {key: int64 [B, 3, 256] numpy, what utils.trimap_counts gives for that label map} and "band_Mean_IOU" {key: float64
+        [B]}, widths in the caller's order; band_ignore_label (-1 or None: none) is left out of every bin.  One distance
+        launch on gt_dev, one band-count launch over all label maps, and the same single copy to the host as "counts".
+        With band_widths=None nothing else is launched and nothing else returned."""
         ids = [int(c) for c in class_ids]
+        bands = ops.check_band_widths(band_widths) if band_widths is not None else None
         if any(c == 0 for c in ids):
             raise ValueError(f"class id 0 is the fallback label, never a candidate: {ids}")
         unknown = [t for t in sr_types if t not in ("aug", "max", "mean")]
@@ -347,7 +355,11 @@ class HotPath:
         counts = None
         if gt_dev is not None:
             gt = (gt_dev if gt_dev.dtype == torch.int32 else gt_dev.to(torch.int32)).contiguous()
-            counts = torch.empty((len(keys), 3, 256), dtype=torch.int64, device=dev)
+            if bands is None:
+                counts = torch.empty((len(keys), 3, 256), dtype=torch.int64, device=dev)
+            else:                                   # one buffer for both sets of counts: they reach the host in one copy
+                both = torch.empty(len(keys) * (1 + len(bands)) * 768, dtype=torch.int64, device=dev)
+                counts = both[:len(keys) * 768].view(len(keys), 3, 256)
             if want_standard:
                 counts[0] = ops.class_counts(gt, maps[0])[0]
         scores = {}
@@ -368,14 +380,26 @@ class HotPath:
                 counts[first:] = ops.class_counts(gt, maps[first])[0]          # one count serves every (equal) zero map
         if adam_starts is None and "aug" in sr_types and sr.optimizer is not None and ids:
             sr.optimizer.optimizer.iterations = starts[-1] + solves * sr.num_iter
+        if bands is not None and gt is not None:
+            r_max = max(bands)
+            ops.band_class_counts(gt, maps, ops.boundary_dist2(gt.view(out_hw[0], out_hw[1]), r_max), bands, r_max,
+                                  -1 if band_ignore_label is None else int(band_ignore_label), out=both[len(keys) * 768:])
         if profile is not None:
             e1.record()
             torch.cuda.synchronize()
             profile["_sr_stage_ms"] = profile.get("_sr_stage_ms", 0.0) + e0.elapsed_time(e1)
         res = {key: maps[j] for j, key in enumerate(keys)}
         res["solved_ids"] = solved
-        if counts is not None:
+        if counts is not None and bands is not None:
+            host = both.cpu().numpy()
+            band = host[len(keys) * 768:].reshape(len(keys), len(bands), 3, 256)
+            host = host[:len(keys) * 768].reshape(len(keys), 3, 256)
+            res["band_counts"] = {key: band[j] for j, key in enumerate(keys)}
+            res["band_Mean_IOU"] = {key: np.array([mean_iou_from_counts(c) for c in band[j]], dtype=np.float64)
+                                    for j, key in enumerate(keys)}
+        elif counts is not None:
             host = counts.cpu().numpy()
+        if counts is not None:
             res["counts"] = {key: host[j] for j, key in enumerate(keys)}
             res["Mean_IOU"] = {key: mean_iou_from_counts(host[j]) for j, key in enumerate(keys)}
         if keep_scores:

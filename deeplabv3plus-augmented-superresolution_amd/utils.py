@@ -116,6 +116,52 @@ def Mean_IOU(y_true, y_pred):
     return mean_iou_from_counts(counts)
 
 
+def _label_map_shape(a, img_size):
+    """(H, W) of a label map given as [H, W], [H, W, 1] or flat with img_size."""
+    shape = tuple(a.shape)
+    if len(shape) == 3 and shape[-1] == 1:
+        shape = shape[:2]
+    if img_size is not None:
+        hw = (int(img_size[0]), int(img_size[1]))
+        if int(np.prod(shape)) != hw[0] * hw[1]:
+            raise ValueError(f"expected {hw[0] * hw[1]} pixels, got {int(np.prod(shape))}")
+        return hw
+    if len(shape) != 2:
+        raise ValueError(f"a label map of shape {shape} needs img_size=(H, W): distances to a boundary are two-dimensional")
+    return shape
+
+
+def trimap_counts(y_true, y_pred, widths, ignore_label=255, img_size=None):
+    """Band counts of one prediction against one ground truth (include/asr_hip.h, "trimap"): int64 [B, 3, 256], row b
+    what ops.class_counts counts over the pixels within widths[b] pixels (Euclidean) of a ground-truth label boundary whose
+    truth is not ignore_label (-1 or None: none ignored; ignored pixels still make boundaries).  widths: 1..16 integers in
+    [1, 64], any order, repeats allowed.  numpy arrays or tensors, [H, W] / [H, W, 1], or flat with img_size."""
+    ws = ops.check_band_widths(widths)
+    ignore = -1 if ignore_label is None else int(ignore_label)
+    h, w = _label_map_shape(y_true if hasattr(y_true, "shape") else np.asarray(y_true), img_size)
+    dev = _lib.require_gpu()
+    t = _as_label_tensor(y_true, dev)
+    p = _as_label_tensor(y_pred, dev)
+    if p.numel() != t.numel():
+        raise ValueError(f"expected {t.numel()} predicted pixels, got {p.numel()}")
+    r_max = max(ws)
+    d2 = ops.boundary_dist2(t.view(h, w), r_max)
+    return ops.band_class_counts(t, p, d2, ws, r_max, ignore)[0].cpu().numpy()
+
+
+def trimap_IoU(y_true, y_pred, widths, class_id=None, ignore_label=255, img_size=None):
+    """float64 [B]: Mean_IOU inside the band of each width (mean_iou_from_counts of trimap_counts), or with class_id the IoU
+    of that label there (NaN where neither map holds it in the band)."""
+    counts = trimap_counts(y_true, y_pred, widths, ignore_label=ignore_label, img_size=img_size)
+    if class_id is None:
+        return np.array([mean_iou_from_counts(c) for c in counts], dtype=np.float64)
+    l = int(class_id)
+    if not 0 <= l <= 255:
+        raise ValueError(f"class_id {l} is not a label 0..255")
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.float64(counts[:, 2, l]) / np.float64(counts[:, 0, l] + counts[:, 1, l] - counts[:, 2, l])
+
+
 def compute_IoU(true_image, image, img_size=(512, 512), class_id=None, include_bg=False):
     """IoU of two label maps (utils.py:207-230): single class (optionally with background) when class_id is given,
     otherwise the multi-class Mean_IOU.  Void (255) pixels are NOT excluded from the single-class form, exactly

@@ -318,6 +318,37 @@ int asr_standard_labels_i32(const float* logits0, int32_t* labels, int h_in, int
 int asr_class_counts_i32(const int32_t* truth, const int32_t* pred, int64_t* counts, int64_t per_segment, int segments,
                          asr_stream_t stream);
 
+/* --- trimap: label maps scored inside bands round the ground truth's label boundaries -----------------------------------
+ * Definitions (everything is integer; nothing is ever rounded):
+ *  - a pixel p of a ground-truth label map T [h, w] (int32) is a BOUNDARY PIXEL when at least one of its 4-neighbours inside
+ *    the image holds a different value.  Void (255) is a value like any other here, so the void ring VOC draws round objects
+ *    makes boundaries; the image border itself makes none;
+ *  - d2(p) is the squared Euclidean distance, in pixels, from p to the nearest boundary pixel (0 on a boundary pixel);
+ *  - the BAND OF WIDTH w (integer, 1 <= w <= 64) is {p : d2(p) <= w * w}.  Bands are nested;
+ *  - ignore_label (-1 = none): pixels whose truth equals it are counted in no bin, but still make boundaries;
+ *  - the band counts of a prediction P against T at width w are counts[0][l], [1][l], [2][l] exactly as
+ *    asr_class_counts_i32 defines them, over the pixels of the band that are not ignored.
+ * Hence with ignore_label = -1 and a band that covers the image, the band counts are asr_class_counts_i32's bit for bit.
+ *
+ * asr_boundary_dist2_u16: truth [segments, h, w] int32 -> dist2 [segments, h, w] uint16 = d2(p) where d2(p) <= r_max^2, else
+ * 0xFFFF (a map without a boundary is all 0xFFFF).  1 <= r_max <= 64, any h, w >= 1, segments <= 65535.  Not a
+ * (2 r_max + 1)^2 window: boundary bits packed by wave ballots, the row distance from two 64-bit windows, then a min over the
+ * rows above and below that stops as soon as the row offset alone exceeds the running minimum. */
+int asr_boundary_dist2_u16(const int32_t* truth, uint16_t* dist2, int segments, int h, int w, int r_max, asr_stream_t stream);
+
+/* Band counts of num_preds (1..8) predictions [num_preds, pixels] against ONE truth [pixels] and its dist2 [pixels] (the four
+ * label maps of an image, shared as asr_iou_counts_shared_truth_i32 shares its truth), for num_widths = B (1..16) widths:
+ * widths is a HOST int array read during the call, any order, repeats allowed, each in [1, 64] and <= r_max, the value the
+ * distance map was built with (the kernel cannot tell it from its inputs).  counts [num_preds, B, 3, 256] int64, zeroed by the
+ * call, in the caller's width order.  Labels outside 0..255 are not counted.  A bad argument returns ASR_ERR_INVALID_ARG
+ * before any launch.  One launch reads the planes once for all widths: each pixel is added once, under the narrowest
+ * requested width that holds it, and a small second launch turns those into the cumulative counts per width.  Cost: 3 KiB of
+ * LDS per DISTINCT width in a workgroup (48 KiB at 16); each prediction is a grid row of its own that re-reads truth and
+ * dist2 (6 bytes per pixel, cache-fed), so the time grows with num_preds and hardly with B. */
+int asr_band_class_counts_i32(const int32_t* truth, const int32_t* preds, const uint16_t* dist2, const int* widths,
+                              int64_t* counts, int64_t pixels, int num_preds, int num_widths, int r_max, int ignore_label,
+                              asr_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * DeepLabV3+ (Xception-65, OS16) layers -- model.py.  BatchNorm is folded by the caller.
  * ------------------------------------------------------------------------------------------ */

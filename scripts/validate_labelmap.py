@@ -9,7 +9,11 @@ augmented, max and mean label maps) and both means: "dataset_mIoU", the VOC conv
 summed counts), and "mean_image_mIoU", the reference's (np.mean of the per-image Mean_IOU).  Void (255) never counts.
 --save_dir: the label maps as <image stem>_<standard|aug|max|mean>.png.  Draws and Adam step counters as validate_classes.py
 (image g gets draw g of the seeded stream; class c of image g starts where g earlier solves of c leave the counter).  With one
-process per GPU (torch.distributed.run) images are dealt round-robin over the ranks; one all-gather at the end."""
+process per GPU (torch.distributed.run) images are dealt round-robin over the ranks; one all-gather at the end.
+
+--band_widths 1,2,4,8,16,32 --trimap_out trimap.csv: the trimap curve as well -- each label map scored only on the pixels within
+w pixels of a ground-truth label boundary (include/asr_hip.h, "trimap"), void (255) pixels left out, one CSV row per width
+(evaluation.write_trimap_csv).  Without these two flags nothing else is computed or written."""
 import argparse
 import os
 import sys
@@ -41,6 +45,9 @@ parser.add_argument("--class_ids", type=int, nargs="+", default=list(range(1, 21
 parser.add_argument("--out", default=os.path.join(ROOT, "data", "superres_root", "labelmap_validation.csv"),
                     help="CSV file to write")
 parser.add_argument("--save_dir", default=None, help="folder for the label maps as PNG (not written when omitted)")
+parser.add_argument("--band_widths", default=None,
+                    help="comma-separated band widths in pixels (1..64, at most 16), e.g. 1,2,4,8,16,32: score the trimap too")
+parser.add_argument("--trimap_out", default=None, help="CSV file for the trimap (default: <--out stem>_trimap.csv)")
 parser.add_argument("--no_prune", action="store_true", help="solve every class, also those that win no pixel (same results)")
 
 
@@ -48,13 +55,16 @@ def main():
     args = parser.parse_args()
     import torch
     from asr_amd import distributed as D
-    from asr_amd.evaluation import LABELMAP_KEYS, dataset_miou, evaluate_labelmaps, write_labelmap_csv
+    from asr_amd.evaluation import LABELMAP_KEYS, dataset_miou, evaluate_labelmaps, write_labelmap_csv, write_trimap_csv
     from asr_amd.model import DeeplabV3Plus
     from asr_amd.pipeline import HotPath
     from asr_amd.superresolution_scripts.optimizer import Optimizer
     from asr_amd.superresolution_scripts.superresolution import Superresolution
     from generate_augmented_copies import list_images
 
+    if args.trimap_out and not args.band_widths:
+        parser.error("--trimap_out needs --band_widths")
+    bands = [int(v) for v in args.band_widths.split(",")] if args.band_widths else None
     rank, world, local_rank = D.init_from_env()
     torch.cuda.set_device(D.local_device(local_rank))
     paths = list_images(args.images, args.num_samples)
@@ -69,15 +79,21 @@ def main():
                          lambda_L1=HYPER["lambda_L1"], num_iter=args.num_iter, num_aug=args.num_aug, optimizer=opt,
                          feature_size=(feat, feat), output_size=IMG_SIZE)
     path = HotPath(model, sr, mode=args.mode, th_factor=args.th_factor, batch_size=BATCH_SIZE)
-    rows, counts = evaluate_labelmaps(path, paths, gts, class_ids, num_aug=args.num_aug, angle_max=args.angle_max,
-                                      shift_max=args.shift_max, img_size=IMG_SIZE, rank=rank, world=world, seed=SEED,
-                                      prune=not args.no_prune, save_dir=args.save_dir)
+    out = evaluate_labelmaps(path, paths, gts, class_ids, num_aug=args.num_aug, angle_max=args.angle_max,
+                             shift_max=args.shift_max, img_size=IMG_SIZE, rank=rank, world=world, seed=SEED,
+                             prune=not args.no_prune, save_dir=args.save_dir, band_widths=bands)
+    rows, counts = out[:2]
     if rank == 0:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         write_labelmap_csv(args.out, counts, rows)
         for j, key in enumerate(LABELMAP_KEYS):
             print(f"{key}: dataset mIoU {dataset_miou(counts[j]):.4f}, mean of per-image Mean_IOU {float(rows[:, j].mean()):.4f}")
         print(f"Wrote {args.out}")
+        if bands:
+            trimap = args.trimap_out or os.path.splitext(os.path.abspath(args.out))[0] + "_trimap.csv"
+            os.makedirs(os.path.dirname(os.path.abspath(trimap)), exist_ok=True)
+            write_trimap_csv(trimap, bands, out[3], out[2], counts=counts)
+            print(f"Wrote {trimap}")
     if world > 1:
         torch.distributed.barrier()
         torch.distributed.destroy_process_group()
