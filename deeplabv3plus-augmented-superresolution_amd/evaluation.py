@@ -6,8 +6,10 @@ from __future__ import annotations
 import os
 
 import numpy as np
+import torch
 
-from . import distributed as D
+from . import distributed as D, ops
+from .superresolution_scripts.augmentation_utils import _image_to_device
 from .superresolution_scripts.superres_utils import DATA_EXTS, compute_SR, load_SR_data, probe_SR_data
 from .utils import compute_IoU, load_image
 
@@ -112,6 +114,24 @@ def class_presence(gt_paths, class_ids, img_size):
     return out
 
 
+def _class_set_run(class_ids, image_paths, gt_paths, rank, world, **draw):
+    """What evaluate_classes and evaluate_labelmaps share before their loops: (the validated class ids, image g's replayed draw
+    params[g] for every image of the whole list, this rank's image indices).  draw: replay_augmentation_stream's arguments."""
+    class_ids = [int(c) for c in class_ids]
+    if any(c in (0, 255) for c in class_ids) or len(set(class_ids)) != len(class_ids):
+        raise ValueError(f"class_ids must be distinct and exclude 0 (background) and 255 (void), got {class_ids}")
+    n_img = len(image_paths)
+    if len(gt_paths) != n_img:
+        raise ValueError(f"{n_img} images but {len(gt_paths)} ground truths")
+    return class_ids, D.replay_augmentation_stream(n_img, **draw), D.shard_indices(n_img, rank, world)
+
+
+def _image_and_labels_on_device(image_path, gt_path, img_size):
+    """(normalised image float32 [H, W, 3], its label map int32 [H, W]), both on the device."""
+    image = _image_to_device(load_image(image_path, image_size=img_size, normalize=True))
+    return image, ops.to_device(load_label_map(gt_path, img_size), torch.int32, device=image.device)
+
+
 def evaluate_classes(path, image_paths, gt_paths, class_ids=tuple(range(1, 21)), num_aug=100, angle_max=0.3, shift_max=30,
                      img_size=(512, 512), rank=0, world=1, seed=1234, sr_types=("aug", "max", "mean")):
     """Per-class evaluation of a set of images with one forward pass per image (HotPath.run_image_classes).  Returns
@@ -124,26 +144,17 @@ def evaluate_classes(path, image_paths, gt_paths, class_ids=tuple(range(1, 21)),
     Adam: class c of image g starts at num_iter * solves_per_image(mode) * #{images before g whose ground truth holds c}
     -- the counter a per-class SR_single_class run over the filtered list reaches.  Every rank reads all label maps to know
     it, so the one all-gather of the results is the only collective."""
-    from .superresolution_scripts.augmentation_utils import _image_to_device
-    from . import ops
-    import torch
-    class_ids = [int(c) for c in class_ids]
-    if any(c in (0, 255) for c in class_ids) or len(set(class_ids)) != len(class_ids):
-        raise ValueError(f"class_ids must be distinct and exclude 0 (background) and 255 (void), got {class_ids}")
+    class_ids, params, mine = _class_set_run(class_ids, image_paths, gt_paths, rank, world, num_aug=num_aug,
+                                             angle_max=angle_max, shift_max=shift_max, seed=seed)
     n_img, k_set = len(image_paths), len(class_ids)
-    if len(gt_paths) != n_img:
-        raise ValueError(f"{n_img} images but {len(gt_paths)} ground truths")
     presence = class_presence(gt_paths, class_ids, img_size)
     starts = D.adam_class_starts(presence, path.sr.num_iter, path.mode)
-    params = D.replay_augmentation_stream(n_img, num_aug, angle_max, shift_max, seed=seed)
-    mine = D.shard_indices(n_img, rank, world)
     rows = []
     for g in mine:
         rec = np.full((k_set, len(D.IOU_FIELDS)), np.nan)
         held = [c for c, p in zip(class_ids, presence[g]) if p]
         if held:
-            image = _image_to_device(load_image(image_paths[g], image_size=img_size, normalize=True))
-            gt = ops.to_device(load_label_map(gt_paths[g], img_size), torch.int32, device=image.device)
+            image, gt = _image_and_labels_on_device(image_paths[g], gt_paths[g], img_size)
             angles, shifts = params[g]
             res = path.run_image_classes(image, angles, shifts, held, gt_dev=gt, sr_types=sr_types,
                                          adam_starts={c: int(starts[g, class_ids.index(c)]) for c in held})
@@ -247,26 +258,17 @@ def evaluate_labelmaps(path, image_paths, gt_paths, class_ids=tuple(range(1, 21)
     band_widths / band_ignore_label) and the return value is (rows, counts, band_rows, band_counts): band_rows [images, 4, B]
     per-image Mean_IOU inside each band, band_counts [4, B, 3, 256] int64 summed over the images, both NaN / zero for a label
     map that was not asked for.  They travel in the same all-gather."""
-    from .superresolution_scripts.augmentation_utils import _image_to_device
-    from . import ops
-    import torch
-    class_ids = [int(c) for c in class_ids]
-    if any(c in (0, 255) for c in class_ids) or len(set(class_ids)) != len(class_ids):
-        raise ValueError(f"class_ids must be distinct and exclude 0 (background) and 255 (void), got {class_ids}")
+    class_ids, params, mine = _class_set_run(class_ids, image_paths, gt_paths, rank, world, num_aug=num_aug,
+                                             angle_max=angle_max, shift_max=shift_max, seed=seed)
     n_img = len(image_paths)
-    if len(gt_paths) != n_img:
-        raise ValueError(f"{n_img} images but {len(gt_paths)} ground truths")
     starts = D.adam_class_starts(np.ones((n_img, len(class_ids)), dtype=bool), path.sr.num_iter, path.mode)
-    params = D.replay_augmentation_stream(n_img, num_aug, angle_max, shift_max, seed=seed)
-    mine = D.shard_indices(n_img, rank, world)
     if save_dir:
         os.makedirs(save_dir, exist_ok=True)
     bands = ops.check_band_widths(band_widths) if band_widths is not None else None
     n_b = len(bands) if bands else 0
     mious, counts, band_mious, band_counts = [], [], [], []
     for g in mine:
-        image = _image_to_device(load_image(image_paths[g], image_size=img_size, normalize=True))
-        gt = ops.to_device(load_label_map(gt_paths[g], img_size), torch.int32, device=image.device)
+        image, gt = _image_and_labels_on_device(image_paths[g], gt_paths[g], img_size)
         angles, shifts = params[g]
         extra = dict(band_widths=bands, band_ignore_label=band_ignore_label) if bands else {}
         res = path.run_image_labels(image, angles, shifts, class_ids, gt_dev=gt, sr_types=sr_types, prune=prune,

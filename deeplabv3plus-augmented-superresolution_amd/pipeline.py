@@ -9,6 +9,8 @@ Used by bench.py, the scripts and the smoke test.
 """
 from __future__ import annotations
 
+import contextlib
+
 import numpy as np
 import torch
 
@@ -40,36 +42,59 @@ class HotPath:
         logits of the un-augmented copy 0 (one kernel)."""
         return ops.standard_mask(logits0.contiguous(), out_hw, self.class_id, out=out)
 
-    # ---- stage 1 (model stream): augment -> forward -> OPM (-> standard mask) --------------------------
-    def _stage_model(self, image_dev, angles, shifts, profile=None, want_standard=True, lane=0):
+    # ---- stage 1 (model stream): augment -> forward -> OPM (-> standard output) ------------------------
+    def _forward_stacks(self, image_dev, angles, shifts, planes, opm, logits0=None, profile=None, lane=0):
         """The copies go through the model one forward batch at a time (augmentation_utils.py:30-59 draws them in chunks
         for the same reason): each batch is augmented straight into the plan's input buffer, its logits are consumed in
-        place by the OPM kernel, which writes its rows of the image's [N,h,w] stack -- nothing of size [N,H,W,3] or
-        [N,h,w,classes] outlives a batch."""
-        out_hw = self.sr.output_size
+        place by the OPM, which writes its rows of the image's stacks -- nothing of size [N,H,W,3] or [N,h,w,classes]
+        outlives a batch.  planes: 1, or the K classes of a class set.  opm(preds, out_rows, out_max_rows) fills the batch's
+        rows [planes, k, fh, fw] of the stacks (out_max_rows: None unless slice_max); logits0, when given, gets copy 0's
+        logits [fh, fw, C] (the standard output is made from them).  Returns the raw stacks y, ymax [planes, N, fh, fw]."""
         n = len(angles)
         h, w, _ = image_dev.shape
         eng = self.model.engine
         bs = min(self.batch_size, n)
-        y = ymax = None                     # [1, N, fh, fw], allocated from the first batch's logits: their size depends on the
-        res = {"_masks": torch.empty((len(self.MASK_KEYS),) + tuple(out_hw), dtype=torch.int32, device=image_dev.device)}
+        y = ymax = None                     # allocated from the first batch's logits: their size depends on the
         for i in range(0, n, bs):
             k = min(bs, n - i)
             copies = au.augment_on_device(image_dev, angles[i:i + k], shifts[i:i + k], out=eng.input_view(k, h, w, lane))
             preds = self.model.predict_device(copies, batch_size=k, profile=profile, lane=lane, clone=False)  # logits stay there
             if y is None:                   # decoder / upsampling options, not only on the backbone's stride
-                y = torch.empty((1, n) + tuple(preds.shape[1:3]), dtype=torch.float32, device=image_dev.device)
+                y = torch.empty((planes, n) + tuple(preds.shape[1:3]), dtype=torch.float32, device=image_dev.device)
                 ymax = torch.empty_like(y) if self.mode == "slice_max" else None
-            if i == 0 and want_standard:
-                res["standard"] = self.standard_mask(self.model.logits_of(preds, 0), out_hw, out=res["_masks"][0])
-            au.output_processing(preds, self.class_id, self.mode, out=y[0, i:i + k],
-                                 out_max=ymax[0, i:i + k] if ymax is not None else None)
+            if i == 0 and logits0 is not None:
+                logits0(self.model.logits_of(preds, 0).contiguous())
+            opm(preds, y[:, i:i + k], ymax[:, i:i + k] if ymax is not None else None)
             del copies, preds
-        if self.mode != "slice":            # load_SR_data's global min-max normalisation (superres_utils.py:183-192)
-            y = self._normalise(y)
+        return y, ymax
+
+    def _stage_model(self, image_dev, angles, shifts, profile=None, want_standard=True, lane=0):
+        """Stage 1 of the single class: (res with the mask buffer and the standard mask, normalised y, ymax [1, N, fh, fw])."""
+        out_hw = self.sr.output_size
+        res = {"_masks": torch.empty((len(self.MASK_KEYS),) + tuple(out_hw), dtype=torch.int32, device=image_dev.device)}
+        opm = lambda preds, out, out_max: au.output_processing(preds, self.class_id, self.mode, out=out[0],
+                                                               out_max=out_max[0] if out_max is not None else None)
+
+        def standard(logits0):
+            res["standard"] = self.standard_mask(logits0, out_hw, out=res["_masks"][0])
+
+        y, ymax = self._forward_stacks(image_dev, angles, shifts, 1, opm, standard if want_standard else None, profile, lane)
+        return (res,) + self._normalise(y, ymax)
+
+    def _classes_stage_model(self, image_dev, angles, shifts, ids, profile, standard):
+        """Stage 1 of a class set: the OPM of every class into raw [K, N, h, w] stacks (y, ymax).
+        standard: None, or a function of copy 0's logits [h, w, C] (the standard masks / label map are made from them)."""
+        opm = lambda preds, out, out_max: au.output_processing_classes(preds, ids, self.mode, out=out, out_max=out_max)
+        return self._forward_stacks(image_dev, angles, shifts, len(ids), opm, standard, profile)
+
+    def _normalise(self, y, ymax):
+        """load_SR_data's global min-max normalisation of each plane's stack to [0, 1] (superres_utils.py:183-206); not in
+        slice mode."""
+        if self.mode != "slice":
+            y = ops.minmax_normalize(y, segments=y.shape[0], new_min=0.0, new_max=1.0)
             if ymax is not None:
-                ymax = self._normalise(ymax)
-        return res, y, ymax
+                ymax = ops.minmax_normalize(ymax, segments=ymax.shape[0], new_min=0.0, new_max=1.0)
+        return y, ymax
 
     def _sr_frame(self, image_dev, shifts):
         """The SR stage applies the copies' shifts in ITS pixel frame (superresolution.py:61-64 translates the HR estimate,
@@ -83,43 +108,65 @@ class HotPath:
         return (np.asarray(shifts, dtype=np.float32) * np.array([Wd / w, H / h], dtype=np.float32)).astype(np.float32)
 
     # ---- stage 2 (any stream): ASR solve, max / mean realign, threshold, IoU counts --------------------
-    def _stage_sr(self, res, y, ymax, angles, shifts, gt_dev, adam_start, sr_types):
+    def _sr_scores(self, y, ymax, angles, fshifts, sr_types, solve):
+        """Stage 2 up to the SR outputs: yields (t, scores [P, H, W], max-map scores [P, H, W] | None) for each SR type, the P
+        planes of the stacks as a batch of the solver / realign.  solve(stack, a, s, second) -> [P, H, W] is the ASR solve of a
+        stack under the angles a [P, N] and shifts s [P, N, 2]; second: the stack is the max map, solved after y."""
         sr = self.sr
-        a, s = angles[None], shifts[None]
+        a = np.repeat(np.asarray(angles, dtype=np.float32)[None], y.shape[0], axis=0)
+        s = np.repeat(np.asarray(fshifts, dtype=np.float32)[None], y.shape[0], axis=0)
         both = None
         if "max" in sr_types and "mean" in sr_types:            # one pass over the copies serves both (bit-identical)
             both = (sr.realign_batch(y, a, s, "both"), sr.realign_batch(ymax, a, s, "both") if ymax is not None else None)
         for t in sr_types:
             if t == "aug":
-                if adam_start is not None:
-                    sr.optimizer.optimizer.iterations = adam_start
-                tgt, _ = sr.augmented_superresolution_batch(y, a, s)
-                tmax = sr.augmented_superresolution_batch(ymax, a, s)[0] if ymax is not None else None
+                tgt = solve(y, a, s, False)
+                tmax = solve(ymax, a, s, True) if ymax is not None else None
             elif both is not None:
-                k = 0 if t == "max" else 1
-                tgt, tmax = both[0][k], (both[1][k] if both[1] is not None else None)
+                j = 0 if t == "max" else 1
+                tgt, tmax = both[0][j], (both[1][j] if both[1] is not None else None)
             else:
                 tgt = sr.realign_batch(y, a, s, t)
                 tmax = sr.realign_batch(ymax, a, s, t) if ymax is not None else None
+            yield t, tgt, tmax
+
+    def _stage_sr(self, res, y, ymax, angles, shifts, gt_dev, adam_start, sr_types):
+        sr = self.sr
+
+        def solve(stack, a, s, second):     # the max map's solve goes on from where y's left the Adam counter
+            if adam_start is not None and not second:
+                sr.optimizer.optimizer.iterations = adam_start
+            return sr.augmented_superresolution_batch(stack, a, s)[0]
+
+        for t, tgt, tmax in self._sr_scores(y, ymax, angles, shifts, sr_types, solve):
             res[t] = self._threshold(tgt[0], tmax[0] if tmax is not None else None,
                                      out=res["_masks"][self.MASK_KEYS.index(t)])
         if gt_dev is not None:
             res["_iou_keys"], res["_iou_counts"] = self._iou_counts(res, gt_dev)
         return res
 
+    @staticmethod
+    @contextlib.contextmanager
+    def _sr_stage_timed(profile):
+        """What runs inside (the SR stage: solve, realign, thresholds or fusion, counts) as one HIP-event interval, added to
+        profile["_sr_stage_ms"]; nothing with profile None."""
+        if profile is None:
+            yield
+            return
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        yield
+        e1.record()
+        torch.cuda.synchronize()
+        profile["_sr_stage_ms"] = profile.get("_sr_stage_ms", 0.0) + e0.elapsed_time(e1)
+
     def run_image(self, image_dev, angles, shifts, gt_dev=None, adam_start=None, profile=None,
                   sr_types=("aug", "max", "mean"), want_standard=True):
         """image_dev [H,W,3] float32 device; angles [N], shifts [N,2] float32 host arrays;
         gt_dev [H,W] int32 device labels (optional).  Returns dict of device masks (+ 6 IoUs)."""
         res, y, ymax = self._stage_model(image_dev, angles, shifts, profile, want_standard)
-        if profile is not None:         # the SR stage (solve, realign, thresholds, IoU counts) as one HIP-event interval
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-        res = self._stage_sr(res, y, ymax, angles, self._sr_frame(image_dev, shifts), gt_dev, adam_start, sr_types)
-        if profile is not None:
-            e1.record()
-            torch.cuda.synchronize()
-            profile["_sr_stage_ms"] = profile.get("_sr_stage_ms", 0.0) + e0.elapsed_time(e1)
+        with self._sr_stage_timed(profile):
+            res = self._stage_sr(res, y, ymax, angles, self._sr_frame(image_dev, shifts), gt_dev, adam_start, sr_types)
         return self._finish(res)
 
     def submit_image(self, image_dev, angles, shifts, gt_dev=None, adam_start=None,
@@ -163,70 +210,37 @@ class HotPath:
         return _Pending(self, res, done, keep=(y, ymax, gt_dev, image_dev))
 
     # ---- class sets: several classes of one image from ONE forward pass --------------------------------------------------
+    @property
+    def _solves(self):
+        """ASR solves per class: its map's, and in slice_max its max map's."""
+        return 2 if self.mode == "slice_max" else 1
+
     def _class_starts(self, ids, adam_starts):
         """Global Adam step counter before each class's solve: adam_starts[c], or consecutive solves in the order of ids
         from the current counter."""
         sr = self.sr
-        solves = 2 if self.mode == "slice_max" else 1
         if adam_starts is None:
             it0 = sr.optimizer.optimizer.iterations if sr.optimizer is not None else 0
-            return [it0 + j * solves * sr.num_iter for j in range(len(ids))]
+            return [it0 + j * self._solves * sr.num_iter for j in range(len(ids))]
         return [int(adam_starts[c]) for c in ids]
 
-    def _classes_stage_model(self, image_dev, angles, shifts, ids, profile, standard):
-        """Stage 1 of a class set: augment -> forward per batch -> OPM of every class into raw [K, N, h, w] stacks (y, ymax).
-        standard: None, or a function of copy 0's logits [h, w, C] (the standard masks / label map are made from them)."""
-        k_set = len(ids)
-        n = len(angles)
-        h, w, _ = image_dev.shape
-        eng = self.model.engine
-        bs = min(self.batch_size, n)
-        y = ymax = None
-        for i in range(0, n, bs):
-            k = min(bs, n - i)
-            copies = au.augment_on_device(image_dev, angles[i:i + k], shifts[i:i + k], out=eng.input_view(k, h, w, 0))
-            preds = self.model.predict_device(copies, batch_size=k, profile=profile, clone=False)
-            if y is None:
-                y = torch.empty((k_set, n) + tuple(preds.shape[1:3]), dtype=torch.float32, device=image_dev.device)
-                ymax = torch.empty_like(y) if self.mode == "slice_max" else None
-            if i == 0 and standard is not None:
-                standard(self.model.logits_of(preds, 0).contiguous())
-            au.output_processing_classes(preds, ids, self.mode, out=y[:, i:i + k],
-                                         out_max=ymax[:, i:i + k] if ymax is not None else None)
-            del copies, preds
-        return y, ymax
-
-    def _classes_normalise(self, y, ymax):
-        """load_SR_data's normalisation, per class stack (not in slice mode)."""
-        if self.mode != "slice":
-            k_set = y.shape[0]
-            y = ops.minmax_normalize(y, segments=k_set, new_min=0.0, new_max=1.0)
-            if ymax is not None:
-                ymax = ops.minmax_normalize(ymax, segments=k_set, new_min=0.0, new_max=1.0)
-        return y, ymax
-
     def _classes_scores(self, y, ymax, angles, fshifts, starts, sr_types):
-        """Stage 2 of a class set up to the SR outputs: yields (t, scores [K, H, W], max-map scores [K, H, W] | None) for each
-        SR type, the K classes as a batch of the existing solver / realign."""
+        """_sr_scores of a class set: class k's solve starts at the Adam step starts[k], its max map's num_iter later; the
+        counter itself is left as it was."""
         sr = self.sr
-        k_set = y.shape[0]
-        a = np.repeat(np.asarray(angles, dtype=np.float32)[None], k_set, axis=0)
-        s = np.repeat(np.asarray(fshifts, dtype=np.float32)[None], k_set, axis=0)
-        both = None
-        if "max" in sr_types and "mean" in sr_types:
-            both = (sr.realign_batch(y, a, s, "both"), sr.realign_batch(ymax, a, s, "both") if ymax is not None else None)
-        for t in sr_types:
-            if t == "aug":
-                tgt, _ = sr.augmented_superresolution_classes(y, angles, fshifts, starts)
-                tmax = (sr.augmented_superresolution_classes(ymax, angles, fshifts, [st + sr.num_iter for st in starts])[0]
-                        if ymax is not None else None)
-            elif both is not None:
-                j = 0 if t == "max" else 1
-                tgt, tmax = both[0][j], (both[1][j] if both[1] is not None else None)
-            else:
-                tgt = sr.realign_batch(y, a, s, t)
-                tmax = sr.realign_batch(ymax, a, s, t) if ymax is not None else None
-            yield t, tgt, tmax
+        solve = lambda stack, a, s, second: sr.augmented_superresolution_classes(
+            stack, a[0], s[0], [st + second * sr.num_iter for st in starts])[0]
+        return self._sr_scores(y, ymax, angles, fshifts, sr_types, solve)
+
+    def _advance_past(self, starts, adam_starts, sr_types):
+        """adam_starts None: the classes counted as consecutive solves, the counter moves past the last of them."""
+        if adam_starts is None and "aug" in sr_types and self.sr.optimizer is not None and starts:
+            self.sr.optimizer.optimizer.iterations = starts[-1] + self._solves * self.sr.num_iter
+
+    @staticmethod
+    def _gt_int32(gt_dev):
+        """The ground truth as a contiguous int32 device tensor."""
+        return (gt_dev if gt_dev.dtype == torch.int32 else gt_dev.to(torch.int32)).contiguous()
 
     def run_image_classes(self, image_dev, angles, shifts, class_ids, gt_dev=None, adam_starts=None,
                           sr_types=("aug", "max", "mean"), want_standard=True, profile=None):
@@ -239,13 +253,9 @@ class HotPath:
         starts num_iter later, as run_image's second solve does); the counter is left as it was.  None: the classes count
         as consecutive run_image calls in the order of class_ids, from the current counter, which advances past them."""
         ids = [int(c) for c in class_ids]
-        k_set = len(ids)
-        sr = self.sr
-        solves = 2 if self.mode == "slice_max" else 1
         starts = self._class_starts(ids, adam_starts)
-        # stage 1: augment -> forward per batch -> OPM of every class into [K, N, h, w] stacks
-        out_hw = sr.output_size
-        masks = torch.empty((len(self.MASK_KEYS), k_set) + tuple(out_hw), dtype=torch.int32, device=image_dev.device)
+        out_hw = self.sr.output_size
+        masks = torch.empty((len(self.MASK_KEYS), len(ids)) + tuple(out_hw), dtype=torch.int32, device=image_dev.device)
         have = []
 
         def standard(logits0):
@@ -253,30 +263,22 @@ class HotPath:
             have.append("standard")
 
         y, ymax = self._classes_stage_model(image_dev, angles, shifts, ids, profile, standard if want_standard else None)
-        y, ymax = self._classes_normalise(y, ymax)
+        y, ymax = self._normalise(y, ymax)
         # stage 2: the K classes as a batch of the existing solver / realign, then K-class threshold and IoU counts
-        if profile is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-        for t, tgt, tmax in self._classes_scores(y, ymax, angles, self._sr_frame(image_dev, shifts), starts, sr_types):
-            row = masks[self.MASK_KEYS.index(t)]
-            if tmax is not None:
-                ops.threshold_classes(tgt, ids, th_mask=tmax, out=row)
-            else:
-                ops.threshold_classes(tgt, ids, th_factor=self.th_factor, out=row)
-            have.append(t)
-        if adam_starts is None and "aug" in sr_types and sr.optimizer is not None:
-            sr.optimizer.optimizer.iterations = starts[-1] + solves * sr.num_iter
-        keys = [key for key in self.MASK_KEYS if key in have]
-        counts = None
-        if gt_dev is not None:
-            gt = gt_dev if gt_dev.dtype == torch.int32 else gt_dev.to(torch.int32)
-            preds = masks[[self.MASK_KEYS.index(key) for key in keys]].transpose(0, 1).contiguous()     # [K, M, H, W]
-            counts = ops.iou_counts_classes(gt.contiguous(), preds, ids, include_bg=True)
-        if profile is not None:
-            e1.record()
-            torch.cuda.synchronize()
-            profile["_sr_stage_ms"] = profile.get("_sr_stage_ms", 0.0) + e0.elapsed_time(e1)
+        with self._sr_stage_timed(profile):
+            for t, tgt, tmax in self._classes_scores(y, ymax, angles, self._sr_frame(image_dev, shifts), starts, sr_types):
+                row = masks[self.MASK_KEYS.index(t)]
+                if tmax is not None:
+                    ops.threshold_classes(tgt, ids, th_mask=tmax, out=row)
+                else:
+                    ops.threshold_classes(tgt, ids, th_factor=self.th_factor, out=row)
+                have.append(t)
+            self._advance_past(starts, adam_starts, sr_types)
+            keys = [key for key in self.MASK_KEYS if key in have]
+            counts = None
+            if gt_dev is not None:
+                preds = masks[[self.MASK_KEYS.index(key) for key in keys]].transpose(0, 1).contiguous()     # [K, M, H, W]
+                counts = ops.iou_counts_classes(self._gt_int32(gt_dev), preds, ids, include_bg=True)
         counts = counts.cpu().numpy() if counts is not None else None
         out = {}
         for j, c in enumerate(ids):
@@ -325,13 +327,10 @@ class HotPath:
         sr_types = [t for t in ("aug", "max", "mean") if t in sr_types]
         if not sr_types and not want_standard:
             raise ValueError("no label map asked for: sr_types holds none of aug / max / mean and want_standard is False")
-        sr = self.sr
-        solves = 2 if self.mode == "slice_max" else 1
         starts = self._class_starts(ids, adam_starts)
-        out_hw = sr.output_size
-        dev = image_dev.device
+        out_hw = self.sr.output_size
         keys = (["standard"] if want_standard else []) + sr_types
-        maps = torch.empty((len(keys),) + tuple(out_hw), dtype=torch.int32, device=dev)
+        maps = torch.empty((len(keys),) + tuple(out_hw), dtype=torch.int32, device=image_dev.device)
         classes = getattr(self.model, "classes", 0)
 
         def standard(logits0):
@@ -347,61 +346,37 @@ class HotPath:
                 y = y[kept].contiguous() if kept else None
         solved = [ids[k] for k in kept]
         if kept:
-            y, ymax = self._classes_normalise(y, ymax)
-        if profile is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-        gt = None
-        counts = None
-        if gt_dev is not None:
-            gt = (gt_dev if gt_dev.dtype == torch.int32 else gt_dev.to(torch.int32)).contiguous()
-            if bands is None:
-                counts = torch.empty((len(keys), 3, 256), dtype=torch.int64, device=dev)
-            else:                                   # one buffer for both sets of counts: they reach the host in one copy
-                both = torch.empty(len(keys) * (1 + len(bands)) * 768, dtype=torch.int64, device=dev)
-                counts = both[:len(keys) * 768].view(len(keys), 3, 256)
-            if want_standard:
-                counts[0] = ops.class_counts(gt, maps[0])[0]
+            y, ymax = self._normalise(y, ymax)
         scores = {}
-        if kept:
-            for t, tgt, tmax in self._classes_scores(y, ymax, angles, self._sr_frame(image_dev, shifts),
-                                                     [starts[k] for k in kept], sr_types):
-                j = keys.index(t)
-                _, c = ops.fuse_labels(tgt, solved, th_factor=self.th_factor, max_scores=tmax, truth=gt, out=maps[j],
-                                       classes=classes)
-                if c is not None:
-                    counts[j] = c
-                if keep_scores:
-                    scores[t] = (tgt, tmax)
-        elif sr_types:
-            first = keys.index(sr_types[0])
-            maps[first:].zero_()
-            if gt is not None:
-                counts[first:] = ops.class_counts(gt, maps[first])[0]          # one count serves every (equal) zero map
-        if adam_starts is None and "aug" in sr_types and sr.optimizer is not None and ids:
-            sr.optimizer.optimizer.iterations = starts[-1] + solves * sr.num_iter
-        if bands is not None and gt is not None:
-            r_max = max(bands)
-            ops.band_class_counts(gt, maps, ops.boundary_dist2(gt.view(out_hw[0], out_hw[1]), r_max), bands, r_max,
-                                  -1 if band_ignore_label is None else int(band_ignore_label), out=both[len(keys) * 768:])
-        if profile is not None:
-            e1.record()
-            torch.cuda.synchronize()
-            profile["_sr_stage_ms"] = profile.get("_sr_stage_ms", 0.0) + e0.elapsed_time(e1)
+        with self._sr_stage_timed(profile):
+            gt = self._gt_int32(gt_dev) if gt_dev is not None else None
+            tally = _LabelCounts(keys, len(bands) if bands else 0, image_dev.device) if gt is not None else None
+            if tally is not None and want_standard:
+                tally.counts[0] = ops.class_counts(gt, maps[0])[0]
+            if kept:
+                for t, tgt, tmax in self._classes_scores(y, ymax, angles, self._sr_frame(image_dev, shifts),
+                                                         [starts[k] for k in kept], sr_types):
+                    j = keys.index(t)
+                    _, c = ops.fuse_labels(tgt, solved, th_factor=self.th_factor, max_scores=tmax, truth=gt, out=maps[j],
+                                           classes=classes)
+                    if c is not None:
+                        tally.counts[j] = c
+                    if keep_scores:
+                        scores[t] = (tgt, tmax)
+            elif sr_types:
+                first = keys.index(sr_types[0])
+                maps[first:].zero_()
+                if gt is not None:
+                    tally.counts[first:] = ops.class_counts(gt, maps[first])[0]          # one count serves every (equal) zero map
+            self._advance_past(starts, adam_starts, sr_types)
+            if bands is not None and gt is not None:
+                r_max = max(bands)
+                ops.band_class_counts(gt, maps, ops.boundary_dist2(gt.view(out_hw[0], out_hw[1]), r_max), bands, r_max,
+                                      -1 if band_ignore_label is None else int(band_ignore_label), out=tally.band)
         res = {key: maps[j] for j, key in enumerate(keys)}
         res["solved_ids"] = solved
-        if counts is not None and bands is not None:
-            host = both.cpu().numpy()
-            band = host[len(keys) * 768:].reshape(len(keys), len(bands), 3, 256)
-            host = host[:len(keys) * 768].reshape(len(keys), 3, 256)
-            res["band_counts"] = {key: band[j] for j, key in enumerate(keys)}
-            res["band_Mean_IOU"] = {key: np.array([mean_iou_from_counts(c) for c in band[j]], dtype=np.float64)
-                                    for j, key in enumerate(keys)}
-        elif counts is not None:
-            host = counts.cpu().numpy()
-        if counts is not None:
-            res["counts"] = {key: host[j] for j, key in enumerate(keys)}
-            res["Mean_IOU"] = {key: mean_iou_from_counts(host[j]) for j, key in enumerate(keys)}
+        if tally is not None:
+            res.update(tally.to_host())
         if keep_scores:
             res["scores"] = scores
         return res
@@ -412,11 +387,6 @@ class HotPath:
             res["ious"] = self._ious_from_counts(res.pop("_iou_keys"), res.pop("_iou_counts").cpu().numpy())
         return res
 
-    @staticmethod
-    def _normalise(stack):
-        """load_SR_data's global min-max normalisation of an image's masks to [0, 1] (superres_utils.py:183-206)."""
-        return ops.minmax_normalize(stack.contiguous(), segments=1, new_min=0.0, new_max=1.0)
-
     def _iou_counts(self, res, gt_dev):
         """Integer intersection / union counts of every produced mask against the ground truth (device): one launch over
         the image's mask buffer; rows of masks that were not asked for are ignored."""
@@ -425,8 +395,7 @@ class HotPath:
         masks = res["_masks"]
         if rows != list(range(len(self.MASK_KEYS))):                    # a subset of the four masks: compact it
             masks = masks[rows].contiguous()
-        gt = gt_dev if gt_dev.dtype == torch.int32 else gt_dev.to(torch.int32)
-        return keys, ops.iou_counts_shared_truth(gt.contiguous(), masks, self.class_id, include_bg=True)
+        return keys, ops.iou_counts_shared_truth(self._gt_int32(gt_dev), masks, self.class_id, include_bg=True)
 
     @staticmethod
     def _ious_from_counts(keys, counts):
@@ -439,6 +408,31 @@ class HotPath:
 
         return np.array([iou("standard", False), iou("standard", True), iou("aug", False), iou("aug", True),
                          iou("max", False), iou("mean", False)], dtype=np.float64)
+
+
+class _LabelCounts:
+    """The counts of run_image_labels on the device, one int64 allocation so that they reach the host in one copy: per label
+    map (in the order of keys) the [3, 256] whole-image counts, then, with B band widths, its [B, 3, 256] band counts."""
+
+    def __init__(self, keys, n_bands, device):
+        self.keys, self.n_bands = keys, n_bands
+        self._split = len(keys) * 768
+        self._buf = torch.empty(self._split * (1 + n_bands), dtype=torch.int64, device=device)
+        self.counts = self._buf[:self._split].view(len(keys), 3, 256)
+        self.band = self._buf[self._split:]             # [len(keys), B, 3, 256], flat: ops.band_class_counts's out
+
+    def to_host(self):
+        """The "counts" / "Mean_IOU" (and "band_counts" / "band_Mean_IOU") entries of the result."""
+        host = self._buf.cpu().numpy()
+        counts = host[:self._split].reshape(len(self.keys), 3, 256)
+        res = {"counts": {key: counts[j] for j, key in enumerate(self.keys)},
+               "Mean_IOU": {key: mean_iou_from_counts(counts[j]) for j, key in enumerate(self.keys)}}
+        if self.n_bands:
+            band = host[self._split:].reshape(len(self.keys), self.n_bands, 3, 256)
+            res["band_counts"] = {key: band[j] for j, key in enumerate(self.keys)}
+            res["band_Mean_IOU"] = {key: np.array([mean_iou_from_counts(c) for c in band[j]], dtype=np.float64)
+                                    for j, key in enumerate(self.keys)}
+        return res
 
 
 class _Pending:

@@ -16,25 +16,15 @@ from bench import shifted_weights, synth_image
 from conftest import GOLDEN, ROOT
 from test_labelmap_host import counts_numpy, fuse_numpy
 
+sys.path.insert(0, GOLDEN)
+from make_hotpath_traces import shift_classes as _shift_classes, small_inputs  # noqa: E402
+
 pytestmark = pytest.mark.gpu
 
 WIN = [3, 8, 15]                         # classes whose logit bias is shifted until they win a share of the pixels
 REQ = [5, 3, 12, 8, 17, 15]              # requested set, unordered: the shifted classes between classes left alone
 KEYS = ("standard", "aug", "max", "mean")
 TH = 0.2
-
-
-def _shift_classes(model, image_dev, ids, fraction=0.25):
-    """engine.shift_logit_bias for each class in turn (tools/bench_class_sets.py): class c then wins on about `fraction` of the
-    un-augmented image's pixels; seeded synthetic weights never make it win by themselves."""
-    out = {}
-    for c in ids:
-        logits = model.predict_device(image_dev[None].contiguous(), batch_size=1)[0]
-        other = logits.clone()
-        other[..., c] = float("-inf")
-        out[c] = float(torch.quantile((other.max(dim=-1).values - logits[..., c]).flatten(), fraction))
-        model.engine.shift_logit_bias(c, out[c])
-    return out
 
 
 def _winners(model, img, angles, shifts):
@@ -59,19 +49,7 @@ def _sr(kind, n, iters, feat, out, use_btv):
 
 @pytest.fixture(scope="module")
 def small(dev):
-    from asr_amd import ops, weights as W
-    from asr_amd.model import DeeplabModel
-    from asr_amd.superresolution_scripts.augmentation_utils import draw_augmentation_parameters
-    model = DeeplabModel(W.make_synthetic_weights(1234, 21), (64, 64, 3), 21, False, None)      # Xception, OS 16
-    img = ops.to_device(synth_image(np.random.default_rng(21), 64), device=dev)
-    _shift_classes(model, img, WIN)
-    logits0 = model.predict_device(img[None].contiguous(), batch_size=1)[0].contiguous()
-    gt = ops.standard_mask_classes(logits0, (64, 64), WIN).sum(dim=0).to(torch.int32)
-    gt[32:34] = 255                                                                             # a void band
-    gt[:8, :8] = 12                                                                             # a class the model never predicts
-    np.random.seed(17)
-    angles, shifts = draw_augmentation_parameters(6, 0.15, 8)
-    return model, img, gt.contiguous(), angles, shifts
+    return small_inputs(dev)
 
 
 @pytest.mark.parametrize("mode", ["argmax", "slice", "slice_max"])
