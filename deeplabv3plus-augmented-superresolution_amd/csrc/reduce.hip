@@ -70,8 +70,8 @@ __device__ __forceinline__ int argmax_row(const float* __restrict__ row, int cla
 // (stride of `classes` words: conflict-free for odd class counts such as 21).  kMaxStageClasses bounds the LDS tile.
 constexpr int kMaxStageClasses = 32;
 
-__device__ __forceinline__ const float* stage_rows(const float* __restrict__ logits, int64_t first, int64_t pixels, int classes,
-                                                   float* __restrict__ tile) {
+__device__ __forceinline__ float* stage_rows(const float* __restrict__ logits, int64_t first, int64_t pixels, int classes,
+                                             float* __restrict__ tile) {
     const int64_t rows = min((int64_t)256, pixels - first);
     const int64_t n = rows * classes;
     const float* src = logits + first * classes;
@@ -80,14 +80,16 @@ __device__ __forceinline__ const float* stage_rows(const float* __restrict__ log
     return tile + (int64_t)threadIdx.x * classes;
 }
 
+// STAGED: the rows go through LDS; else the same walk straight from global memory, for class counts beyond the LDS tile
+template <bool STAGED>
 __global__ __launch_bounds__(256) void argmax_kernel(const float* __restrict__ logits, int32_t* __restrict__ out,
                                                      int64_t pixels, int classes) {
-    __shared__ float tile[256 * kMaxStageClasses];
+    __shared__ float tile[STAGED ? 256 * kMaxStageClasses : 1];
     for (int64_t first = (int64_t)blockIdx.x * 256; first < pixels; first += (int64_t)gridDim.x * 256) {
-        const float* row = stage_rows(logits, first, pixels, classes, tile);
         const int64_t p = first + threadIdx.x;
+        const float* row = STAGED ? stage_rows(logits, first, pixels, classes, tile) : logits + p * classes;
         if (p < pixels) out[p] = argmax_row(row, classes);
-        __syncthreads();
+        if (STAGED) __syncthreads();
     }
 }
 
@@ -102,13 +104,7 @@ __global__ __launch_bounds__(256) void opm_argmax_kernel(const float* __restrict
     }
 }
 
-// same walks straight from global memory, for class counts beyond the LDS tile
-__global__ __launch_bounds__(256) void argmax_direct_kernel(const float* __restrict__ logits, int32_t* __restrict__ out,
-                                                            int64_t pixels, int classes) {
-    for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < pixels; p += (int64_t)gridDim.x * 256)
-        out[p] = argmax_row(logits + p * classes, classes);
-}
-
+// opm_argmax_kernel's walk straight from global memory, for class counts beyond the LDS tile
 __global__ __launch_bounds__(256) void opm_argmax_direct_kernel(const float* __restrict__ logits, float* __restrict__ out,
                                                                 int64_t pixels, int classes, int class_id) {
     for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < pixels; p += (int64_t)gridDim.x * 256)
@@ -317,6 +313,18 @@ __global__ __launch_bounds__(256) void iou_counts_classes_kernel(const int32_t* 
     }
 }
 
+// One histogram add per lane (key -1: none).  Most pixels of a wave share one bin (the background): the lanes that hold lane
+// 0's key add once, by popcount, the others one by one.  Every lane of the wave must reach the call.
+__device__ __forceinline__ void label_hist_add(unsigned int* __restrict__ h, int key, int lane) {
+    const int lead = __shfl(key, 0, 64);
+    const unsigned long long same = __ballot(key == lead);
+    if (key == lead) {
+        if (key >= 0 && lane == __ffsll((long long)same) - 1) atomicAdd(h + key, (unsigned int)__popcll(same));
+    } else if (key >= 0) {
+        atomicAdd(h + key, 1u);
+    }
+}
+
 // ---- threshold sweep: IoU counts of K threshold factors in one pass (threshold_tests.py:113-121) ------------------
 // counts[s][k] equals asr_threshold_f32(image_s, NULL, factors[k]) followed by asr_iou_counts_i32: the pixel is predicted
 // class_id when v > max_s * factors[k] (f32 product, strict >), else 0.  Each workgroup ranks the K thresholds in LDS
@@ -360,7 +368,7 @@ __global__ __launch_bounds__(256) void threshold_sweep_hist_kernel(const float* 
     const float* p = img + (int64_t)seg * per_seg;
     const int32_t* t = truth + (int64_t)seg * truth_stride;              // truth_stride 0: one label map for every image
     unsigned int* h = sub[wave];
-    // the trip count is uniform over the workgroup, so every lane of a wave reaches the shuffle below together
+    // the trip count is uniform over the workgroup, so every lane of a wave reaches label_hist_add together
     for (int64_t i0 = (int64_t)blockIdx.x * 256; i0 < per_seg; i0 += (int64_t)gridDim.x * 256) {
         const int64_t i = i0 + threadIdx.x;
         int key = -1;
@@ -376,14 +384,7 @@ __global__ __launch_bounds__(256) void threshold_sweep_hist_kernel(const float* 
             const int cat = (tv == class_id ? 1 : 0) | (tv == 0 ? 2 : 0);
             key = cat * (K + 1) + lo;
         }
-        // most pixels of a wave share one bin (r == 0 on the background): the lanes of lane 0's bin add once, by popcount
-        const int lead = __shfl(key, 0, 64);
-        const unsigned long long same = __ballot(key == lead);
-        if (key == lead) {
-            if (key >= 0 && lane == __ffsll((long long)same) - 1) atomicAdd(h + key, (unsigned int)__popcll(same));
-        } else if (key >= 0) {
-            atomicAdd(h + key, 1u);
-        }
+        label_hist_add(h, key, lane);
     }
     __syncthreads();
     unsigned long long* g = hist + (int64_t)seg * bins;
@@ -465,16 +466,6 @@ __global__ __launch_bounds__(256) void class_counts_kernel(const int32_t* __rest
 // wave's lanes that share lane 0's label (the background, mostly) add once by popcount, the others one by one, into a
 // workgroup histogram in LDS that leaves through one 64-bit atomic per non-empty bin.  Out-of-range lanes carry key -1; the trip
 // count is uniform over the workgroup, so every lane reaches the shuffles together.
-__device__ __forceinline__ void label_hist_add(unsigned int* __restrict__ h, int key, int lane) {
-    const int lead = __shfl(key, 0, 64);
-    const unsigned long long same = __ballot(key == lead);
-    if (key == lead) {
-        if (key >= 0 && lane == __ffsll((long long)same) - 1) atomicAdd(h + key, (unsigned int)__popcll(same));
-    } else if (key >= 0) {
-        atomicAdd(h + key, 1u);
-    }
-}
-
 template <bool HAS_MAX, bool HAS_TRUTH>
 __global__ __launch_bounds__(256) void fuse_labels_kernel(const float* __restrict__ scores, const float* __restrict__ maxs,
                                                           const float* __restrict__ seg_minmax, const int32_t* __restrict__ truth,
@@ -684,31 +675,26 @@ __device__ __forceinline__ void activate_row(const float* row, float* o, int cla
 
 // Rows of `classes` floats (84 bytes for 21 classes) walked by one thread each are 64-way strided gathers and scatters
 // (measured 0.44 TB/s on the [100,128,128,21] logits of BASELINE configs[2]); like argmax_kernel, a workgroup moves its
-// 256 rows through LDS with coalesced loads and stores and the threads work on the LDS rows, in place.
+// 256 rows through LDS with coalesced loads and stores and the threads work on the LDS rows, in place (STAGED), or, beyond
+// the LDS tile, each thread on its own row in global memory.
+template <bool STAGED>
 __global__ __launch_bounds__(256) void class_activation_kernel(const float* __restrict__ logits, float* __restrict__ out,
                                                               int64_t pixels, int classes, int kind) {
-    __shared__ float tile[256 * kMaxStageClasses];
+    __shared__ float tile[STAGED ? 256 * kMaxStageClasses : 1];
     for (int64_t first = (int64_t)blockIdx.x * 256; first < pixels; first += (int64_t)gridDim.x * 256) {
-        const int64_t rows = min((int64_t)256, pixels - first);
-        const int64_t n = rows * classes;
-        const float* src = logits + first * classes;
-        for (int64_t i = threadIdx.x; i < n; i += 256) tile[i] = src[i];
-        __syncthreads();
-        if ((int64_t)threadIdx.x < rows) {
-            float* row = tile + (int64_t)threadIdx.x * classes;
-            activate_row(row, row, classes, kind);            // every o[c] is written after the last read of row[c'] it needs:
-        }                                                     // softmax re-reads row[c] right before overwriting it
-        __syncthreads();
-        float* dst = out + first * classes;
-        for (int64_t i = threadIdx.x; i < n; i += 256) dst[i] = tile[i];
-        __syncthreads();
+        const int64_t p = first + threadIdx.x;
+        float* o = STAGED ? stage_rows(logits, first, pixels, classes, tile) : out + p * classes;
+        // in place on an LDS row, every o[c] is written after the last read of row[c'] it needs: softmax re-reads row[c]
+        // right before overwriting it
+        if (p < pixels) activate_row(STAGED ? o : logits + p * classes, o, classes, kind);
+        if (STAGED) {
+            __syncthreads();
+            const int64_t n = min((int64_t)256, pixels - first) * classes;
+            float* dst = out + first * classes;
+            for (int64_t i = threadIdx.x; i < n; i += 256) dst[i] = tile[i];
+            __syncthreads();
+        }
     }
-}
-
-__global__ __launch_bounds__(256) void class_activation_direct_kernel(const float* __restrict__ logits, float* __restrict__ out,
-                                                                     int64_t pixels, int classes, int kind) {
-    for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < pixels; p += (int64_t)gridDim.x * 256)
-        activate_row(logits + p * classes, out + p * classes, classes, kind);
 }
 
 int stream_grid(int64_t n) {
@@ -739,9 +725,9 @@ extern "C" int asr_argmax_i32(const float* logits, int32_t* out, int64_t pixels,
     ASR_REQUIRE(logits && out, "asr_argmax_i32: null pointer");
     ASR_REQUIRE(pixels > 0 && classes > 0, "asr_argmax_i32: bad shape");
     if (classes <= kMaxStageClasses)
-        hipLaunchKernelGGL(argmax_kernel, dim3(stream_grid(pixels)), dim3(256), 0, asr_stream(stream), logits, out, pixels, classes);
+        hipLaunchKernelGGL(argmax_kernel<true>, dim3(stream_grid(pixels)), dim3(256), 0, asr_stream(stream), logits, out, pixels, classes);
     else
-        hipLaunchKernelGGL(argmax_direct_kernel, dim3(stream_grid(pixels)), dim3(256), 0, asr_stream(stream), logits, out, pixels, classes);
+        hipLaunchKernelGGL(argmax_kernel<false>, dim3(stream_grid(pixels)), dim3(256), 0, asr_stream(stream), logits, out, pixels, classes);
     ASR_LAUNCH_CHECK();
     return ASR_OK;
 }
@@ -1002,10 +988,10 @@ extern "C" int asr_class_activation_f32(const float* logits, float* out, int64_t
     ASR_REQUIRE(logits && out, "asr_class_activation_f32: null pointer");
     ASR_REQUIRE(pixels > 0 && classes > 0 && (kind == 1 || kind == 2), "asr_class_activation_f32: bad arguments (kind 1 = softmax, 2 = sigmoid)");
     if (classes <= kMaxStageClasses)
-        hipLaunchKernelGGL(class_activation_kernel, dim3(stream_grid(pixels)), dim3(256), 0, asr_stream(stream), logits, out, pixels,
+        hipLaunchKernelGGL(class_activation_kernel<true>, dim3(stream_grid(pixels)), dim3(256), 0, asr_stream(stream), logits, out, pixels,
                            classes, kind);
     else
-        hipLaunchKernelGGL(class_activation_direct_kernel, dim3(stream_grid(pixels)), dim3(256), 0, asr_stream(stream), logits, out,
+        hipLaunchKernelGGL(class_activation_kernel<false>, dim3(stream_grid(pixels)), dim3(256), 0, asr_stream(stream), logits, out,
                            pixels, classes, kind);
     ASR_LAUNCH_CHECK();
     return ASR_OK;

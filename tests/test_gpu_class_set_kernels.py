@@ -23,11 +23,11 @@ def _first_argmax(x):
     return np.argmax(x, axis=-1)             # numpy: first maximum, like tf.argmax and the kernels
 
 
-def make_logits(classes, ids, seed):
+def make_logits(classes, ids, seed, shape=SHAPE):
     """Seeded [copies, h, w, classes] logits in which every id of `ids` wins >= 1 % of the pixels and ties for the maximum
     on some; rows of +-0.0 maxima and rows scaled to ~1e4."""
     rng = np.random.default_rng(seed)
-    n = int(np.prod(SHAPE))
+    n = int(np.prod(shape))
     x = rng.standard_normal((n, classes)).astype(np.float32)
     big = rng.random(n) < 0.2
     x[big] *= np.float32(1e4)
@@ -61,7 +61,7 @@ def make_logits(classes, ids, seed):
         assert (at_max[:, c] & (at_max.sum(axis=1) >= 2)).any(), c
     assert (x == 0).any() and np.signbit(x[x == 0]).any() and (~np.signbit(x[x == 0])).any()
     assert np.abs(x).max() > 1e4
-    return x.reshape(SHAPE + (classes,))
+    return x.reshape(tuple(shape) + (classes,))
 
 
 def _bits(t):

@@ -7,8 +7,9 @@
 classes made to win by logit-bias shifts, on --images synthetic images after two warm-up images.  --impl single: one
 HotPath.run_image per class (what a per-class table costs without class sets); --impl classes: HotPath.run_image_classes.
 Prints one JSON line: ms per image, and the SR-stage time per image (profile["_sr_stage_ms"], from a second, profiled pass).
---what opm: the OPM kernels alone on one configs[1] forward batch of logits [16, 128, 128, 21], argmax and slice_max, 20 calls
-each (single: class 8; classes: K = 4) -- run it under rocprofv3 --kernel-trace --stats for kernel times.
+--what opm: the output-processing kernels alone, 20 calls each: argmax, slice and slice_max on one configs[1] forward batch of
+logits [16, 128, 128, 21], and the standard mask of its first map [128, 128, 21] at 512 x 512 (single: class 8; classes: K = 4).
+Run it under rocprofv3 --kernel-trace --stats for kernel times.
 --root: the tree whose asr_amd is imported (default: this one), so that an older checkout can be measured by the same code.
 """
 import argparse
@@ -43,13 +44,21 @@ def opm():
     dev = torch.device("cuda", 0)
     g = torch.Generator(device=dev).manual_seed(0)
     logits = (torch.randn((16, 128, 128, 21), generator=g, device=dev) * 3.0).contiguous()
-    for mode in ("argmax", "slice_max"):
+    single = {"argmax": ops.opm_argmax, "slice": ops.opm_slice, "slice_max": ops.opm_slice_max}
+    for mode in ("argmax", "slice", "slice_max"):
         for _ in range(20):
             if args.impl == "single":
-                (ops.opm_argmax(logits, 8) if mode == "argmax" else ops.opm_slice_max(logits, 8))
+                single[mode](logits, 8)
             else:
                 ops.opm_classes(logits, [3, 8, 12, 15], mode)
         torch.cuda.synchronize()
+    logits0 = logits[0].contiguous()
+    for _ in range(20):
+        if args.impl == "single":
+            ops.standard_mask(logits0, (512, 512), 8)
+        else:
+            ops.standard_mask_classes(logits0, (512, 512), [3, 8, 12, 15])
+    torch.cuda.synchronize()
     print(json.dumps({"what": "opm", "impl": args.impl, "root": args.root}))
 
 
