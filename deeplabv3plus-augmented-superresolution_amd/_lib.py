@@ -35,6 +35,8 @@ _sz = C.c_size_t
 _ip = C.POINTER(C.c_int)         # host int arrays read during the call (class sets)
 MAX_CLASS_SET = 32               # ASR_MAX_CLASS_SET
 MAX_BAND_WIDTH, MAX_BAND_WIDTHS, MAX_BAND_PREDS = 64, 16, 8     # asr_band_class_counts_i32's limits
+MAX_CONFUSION_LABELS, MAX_CONFUSION_PREDS = 64, 8               # ASR_CONFUSION_MAX_LABELS / _MAX_PREDS
+CONFUSION_SPAN, CONFUSION_GRID = 1024, 64                        # ASR_CONFUSION_SPAN / _GRID: pixels of a workgroup's trip, row cap
 OPM_MODES = {"argmax": 0, "slice": 1, "slice_max": 2}     # ASR_OPM_*
 
 OPT_ADAM, OPT_SGD, OPT_ADAGRAD, OPT_ADADELTA, OPT_ADAMAX = 0, 1, 2, 3, 4
@@ -93,6 +95,7 @@ SIGNATURES = {
     "asr_class_counts_i32": (_i, [_vp, _vp, _vp, _i64, _i, _vp]),
     "asr_boundary_dist2_u16": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "asr_band_class_counts_i32": (_i, [_vp, _vp, _vp, _ip, _vp, _i64, _i, _i, _i, _i, _vp]),
+    "asr_confusion_counts_i32": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp]),
     "asr_pwconv_packed_floats": (_sz, [_i, _i]),
     "asr_pwconv_pack_weights_f32": (_i, [_vp, _vp, _i, _i, _vp]),
     "asr_pwconv_mfma_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),

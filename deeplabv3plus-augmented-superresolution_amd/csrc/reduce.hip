@@ -660,6 +660,44 @@ __global__ __launch_bounds__(256) void band_finalize_kernel(long long* __restric
     }
 }
 
+// ---- confusion matrix: (truth label, predicted label) pair counts of label maps (asr_confusion_counts_i32) ----------------
+// bin(v) = v for 0 <= v < L, else L ("other").  A pixel is one key bin(t) * (L + 1) + bin(p), added with label_hist_add into a
+// workgroup histogram of (L + 1)^2 bins in LDS (most pixels of a wave are background on background: one popcount add); every
+// non-empty bin then leaves through one 64-bit atomic.  Grid row p scores prediction p.  A thread takes kConfPerThread pixels
+// per trip, a workgroup stride apart, and loads them all before the first add: at 512^2 a grid row's workgroup has 4096
+// pixels, so the kernel is a few dependent load round trips long and its time goes with their number, not with LDS or HBM.
+constexpr int kConfPerThread = ASR_CONFUSION_SPAN / 256;
+static_assert(kConfPerThread * 256 == ASR_CONFUSION_SPAN, "a workgroup's trip is a whole number of pixels per thread");
+
+__device__ __forceinline__ int conf_bin(int v, int L) { return (unsigned int)v < (unsigned int)L ? v : L; }
+
+__global__ __launch_bounds__(256) void confusion_hist_kernel(const int32_t* __restrict__ truth, const int32_t* __restrict__ preds,
+                                                             unsigned long long* __restrict__ counts, int64_t pixels, int L) {
+    extern __shared__ unsigned int conf_hist[];                 // [L + 1][L + 1]
+    const int side = L + 1, bins = side * side;
+    for (int i = threadIdx.x; i < bins; i += 256) conf_hist[i] = 0u;
+    __syncthreads();
+    const int32_t* q = preds + (int64_t)blockIdx.y * pixels;
+    const int lane = threadIdx.x & 63;
+    // the trip count is uniform over the workgroup, so every lane of a wave reaches label_hist_add together
+    for (int64_t i0 = (int64_t)blockIdx.x * ASR_CONFUSION_SPAN; i0 < pixels; i0 += (int64_t)gridDim.x * ASR_CONFUSION_SPAN) {
+        int key[kConfPerThread];
+#pragma unroll
+        for (int j = 0; j < kConfPerThread; ++j) {
+            const int64_t i = i0 + j * 256 + threadIdx.x;
+            const bool in = i < pixels;
+            const int tv = in ? truth[i] : 0, pv = in ? q[i] : 0;
+            key[j] = in ? conf_bin(tv, L) * side + conf_bin(pv, L) : -1;
+        }
+#pragma unroll
+        for (int j = 0; j < kConfPerThread; ++j) label_hist_add(conf_hist, key[j], lane);
+    }
+    __syncthreads();
+    unsigned long long* g = counts + (int64_t)blockIdx.y * bins;
+    for (int b = threadIdx.x; b < bins; b += 256)
+        if (conf_hist[b]) atomicAdd(g + b, (unsigned long long)conf_hist[b]);
+}
+
 // ---- last_activation: softmax / sigmoid over the class axis (model.py:124-125) ----------------------
 __device__ __forceinline__ void activate_row(const float* row, float* o, int classes, int kind) {     // o may be row
     if (kind == 1) {                       // softmax: exp(x - max) / sum
@@ -1041,6 +1079,30 @@ extern "C" int asr_band_class_counts_i32(const int32_t* truth, const int32_t* pr
     ASR_LAUNCH_CHECK();
     hipLaunchKernelGGL(band_finalize_kernel, dim3((unsigned)asr_cdiv((int64_t)num_preds * 768, 256)), dim3(256), 0, s,
                        reinterpret_cast<long long*>(counts), num_preds, set);
+    ASR_LAUNCH_CHECK();
+    return ASR_OK;
+}
+
+extern "C" int asr_confusion_counts_i32(const int32_t* truth, const int32_t* preds, int64_t* counts, int64_t pixels,
+                                        int num_preds, int num_labels, asr_stream_t stream) {
+    ASR_REQUIRE(truth && preds && counts, "asr_confusion_counts_i32: null pointer");
+    ASR_REQUIRE(pixels > 0 && pixels < ((int64_t)1 << 62), "asr_confusion_counts_i32: bad shape (pixels=%lld)", (long long)pixels);
+    ASR_REQUIRE(num_preds >= 1 && num_preds <= ASR_CONFUSION_MAX_PREDS, "asr_confusion_counts_i32: %d predictions (1..%d)",
+                num_preds, ASR_CONFUSION_MAX_PREDS);
+    ASR_REQUIRE(num_labels >= 1 && num_labels <= ASR_CONFUSION_MAX_LABELS, "asr_confusion_counts_i32: %d labels (1..%d)",
+                num_labels, ASR_CONFUSION_MAX_LABELS);
+    const size_t bins = (size_t)(num_labels + 1) * (size_t)(num_labels + 1);
+    // A workgroup's bins are 32-bit: it must see fewer than 2^32 pixels.  With G workgroups in a grid row it makes
+    // ceil(pixels / (G * span)) trips of span pixels, fewer than pixels / G + span; G >= pixels / 2^31 keeps that below
+    // 2^31 + span.  Up to 2^37 pixels ASR_CONFUSION_GRID workgroups do; below 2^62 pixels G fits a grid dimension.
+    int64_t grid = asr_cdiv(pixels, (int64_t)ASR_CONFUSION_SPAN);
+    grid = grid > ASR_CONFUSION_GRID ? ASR_CONFUSION_GRID : grid;
+    const int64_t need = asr_cdiv(pixels, (int64_t)1 << 31);
+    grid = grid < need ? need : grid;
+    hipStream_t s = asr_stream(stream);
+    ASR_HIP_CHECK(hipMemsetAsync(counts, 0, sizeof(int64_t) * bins * (size_t)num_preds, s));
+    hipLaunchKernelGGL(confusion_hist_kernel, dim3((unsigned)grid, num_preds), dim3(256), sizeof(unsigned int) * bins, s, truth,
+                       preds, reinterpret_cast<unsigned long long*>(counts), pixels, num_labels);
     ASR_LAUNCH_CHECK();
     return ASR_OK;
 }

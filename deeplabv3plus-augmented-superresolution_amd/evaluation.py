@@ -200,32 +200,42 @@ LABELMAP_CSV_COLUMNS = ("standard_iou", "aug_iou", "max_iou", "mean_iou")
 
 
 def gather_labelmap_records(local_indices, local_miou, local_counts, num_images, local_band_miou=None,
-                            local_band_counts=None, num_widths=0):
+                            local_band_counts=None, num_widths=0, local_confusion=None, confusion_labels=0):
     """The one collective of evaluate_labelmaps.  local_miou: [n_local, 4] per-image Mean_IOU (LABELMAP_KEYS order);
     local_counts: [n_local, 4, 3, 256] integer counts.  Returns on every rank (rows [num_images, 4] float64, NaN rows where
     no rank reported; summed counts [4, 3, 256] int64).  The counts travel as float64 in the same all-gather as the rows:
     exact below 2^53 pixels per bin.
 
     num_widths = B > 0: the trimap records ride in the same all-gather -- local_band_miou [n_local, 4, B], local_band_counts
-    [n_local, 4, B, 3, 256] -- and the result is (rows, counts, band_rows [num_images, 4, B], band_counts [4, B, 3, 256])."""
+    [n_local, 4, B, 3, 256] -- and the result is (rows, counts, band_rows [num_images, 4, B], band_counts [4, B, 3, 256]).
+
+    confusion_labels = L > 0: the confusion matrices ride in it too, as the counts do -- local_confusion [n_local, 4, L+1, L+1]
+    -- and the result ends in one more entry, the summed matrices [4, L+1, L+1] int64."""
     m = len(LABELMAP_KEYS)
     b = int(num_widths)
+    side = int(confusion_labels) + 1 if confusion_labels else 0
     n_local = len(local_indices)
     base = m + m * 768
-    width = base + m * b + m * b * 768
+    conf = base + m * b + m * b * 768
+    width = conf + m * side * side
     rec = np.empty((n_local, width), dtype=np.float64)
     if n_local:
         rec[:, :m] = np.asarray(local_miou, dtype=np.float64).reshape(n_local, m)
         rec[:, m:base] = np.asarray(local_counts, dtype=np.int64).reshape(n_local, m * 768)
         if b:
             rec[:, base:base + m * b] = np.asarray(local_band_miou, dtype=np.float64).reshape(n_local, m * b)
-            rec[:, base + m * b:] = np.asarray(local_band_counts, dtype=np.int64).reshape(n_local, m * b * 768)
+            rec[:, base + m * b:conf] = np.asarray(local_band_counts, dtype=np.int64).reshape(n_local, m * b * 768)
+        if side:
+            rec[:, conf:] = np.asarray(local_confusion, dtype=np.int64).reshape(n_local, m * side * side)
     table = D.all_gather_rows(local_indices, rec, num_images, width)
     counts = np.nan_to_num(table[:, m:base]).astype(np.int64).reshape(num_images, m, 3, 256)
-    if not b:
-        return table[:, :m], counts.sum(axis=0)
-    band_counts = np.nan_to_num(table[:, base + m * b:]).astype(np.int64).reshape(num_images, m, b, 3, 256)
-    return table[:, :m], counts.sum(axis=0), table[:, base:base + m * b].reshape(num_images, m, b), band_counts.sum(axis=0)
+    out = (table[:, :m], counts.sum(axis=0))
+    if b:
+        band_counts = np.nan_to_num(table[:, base + m * b:conf]).astype(np.int64).reshape(num_images, m, b, 3, 256)
+        out += (table[:, base:base + m * b].reshape(num_images, m, b), band_counts.sum(axis=0))
+    if side:
+        out += (np.nan_to_num(table[:, conf:]).astype(np.int64).reshape(num_images, m, side, side).sum(axis=0),)
+    return out
 
 
 def label_ious(counts):
@@ -243,7 +253,7 @@ def dataset_miou(counts):
 
 def evaluate_labelmaps(path, image_paths, gt_paths, class_ids=tuple(range(1, 21)), num_aug=100, angle_max=0.3, shift_max=30,
                        img_size=(512, 512), rank=0, world=1, seed=1234, sr_types=("aug", "max", "mean"), prune=True,
-                       save_dir=None, band_widths=None, band_ignore_label=255):
+                       save_dir=None, band_widths=None, band_ignore_label=255, confusion_labels=None):
     """One fused label map per image and SR type (HotPath.run_image_labels) and its score.  Returns (rows, counts) on every
     rank: rows [images, 4] per-image Mean_IOU in LABELMAP_KEYS order (the reference's per-image-then-mean convention; NaN for
     an SR type that was not asked for), counts [4, 3, 256] int64 summed over the images (dataset_miou, label_ious).
@@ -257,7 +267,12 @@ def evaluate_labelmaps(path, image_paths, gt_paths, class_ids=tuple(range(1, 21)
     band_widths (B integers in [1, 64]): the same loop also collects each label map's trimap counts (run_image_labels'
     band_widths / band_ignore_label) and the return value is (rows, counts, band_rows, band_counts): band_rows [images, 4, B]
     per-image Mean_IOU inside each band, band_counts [4, B, 3, 256] int64 summed over the images, both NaN / zero for a label
-    map that was not asked for.  They travel in the same all-gather."""
+    map that was not asked for.  They travel in the same all-gather.
+
+    confusion_labels (an integer L in [1, 64]): the same loop also collects each label map's confusion matrix against the
+    ground truth (run_image_labels' confusion_labels) and the return value ends in one more entry: the matrices [4, L+1, L+1]
+    int64 in LABELMAP_KEYS order, summed over the images (utils.metrics_from_confusion, write_confusion_csv), all zero for a
+    label map that was not asked for.  They travel in the same all-gather as well."""
     class_ids, params, mine = _class_set_run(class_ids, image_paths, gt_paths, rank, world, num_aug=num_aug,
                                              angle_max=angle_max, shift_max=shift_max, seed=seed)
     n_img = len(image_paths)
@@ -266,11 +281,14 @@ def evaluate_labelmaps(path, image_paths, gt_paths, class_ids=tuple(range(1, 21)
         os.makedirs(save_dir, exist_ok=True)
     bands = ops.check_band_widths(band_widths) if band_widths is not None else None
     n_b = len(bands) if bands else 0
-    mious, counts, band_mious, band_counts = [], [], [], []
+    n_conf = ops.check_confusion_labels(confusion_labels) if confusion_labels is not None else 0
+    mious, counts, band_mious, band_counts, confusion = [], [], [], [], []
     for g in mine:
         image, gt = _image_and_labels_on_device(image_paths[g], gt_paths[g], img_size)
         angles, shifts = params[g]
         extra = dict(band_widths=bands, band_ignore_label=band_ignore_label) if bands else {}
+        if n_conf:
+            extra["confusion_labels"] = n_conf
         res = path.run_image_labels(image, angles, shifts, class_ids, gt_dev=gt, sr_types=sr_types, prune=prune,
                                     adam_starts={c: int(starts[g, k]) for k, c in enumerate(class_ids)}, **extra)
         mious.append([res["Mean_IOU"].get(key, np.nan) for key in LABELMAP_KEYS])
@@ -278,6 +296,8 @@ def evaluate_labelmaps(path, image_paths, gt_paths, class_ids=tuple(range(1, 21)
         if bands:
             band_mious.append([res["band_Mean_IOU"].get(key, np.full(n_b, np.nan)) for key in LABELMAP_KEYS])
             band_counts.append([res["band_counts"].get(key, np.zeros((n_b, 3, 256), np.int64)) for key in LABELMAP_KEYS])
+        if n_conf:
+            confusion.append([res["confusion"].get(key, np.zeros((n_conf + 1, n_conf + 1), np.int64)) for key in LABELMAP_KEYS])
         if save_dir:
             from PIL import Image
             stem = os.path.splitext(os.path.basename(image_paths[g]))[0]
@@ -285,9 +305,8 @@ def evaluate_labelmaps(path, image_paths, gt_paths, class_ids=tuple(range(1, 21)
                 if key in res:
                     Image.fromarray(res[key].cpu().numpy().astype(np.uint8), mode="L").save(
                         os.path.join(save_dir, f"{stem}_{key}.png"))
-    if not bands:
-        return gather_labelmap_records(mine, mious, counts, n_img)
-    return gather_labelmap_records(mine, mious, counts, n_img, band_mious, band_counts, n_b)
+    return gather_labelmap_records(mine, mious, counts, n_img, band_mious if bands else None, band_counts if bands else None,
+                                   n_b, confusion if n_conf else None, n_conf)
 
 
 def write_labelmap_csv(path, counts, rows):
@@ -344,6 +363,75 @@ def write_trimap_csv(path, widths, band_counts, band_rows, counts=None, ignore_l
             pixels = int(band_counts[:, b, 0].max(axis=0).sum())
             share = repr(pixels / total) if total else "nan"
             wr.writerow([f"w={width}"] + cells + [str(pixels), share, str(len(band_rows))])
+
+
+CONFUSION_CSV_COLUMNS = ("key", "truth", "predicted", "pixels", "share_of_truth")
+CONFUSION_METRICS_CSV_COLUMNS = ("key", "other", "metric", "label", "value")
+CONFUSION_SCALARS = ("pixel_accuracy", "mean_accuracy", "Mean_IOU", "fw_iou")
+CONFUSION_PER_LABEL = ("precision", "recall", "iou")
+
+
+def _confusion_by_key(matrices):
+    """{key: [L+1, L+1] int64} in LABELMAP_KEYS order from such a dict or from an array [4, L+1, L+1] in that order; a label map
+    that was not produced (an all-zero matrix) is left out."""
+    if isinstance(matrices, dict):
+        items = [(key, matrices[key]) for key in LABELMAP_KEYS if key in matrices]
+    else:
+        items = list(zip(LABELMAP_KEYS, np.asarray(matrices)))
+    out = {key: np.asarray(m, dtype=np.int64) for key, m in items}
+    for key, m in out.items():
+        if m.ndim != 2 or m.shape[0] != m.shape[1] or m.shape[0] < 2:
+            raise ValueError(f"confusion matrix of {key}: expected [L+1, L+1], got {m.shape}")
+    return {key: m for key, m in out.items() if m.any()}
+
+
+def confusion_label_names(num_labels, class_names=None):
+    """The L + 1 names of a confusion matrix's bins: class_names (at least L of them) or "0".."L-1", then "other"."""
+    if class_names is None:
+        names = [str(l) for l in range(num_labels)]
+    else:
+        names = [str(n) for n in class_names][:num_labels]
+        if len(names) < num_labels:
+            raise ValueError(f"{len(names)} class names for {num_labels} labels")
+    return names + ["other"]
+
+
+def write_confusion_csv(path, matrices, class_names=None):
+    """The confusion matrices in long form: one row per (key, truth label, predicted label) with its pixels and its share of
+    the truth label's row (nan for a label the ground truths do not hold), for every label map that was produced.  matrices:
+    {key: int64 [L+1, L+1]} or an array [4, L+1, L+1] in LABELMAP_KEYS order (evaluate_labelmaps' last entry).  Labels are
+    named by class_names (L names) or by their number; bin L is "other".  The shares of a row that holds pixels sum to 1."""
+    import csv
+    with open(path, "w", newline="") as fh:
+        wr = csv.writer(fh, quoting=csv.QUOTE_ALL, lineterminator="\n")
+        wr.writerow(CONFUSION_CSV_COLUMNS)
+        for key, m in _confusion_by_key(matrices).items():
+            names = confusion_label_names(m.shape[0] - 1, class_names)
+            rows = m.sum(axis=1)
+            for i, t in enumerate(names):
+                for j, p in enumerate(names):
+                    share = repr(float(np.float64(m[i, j]) / np.float64(rows[i]))) if rows[i] else "nan"
+                    wr.writerow([key, t, p, str(int(m[i, j])), share])
+
+
+def write_confusion_metrics_csv(path, matrices, class_names=None):
+    """utils.metrics_from_confusion of every produced label map under both conventions for the other bin, in long form: one
+    row per (key, other, metric, label, value); label is empty for pixel_accuracy, mean_accuracy, Mean_IOU and fw_iou and the
+    label's name for precision, recall and iou."""
+    import csv
+    from .utils import metrics_from_confusion
+    with open(path, "w", newline="") as fh:
+        wr = csv.writer(fh, quoting=csv.QUOTE_ALL, lineterminator="\n")
+        wr.writerow(CONFUSION_METRICS_CSV_COLUMNS)
+        for key, m in _confusion_by_key(matrices).items():
+            names = confusion_label_names(m.shape[0] - 1, class_names)
+            for other in ("ignore", "label"):
+                res = metrics_from_confusion(m, other=other)
+                for name in CONFUSION_SCALARS:
+                    wr.writerow([key, other, name, "", repr(float(res[name]))])
+                for name in CONFUSION_PER_LABEL:
+                    for l, v in enumerate(res[name]):
+                        wr.writerow([key, other, name, names[l], repr(float(v))])
 
 
 def valid_rows(table, valid=None):

@@ -288,6 +288,42 @@ def band_class_counts(truth, preds, dist2, widths, r_max, ignore_label=255, out=
     return out.view(p, len(ws), 3, 256)
 
 
+def check_confusion_labels(num_labels):
+    """num_labels of a confusion matrix as an int in [1, 64].  Host only; ValueError otherwise."""
+    try:
+        n = int(num_labels)
+        same = not isinstance(num_labels, (bool, str, bytes)) and float(num_labels) == float(n)
+    except (TypeError, ValueError):
+        raise ValueError(f"num_labels must be an integer, got {num_labels!r}") from None
+    if not same:
+        raise ValueError(f"num_labels must be an integer, got {num_labels!r}")
+    if not 1 <= n <= _lib.MAX_CONFUSION_LABELS:
+        raise ValueError(f"num_labels {n} (1..{_lib.MAX_CONFUSION_LABELS})")
+    return n
+
+
+def confusion_counts(truth, preds, num_labels, out=None):
+    """One int32 truth, P <= 8 int32 predictions [P, ...] of the same size -> int64 [P, L+1, L+1], L = num_labels in [1, 64]:
+    [p, i, j] = the pixels whose truth falls in bin i and whose prediction p falls in bin j, bin(v) = v for 0 <= v < L and L
+    ("other": void, negative values, ids >= L) otherwise (asr_confusion_counts_i32).  out: a contiguous int64 tensor of that
+    size to write into."""
+    n = check_confusion_labels(num_labels)
+    per = truth.numel()
+    p = preds.numel() // per if per else 0
+    if per == 0 or p * per != preds.numel():
+        raise AsrError("confusion_counts: truth / preds size mismatch")
+    if not 1 <= p <= _lib.MAX_CONFUSION_PREDS:
+        raise AsrError(f"confusion_counts: {p} predictions (1..{_lib.MAX_CONFUSION_PREDS})")
+    side = n + 1
+    if out is None:
+        out = torch.empty((p, side, side), dtype=torch.int64, device=truth.device)
+    elif out.numel() != p * side * side:
+        raise AsrError("confusion_counts: out size mismatch")
+    call("asr_confusion_counts_i32", ptr(truth, torch.int32), ptr(preds, torch.int32), ptr(out, torch.int64), per, p, n,
+         stream_ptr())
+    return out.view(p, side, side)
+
+
 def realign(y, trans_tf, rot_tf, out_hw, mode):
     """mode "max" | "mean" -> [B,H,W]; "both" -> (max, mean) from one pass over the copies."""
     if y.dim() != 4:

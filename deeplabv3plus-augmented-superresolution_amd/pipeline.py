@@ -291,7 +291,7 @@ class HotPath:
     # ---- label maps: the classes of an image fused into one label map per SR type, and its Mean_IOU -----------------------
     def run_image_labels(self, image_dev, angles, shifts, class_ids=range(1, 21), gt_dev=None, adam_starts=None,
                          sr_types=("aug", "max", "mean"), want_standard=True, prune=True, profile=None, keep_scores=False,
-                         band_widths=None, band_ignore_label=255):
+                         band_widths=None, band_ignore_label=255, confusion_labels=None):
         """One label map per SR type from one forward pass: stage 1 and the solves are run_image_classes's; stage 2 ends in the
         fusion kernel (ops.fuse_labels) instead of K thresholds.  class_ids: K <= 32 distinct ids, none 0 (the label of "no
         class").  At each pixel the label is the class whose single-class mask is set there and whose SR output is greatest
@@ -316,9 +316,17 @@ class HotPath:
         {key: int64 [B, 3, 256] numpy, what utils.trimap_counts gives for that label map} and "band_Mean_IOU" {key: float64
         [B]}, widths in the caller's order; band_ignore_label (-1 or None: none) is left out of every bin.  One distance
         launch on gt_dev, one band-count launch over all label maps, and the same single copy to the host as "counts".
-        With band_widths=None nothing else is launched and nothing else returned."""
+        With band_widths=None nothing else is launched and nothing else returned.
+
+        confusion_labels (with gt_dev; an integer L in [1, 64]): the result gains "confusion" {key: int64 [L+1, L+1] numpy, what
+        utils.confusion_matrix(gt, label map, L) gives: truth in the rows, bin L holding void and every other value outside
+        0..L-1}.  One launch over all label maps, after the band counts, and the same single copy to the host as "counts".
+        With confusion_labels=None nothing else is launched and nothing else returned."""
         ids = [int(c) for c in class_ids]
         bands = ops.check_band_widths(band_widths) if band_widths is not None else None
+        n_conf = ops.check_confusion_labels(confusion_labels) if confusion_labels is not None else 0
+        if n_conf and gt_dev is None:
+            raise ValueError("confusion_labels needs gt_dev: a confusion matrix is counted against a ground truth")
         if any(c == 0 for c in ids):
             raise ValueError(f"class id 0 is the fallback label, never a candidate: {ids}")
         unknown = [t for t in sr_types if t not in ("aug", "max", "mean")]
@@ -350,7 +358,7 @@ class HotPath:
         scores = {}
         with self._sr_stage_timed(profile):
             gt = self._gt_int32(gt_dev) if gt_dev is not None else None
-            tally = _LabelCounts(keys, len(bands) if bands else 0, image_dev.device) if gt is not None else None
+            tally = _LabelCounts(keys, len(bands) if bands else 0, image_dev.device, n_conf) if gt is not None else None
             if tally is not None and want_standard:
                 tally.counts[0] = ops.class_counts(gt, maps[0])[0]
             if kept:
@@ -373,6 +381,8 @@ class HotPath:
                 r_max = max(bands)
                 ops.band_class_counts(gt, maps, ops.boundary_dist2(gt.view(out_hw[0], out_hw[1]), r_max), bands, r_max,
                                       -1 if band_ignore_label is None else int(band_ignore_label), out=tally.band)
+            if n_conf:
+                ops.confusion_counts(gt, maps, n_conf, out=tally.confusion)
         res = {key: maps[j] for j, key in enumerate(keys)}
         res["solved_ids"] = solved
         if tally is not None:
@@ -412,14 +422,18 @@ class HotPath:
 
 class _LabelCounts:
     """The counts of run_image_labels on the device, one int64 allocation so that they reach the host in one copy: per label
-    map (in the order of keys) the [3, 256] whole-image counts, then, with B band widths, its [B, 3, 256] band counts."""
+    map (in the order of keys) the [3, 256] whole-image counts, then, with B band widths, its [B, 3, 256] band counts, then,
+    with L confusion labels, its [L+1, L+1] confusion matrix."""
 
-    def __init__(self, keys, n_bands, device):
-        self.keys, self.n_bands = keys, n_bands
+    def __init__(self, keys, n_bands, device, n_conf=0):
+        self.keys, self.n_bands, self.n_conf = keys, n_bands, n_conf
         self._split = len(keys) * 768
-        self._buf = torch.empty(self._split * (1 + n_bands), dtype=torch.int64, device=device)
+        self._conf = self._split * (1 + n_bands)
+        cells = (n_conf + 1) ** 2 if n_conf else 0
+        self._buf = torch.empty(self._conf + len(keys) * cells, dtype=torch.int64, device=device)
         self.counts = self._buf[:self._split].view(len(keys), 3, 256)
-        self.band = self._buf[self._split:]             # [len(keys), B, 3, 256], flat: ops.band_class_counts's out
+        self.band = self._buf[self._split:self._conf]   # [len(keys), B, 3, 256], flat: ops.band_class_counts's out
+        self.confusion = self._buf[self._conf:]         # [len(keys), L+1, L+1], flat: ops.confusion_counts's out
 
     def to_host(self):
         """The "counts" / "Mean_IOU" (and "band_counts" / "band_Mean_IOU") entries of the result."""
@@ -428,10 +442,13 @@ class _LabelCounts:
         res = {"counts": {key: counts[j] for j, key in enumerate(self.keys)},
                "Mean_IOU": {key: mean_iou_from_counts(counts[j]) for j, key in enumerate(self.keys)}}
         if self.n_bands:
-            band = host[self._split:].reshape(len(self.keys), self.n_bands, 3, 256)
+            band = host[self._split:self._conf].reshape(len(self.keys), self.n_bands, 3, 256)
             res["band_counts"] = {key: band[j] for j, key in enumerate(self.keys)}
             res["band_Mean_IOU"] = {key: np.array([mean_iou_from_counts(c) for c in band[j]], dtype=np.float64)
                                     for j, key in enumerate(self.keys)}
+        if self.n_conf:
+            conf = host[self._conf:].reshape(len(self.keys), self.n_conf + 1, self.n_conf + 1)
+            res["confusion"] = {key: conf[j] for j, key in enumerate(self.keys)}
         return res
 
 

@@ -162,6 +162,66 @@ def trimap_IoU(y_true, y_pred, widths, class_id=None, ignore_label=255, img_size
         return np.float64(counts[:, 2, l]) / np.float64(counts[:, 0, l] + counts[:, 1, l] - counts[:, 2, l])
 
 
+def confusion_matrix(y_true, y_pred, num_labels):
+    """The confusion matrix of one prediction against one ground truth (include/asr_hip.h, "confusion matrix"): a host int64
+    [L+1, L+1], L = num_labels in [1, 64], truth in the rows; [i, j] = the pixels whose truth falls in bin i and whose
+    prediction falls in bin j, where bin(v) = v for 0 <= v < L and L ("other": void, negative values, ids >= L) otherwise.
+    numpy arrays or tensors, on the host or the device, any shape with equal pixel counts."""
+    n = ops.check_confusion_labels(num_labels)
+    dev = _lib.require_gpu()
+    t = _as_label_tensor(y_true, dev)
+    p = _as_label_tensor(y_pred, dev)
+    if p.numel() != t.numel():
+        raise ValueError(f"expected {t.numel()} predicted pixels, got {p.numel()}")
+    return ops.confusion_counts(t, p, n)[0].cpu().numpy()
+
+
+def metrics_from_confusion(M, other="ignore"):
+    """The usual result table of a segmentation from one confusion matrix M [L+1, L+1] (truth in the rows, the last row and
+    column the "other" bin).  Pure numpy, float64.  With row_l, col_l the sums of row and column l and d_l = M[l, l]:
+
+      precision [L]     d_l / col_l                       NaN where the label is never predicted
+      recall [L]        d_l / row_l                       NaN where the truth does not hold the label
+      iou [L]           d_l / (row_l + col_l - d_l)       NaN where neither map holds the label
+      pixel_accuracy    the matrix's trace over its sum
+      mean_accuracy     the mean of recall over the labels the truth holds
+      Mean_IOU          the mean of iou over the labels the truth holds: NaN labels are dropped and, as Mean_IOU does, a label
+                        that is predicted but absent from the truth (iou 0) is not among them
+      fw_iou            sum of row_l * iou_l over the labels the truth holds, over the sum of their row_l
+    (NaN for a mean over no label).  The per-label arrays and the three means cover the L labels, never the other bin.
+
+    other="ignore": the other row and the other column are dropped before anything is computed -- the VOC protocol: a pixel
+    that is void in the truth (or predicted outside 0..L-1) is scored nowhere.
+    other="label": the other bin stays in the matrix as a label like any other: its pixels stay in the row sums, the column
+    sums, the trace and the total, so a void pixel predicted as l enters l's union.  That is how Mean_IOU treats void (255),
+    so when every value outside 0..L-1 that the truth holds is void, negative or above 255 (Mean_IOU never scores those as
+    a label) Mean_IOU here equals utils.mean_iou_from_counts(ops.class_counts(truth, pred)) exactly."""
+    m = np.asarray(M)
+    if m.ndim != 2 or m.shape[0] != m.shape[1] or m.shape[0] < 2:
+        raise ValueError(f"a confusion matrix is [L+1, L+1] with L >= 1, got shape {m.shape}")
+    if other not in ("ignore", "label"):
+        raise ValueError(f'other must be "ignore" or "label", got {other!r}')
+    m = m.astype(np.int64)
+    L = m.shape[0] - 1
+    if other == "ignore":
+        m = m[:L, :L]
+    rows, cols, diag = m.sum(axis=1)[:L], m.sum(axis=0)[:L], np.diagonal(m)[:L]
+    total, trace = int(m.sum()), int(np.trace(m))
+    f64 = lambda a: a.astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        precision = f64(diag) / f64(cols)
+        recall = f64(diag) / f64(rows)
+        iou = f64(diag) / f64(rows + cols - diag)
+        present = rows > 0
+        nan = float("nan")
+        return {"pixel_accuracy": float(np.float64(trace) / np.float64(total)) if total else nan,
+                "mean_accuracy": float(np.mean(recall[present])) if present.any() else nan,
+                "precision": precision, "recall": recall, "iou": iou,
+                "Mean_IOU": float(np.mean(iou[present])) if present.any() else nan,
+                "fw_iou": float(np.sum(f64(rows[present]) * iou[present]) / np.float64(rows[present].sum()))
+                if present.any() else nan}
+
+
 def compute_IoU(true_image, image, img_size=(512, 512), class_id=None, include_bg=False):
     """IoU of two label maps (utils.py:207-230): single class (optionally with background) when class_id is given,
     otherwise the multi-class Mean_IOU.  Void (255) pixels are NOT excluded from the single-class form, exactly

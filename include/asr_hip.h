@@ -349,6 +349,28 @@ int asr_band_class_counts_i32(const int32_t* truth, const int32_t* preds, const 
                               int64_t* counts, int64_t pixels, int num_preds, int num_widths, int r_max, int ignore_label,
                               asr_stream_t stream);
 
+/* --- confusion matrix: where the pixels of each ground-truth label go in a label map --------------------------------------
+ * Definitions (everything is integer):
+ *  - num_labels = L (1..64) labels 0..L-1 are told apart; bin(v) = v when 0 <= v < L, else L.  Bin L is OTHER: void (255),
+ *    negative values and every id >= L;
+ *  - the confusion matrix of a prediction P against a ground truth T is M [L+1, L+1] int64, truth in the rows:
+ *    M[i][j] = |{x : bin(T[x]) == i and bin(P[x]) == j}|.
+ * Hence M sums to pixels, and for l < L row sum l, column sum l and M[l][l] are asr_class_counts_i32's counts[0][l],
+ * counts[1][l] and counts[2][l], bit for bit.
+ *
+ * asr_confusion_counts_i32: num_preds (1..8) predictions [num_preds, pixels] against ONE truth [pixels] (shared as
+ * asr_band_class_counts_i32 shares its truth) -> counts [num_preds, L+1, L+1] int64, zeroed by the call.  A bad argument
+ * returns ASR_ERR_INVALID_ARG before any launch.  One launch: each prediction is a grid row that re-reads the truth
+ * (cache-fed); a workgroup of 256 threads takes ASR_CONFUSION_SPAN pixels per trip of its grid-stride loop, and a grid row
+ * has at most ASR_CONFUSION_GRID workgroups, or as many as keep a workgroup below 2^32 pixels.  (L+1)^2 * 4 bytes of LDS
+ * per workgroup: 1.9 KiB at L = 21, 16.5 KiB at L = 64. */
+#define ASR_CONFUSION_MAX_LABELS 64
+#define ASR_CONFUSION_MAX_PREDS 8
+#define ASR_CONFUSION_SPAN 1024
+#define ASR_CONFUSION_GRID 64
+int asr_confusion_counts_i32(const int32_t* truth, const int32_t* preds, int64_t* counts, int64_t pixels, int num_preds,
+                             int num_labels, asr_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * DeepLabV3+ (Xception-65, OS16) layers -- model.py.  BatchNorm is folded by the caller.
  * ------------------------------------------------------------------------------------------ */

@@ -13,7 +13,13 @@ process per GPU (torch.distributed.run) images are dealt round-robin over the ra
 
 --band_widths 1,2,4,8,16,32 --trimap_out trimap.csv: the trimap curve as well -- each label map scored only on the pixels within
 w pixels of a ground-truth label boundary (include/asr_hip.h, "trimap"), void (255) pixels left out, one CSV row per width
-(evaluation.write_trimap_csv).  Without these two flags nothing else is computed or written."""
+(evaluation.write_trimap_csv).  Without these two flags nothing else is computed or written.
+
+--confusion_out conf.csv [--confusion_labels 21] [--class_names FILE]: the confusion matrix of every label map against the ground
+truth, summed over the images, in long form (evaluation.write_confusion_csv: key, truth label, predicted label, pixels, share of
+the truth label's pixels; "other" holds void and every value outside 0..labels-1), and next to it <stem>_metrics.csv with pixel
+accuracy, mean class accuracy, mIoU, frequency-weighted IoU and per-label precision / recall / IoU, once with the other bin left
+out (the VOC protocol) and once with it kept as a label (Mean_IOU's convention).  FILE: one label name per line."""
 import argparse
 import os
 import sys
@@ -48,6 +54,9 @@ parser.add_argument("--save_dir", default=None, help="folder for the label maps 
 parser.add_argument("--band_widths", default=None,
                     help="comma-separated band widths in pixels (1..64, at most 16), e.g. 1,2,4,8,16,32: score the trimap too")
 parser.add_argument("--trimap_out", default=None, help="CSV file for the trimap (default: <--out stem>_trimap.csv)")
+parser.add_argument("--confusion_out", default=None, help="CSV file for the confusion matrices (not counted when omitted)")
+parser.add_argument("--confusion_labels", type=int, default=21, help="labels 0..N-1 of the confusion matrix (1..64)")
+parser.add_argument("--class_names", default=None, help="text file with one label name per line (default: the numbers)")
 parser.add_argument("--no_prune", action="store_true", help="solve every class, also those that win no pixel (same results)")
 
 
@@ -55,7 +64,8 @@ def main():
     args = parser.parse_args()
     import torch
     from asr_amd import distributed as D
-    from asr_amd.evaluation import LABELMAP_KEYS, dataset_miou, evaluate_labelmaps, write_labelmap_csv, write_trimap_csv
+    from asr_amd.evaluation import (LABELMAP_KEYS, dataset_miou, evaluate_labelmaps, write_confusion_csv,
+                                    write_confusion_metrics_csv, write_labelmap_csv, write_trimap_csv)
     from asr_amd.model import DeeplabV3Plus
     from asr_amd.pipeline import HotPath
     from asr_amd.superresolution_scripts.optimizer import Optimizer
@@ -65,6 +75,14 @@ def main():
     if args.trimap_out and not args.band_widths:
         parser.error("--trimap_out needs --band_widths")
     bands = [int(v) for v in args.band_widths.split(",")] if args.band_widths else None
+    if args.confusion_out and not 1 <= args.confusion_labels <= 64:
+        parser.error("--confusion_labels must lie in 1..64")
+    names = None
+    if args.class_names:
+        with open(args.class_names) as fh:
+            names = [line.strip() for line in fh if line.strip()]
+        if args.confusion_out and len(names) < args.confusion_labels:
+            parser.error(f"--class_names holds {len(names)} names for {args.confusion_labels} labels")
     rank, world, local_rank = D.init_from_env()
     torch.cuda.set_device(D.local_device(local_rank))
     paths = list_images(args.images, args.num_samples)
@@ -81,7 +99,8 @@ def main():
     path = HotPath(model, sr, mode=args.mode, th_factor=args.th_factor, batch_size=BATCH_SIZE)
     out = evaluate_labelmaps(path, paths, gts, class_ids, num_aug=args.num_aug, angle_max=args.angle_max,
                              shift_max=args.shift_max, img_size=IMG_SIZE, rank=rank, world=world, seed=SEED,
-                             prune=not args.no_prune, save_dir=args.save_dir, band_widths=bands)
+                             prune=not args.no_prune, save_dir=args.save_dir, band_widths=bands,
+                             confusion_labels=args.confusion_labels if args.confusion_out else None)
     rows, counts = out[:2]
     if rank == 0:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
@@ -94,6 +113,12 @@ def main():
             os.makedirs(os.path.dirname(os.path.abspath(trimap)), exist_ok=True)
             write_trimap_csv(trimap, bands, out[3], out[2], counts=counts)
             print(f"Wrote {trimap}")
+        if args.confusion_out:
+            metrics = os.path.splitext(os.path.abspath(args.confusion_out))[0] + "_metrics.csv"
+            os.makedirs(os.path.dirname(os.path.abspath(args.confusion_out)), exist_ok=True)
+            write_confusion_csv(args.confusion_out, out[-1], names)
+            write_confusion_metrics_csv(metrics, out[-1], names)
+            print(f"Wrote {args.confusion_out} and {metrics}")
     if world > 1:
         torch.distributed.barrier()
         torch.distributed.destroy_process_group()
