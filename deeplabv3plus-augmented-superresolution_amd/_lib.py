@@ -91,6 +91,8 @@ SIGNATURES = {
     "asr_iou_counts_classes_i32": (_i, [_vp, _vp, _vp, _i64, _i, _i, _ip, _i, _vp]),
     "asr_standard_mask_classes_i32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _ip, _i, _vp]),
     "asr_fuse_labels_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _fl, _ip, _i, _vp]),
+    "asr_fuse_labels_sweep_workspace_bytes": (_sz, [_i, _i]),
+    "asr_fuse_labels_sweep_counts_f32": (_i, [_vp, _vp, _vp, _vp, _sz, _vp, _i64, _i, _i, _ip, _i, _vp]),
     "asr_standard_labels_i32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _ip, _i, _vp]),
     "asr_class_counts_i32": (_i, [_vp, _vp, _vp, _i64, _i, _vp]),
     "asr_boundary_dist2_u16": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),

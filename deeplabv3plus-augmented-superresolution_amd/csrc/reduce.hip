@@ -520,6 +520,113 @@ __global__ __launch_bounds__(256) void fuse_labels_kernel(const float* __restric
     }
 }
 
+// ---- label fusion swept over T threshold factors: counts only (asr_fuse_labels_sweep_counts_f32) --------------------------
+// counts[j] is what fuse_labels_kernel<false, true> leaves at th_factor = factors[j]: the same f32 product max_k * factors[j],
+// the same strict comparisons in the same order of k.  A predicted label is 0 or one of the K ids, so a workgroup counts in SLOTS
+// (slot 0: label 0, slot k + 1: ids[k]) -- per factor a row of predicted and a row of agreeing pixels, K + 1 slots each, plus
+// one 256-bin truth histogram that every factor shares -- and the finalize kernel scatters the slots into [T, 3, 256].  A thread
+// keeps its pixel's K scores in its own column of an LDS tile (written and read by that thread alone: no barrier), loaded four
+// planes at a time, and walks the factors over it; the thresholds th[j][k] sit in LDS and are read as broadcasts.  lo[k] is
+// class k's lowest threshold over the factors: a wave none of whose pixels exceeds any lo[k] holds label 0 under every factor
+// and adds its T rows by popcount, one lane per factor.  Dynamic LDS: tile [K][256] f32, th [T][K] f32, lo [K] f32,
+// id [K + 1] i32, hist [T][2][K + 1] + [256] u32.  The trip count and T are uniform over the workgroup, so every lane reaches
+// the ballots and label_hist_add together.
+constexpr int kLabelSweepMaxFactors = 64;
+
+__host__ __device__ constexpr size_t label_sweep_slots(int K, int T) { return (size_t)T * 2 * (size_t)(K + 1) + 256; }
+
+__global__ __launch_bounds__(256) void fuse_labels_sweep_kernel(const float* __restrict__ scores, const float* __restrict__ seg_minmax,
+                                                                const float* __restrict__ factors,
+                                                                const int32_t* __restrict__ truth,
+                                                                unsigned long long* __restrict__ slots, int64_t pixels, int T,
+                                                                AsrClassSet set) {
+    extern __shared__ unsigned int sweep_lds[];
+    const int K = set.n, row = K + 1;
+    float* tile = reinterpret_cast<float*>(sweep_lds);          // [K][256]
+    float* th = tile + K * 256;                                 // [T][K]
+    float* lo = th + T * K;                                     // [K]
+    int* id = reinterpret_cast<int*>(lo + K);                   // [K + 1]
+    unsigned int* hist = reinterpret_cast<unsigned int*>(id + row);     // [T][2][K + 1], then the truth's [256]
+    unsigned int* thist = hist + T * 2 * row;
+    const int nslots = (int)label_sweep_slots(K, T);
+    for (int i = threadIdx.x; i < T * K; i += 256) th[i] = seg_minmax[(i % K) * 2 + 1] * factors[i / K];
+    for (int i = threadIdx.x; i < nslots; i += 256) hist[i] = 0u;
+    if ((int)threadIdx.x < row) {
+        int v = 0;
+        for (int k = 0; k < K; ++k) v = ((int)threadIdx.x == k + 1) ? set.id[k] : v;          // (no dynamic indexing of the argument)
+        id[threadIdx.x] = v;
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < K) {
+        float m = th[threadIdx.x];
+        for (int j = 1; j < T; ++j) m = fminf(m, th[j * K + threadIdx.x]);
+        lo[threadIdx.x] = m;
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    float* mine = tile + threadIdx.x;
+    for (int64_t i0 = (int64_t)blockIdx.x * 256; i0 < pixels; i0 += (int64_t)gridDim.x * 256) {
+        const int64_t i = i0 + threadIdx.x;
+        const bool in = i < pixels;
+        bool any = false;
+        for (int k0 = 0; k0 < K; k0 += 4) {
+            float s[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) s[j] = (in && k0 + j < K) ? scores[(int64_t)(k0 + j) * pixels + i] : 0.0f;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (k0 + j < K) {
+                    mine[(k0 + j) * 256] = s[j];
+                    any = any || (in && s[j] > lo[k0 + j]);
+                }
+            }
+        }
+        const int tv = in ? truth[i] : -1;
+        const bool t_ok = in && tv >= 0 && tv < 256;
+        label_hist_add(thist, t_ok ? tv : -1, lane);
+        if (__ballot(any) == 0ull) {                            // label 0 everywhere in the wave, whatever the factor
+            const unsigned int n_in = (unsigned int)__popcll(__ballot(in)), n_zero = (unsigned int)__popcll(__ballot(in && tv == 0));
+            if (lane < T) {
+                if (n_in) atomicAdd(hist + lane * 2 * row, n_in);
+                if (n_zero) atomicAdd(hist + lane * 2 * row + row, n_zero);
+            }
+            continue;
+        }
+        int t_slot = -1;                                        // the slot whose label the truth holds, if any
+        if (t_ok)
+            for (int q = 0; q < row; ++q) t_slot = (id[q] == tv) ? q : t_slot;
+        for (int j = 0; j < T; ++j) {
+            const float* tj = th + j * K;
+            float best = 0.0f;
+            int slot = 0;
+            for (int k = 0; k < K; ++k) {
+                const float s = mine[k * 256];
+                if (s > tj[k] && (slot == 0 || s > best)) { best = s; slot = k + 1; }
+            }
+            const bool p_ok = in && id[slot] < 256;
+            unsigned int* h = hist + j * 2 * row;
+            label_hist_add(h, p_ok ? slot : -1, lane);
+            label_hist_add(h + row, (p_ok && slot == t_slot) ? slot : -1, lane);
+        }
+    }
+    __syncthreads();
+    for (int b = threadIdx.x; b < nslots; b += 256)
+        if (hist[b]) atomicAdd(slots + b, (unsigned long long)hist[b]);
+}
+
+// one workgroup per factor, one thread per label: row 0 is the truth histogram, rows 1 and 2 take the slot of their label
+__global__ __launch_bounds__(256) void fuse_labels_sweep_finalize_kernel(const unsigned long long* __restrict__ slots,
+                                                                         long long* __restrict__ counts, int T, AsrClassSet set) {
+    const int K = set.n, row = K + 1, j = blockIdx.x, l = threadIdx.x;
+    int slot = l == 0 ? 0 : -1;
+    for (int k = 0; k < K; ++k) slot = (set.id[k] == l) ? k + 1 : slot;
+    const unsigned long long* h = slots + (size_t)j * 2 * row;
+    long long* c = counts + (size_t)j * 768;
+    c[l] = (long long)slots[(size_t)T * 2 * row + l];
+    c[256 + l] = slot >= 0 ? (long long)h[slot] : 0;
+    c[512 + l] = slot >= 0 ? (long long)h[row + slot] : 0;
+}
+
 // ---- trimap: squared distance to the nearest ground-truth label boundary (asr_boundary_dist2_u16) --------------------------
 // A workgroup owns a 64-column x kDistRows-row output tile.  The strip it needs is the tile's rows +- r_max and the three
 // 64-column words x0 - 64 .. x0 + 127 (r_max <= 64).  Phase 1: a wave walks down a word column of the strip holding the pixel
@@ -952,6 +1059,48 @@ extern "C" int asr_fuse_labels_f32(const float* scores, const float* max_scores,
         if (truth) ASR_FUSE_LAUNCH(false, true); else ASR_FUSE_LAUNCH(false, false);
     }
 #undef ASR_FUSE_LAUNCH
+    ASR_LAUNCH_CHECK();
+    return ASR_OK;
+}
+
+extern "C" size_t asr_fuse_labels_sweep_workspace_bytes(int K, int num_factors) {
+    if (K <= 0 || num_factors <= 0) return 0;
+    return sizeof(unsigned long long) * label_sweep_slots(K, num_factors) + sizeof(float) * 2 * (size_t)K;
+}
+
+extern "C" int asr_fuse_labels_sweep_counts_f32(const float* scores, const int32_t* truth, const float* factors, void* workspace,
+                                                size_t workspace_bytes, int64_t* counts, int64_t pixels, int K, int num_factors,
+                                                const int* ids, int classes, asr_stream_t stream) {
+    AsrClassSet set;
+    int rc = asr_label_set("asr_fuse_labels_sweep_counts_f32", ids, K, classes, &set);
+    if (rc != ASR_OK) return rc;
+    ASR_REQUIRE(scores && truth && factors && workspace && counts, "asr_fuse_labels_sweep_counts_f32: null pointer");
+    ASR_REQUIRE(pixels > 0, "asr_fuse_labels_sweep_counts_f32: bad shape");
+    ASR_REQUIRE(num_factors >= 1 && num_factors <= kLabelSweepMaxFactors,
+                "asr_fuse_labels_sweep_counts_f32: %d threshold factors (1..%d)", num_factors, kLabelSweepMaxFactors);
+    ASR_REQUIRE(reinterpret_cast<uintptr_t>(workspace) % sizeof(unsigned long long) == 0,
+                "asr_fuse_labels_sweep_counts_f32: workspace not aligned to 8 bytes");
+    const size_t need = asr_fuse_labels_sweep_workspace_bytes(K, num_factors);
+    if (workspace_bytes < need) {
+        asr_set_error("asr_fuse_labels_sweep_counts_f32: workspace of %zu bytes, %zu needed", workspace_bytes, need);
+        return ASR_ERR_WORKSPACE;
+    }
+    hipStream_t s = asr_stream(stream);
+    auto* slots = reinterpret_cast<unsigned long long*>(workspace);
+    const size_t slot_bytes = sizeof(unsigned long long) * label_sweep_slots(K, num_factors);
+    float* minmax = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + slot_bytes);
+    rc = asr_minmax_f32(scores, minmax, pixels, K, stream);
+    if (rc != ASR_OK) return rc;
+    ASR_HIP_CHECK(hipMemsetAsync(slots, 0, slot_bytes, s));
+    // every workgroup flushes its own slots: at most two workgroups per compute unit's worth of them
+    const int grid = stream_grid(pixels) > 512 ? 512 : stream_grid(pixels);
+    const size_t lds = sizeof(float) * ((size_t)K * 256 + (size_t)num_factors * K + K) + sizeof(int) * (size_t)(K + 1) +
+                       sizeof(unsigned int) * label_sweep_slots(K, num_factors);
+    hipLaunchKernelGGL(fuse_labels_sweep_kernel, dim3(grid), dim3(256), lds, s, scores, minmax, factors, truth, slots, pixels,
+                       num_factors, set);
+    ASR_LAUNCH_CHECK();
+    hipLaunchKernelGGL(fuse_labels_sweep_finalize_kernel, dim3(num_factors), dim3(256), 0, s, slots,
+                       reinterpret_cast<long long*>(counts), num_factors, set);
     ASR_LAUNCH_CHECK();
     return ASR_OK;
 }

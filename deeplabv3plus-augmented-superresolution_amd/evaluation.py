@@ -200,7 +200,8 @@ LABELMAP_CSV_COLUMNS = ("standard_iou", "aug_iou", "max_iou", "mean_iou")
 
 
 def gather_labelmap_records(local_indices, local_miou, local_counts, num_images, local_band_miou=None,
-                            local_band_counts=None, num_widths=0, local_confusion=None, confusion_labels=0):
+                            local_band_counts=None, num_widths=0, local_confusion=None, confusion_labels=0,
+                            local_sweep_miou=None, local_sweep_counts=None, num_factors=0):
     """The one collective of evaluate_labelmaps.  local_miou: [n_local, 4] per-image Mean_IOU (LABELMAP_KEYS order);
     local_counts: [n_local, 4, 3, 256] integer counts.  Returns on every rank (rows [num_images, 4] float64, NaN rows where
     no rank reported; summed counts [4, 3, 256] int64).  The counts travel as float64 in the same all-gather as the rows:
@@ -210,14 +211,22 @@ def gather_labelmap_records(local_indices, local_miou, local_counts, num_images,
     [n_local, 4, B, 3, 256] -- and the result is (rows, counts, band_rows [num_images, 4, B], band_counts [4, B, 3, 256]).
 
     confusion_labels = L > 0: the confusion matrices ride in it too, as the counts do -- local_confusion [n_local, 4, L+1, L+1]
-    -- and the result ends in one more entry, the summed matrices [4, L+1, L+1] int64."""
+    -- and the result gains one more entry, the summed matrices [4, L+1, L+1] int64.
+
+    num_factors = T > 0: the threshold-sweep records of the three SR label maps (LABELMAP_KEYS[1:]) ride in it as well --
+    local_sweep_miou [n_local, 3, T], local_sweep_counts [n_local, 3, T, 3, 256] -- and the result ends in two more entries,
+    sweep_rows [num_images, 3, T] and the summed sweep_counts [3, T, 3, 256] int64.  The order of the result is
+    (rows, counts[, band_rows, band_counts][, confusion][, sweep_rows, sweep_counts])."""
     m = len(LABELMAP_KEYS)
     b = int(num_widths)
     side = int(confusion_labels) + 1 if confusion_labels else 0
+    t = int(num_factors)
+    ms = m - 1                                      # the SR label maps: the standard map does not depend on the factor
     n_local = len(local_indices)
     base = m + m * 768
     conf = base + m * b + m * b * 768
-    width = conf + m * side * side
+    sweep = conf + m * side * side
+    width = sweep + ms * t + ms * t * 768
     rec = np.empty((n_local, width), dtype=np.float64)
     if n_local:
         rec[:, :m] = np.asarray(local_miou, dtype=np.float64).reshape(n_local, m)
@@ -226,7 +235,10 @@ def gather_labelmap_records(local_indices, local_miou, local_counts, num_images,
             rec[:, base:base + m * b] = np.asarray(local_band_miou, dtype=np.float64).reshape(n_local, m * b)
             rec[:, base + m * b:conf] = np.asarray(local_band_counts, dtype=np.int64).reshape(n_local, m * b * 768)
         if side:
-            rec[:, conf:] = np.asarray(local_confusion, dtype=np.int64).reshape(n_local, m * side * side)
+            rec[:, conf:sweep] = np.asarray(local_confusion, dtype=np.int64).reshape(n_local, m * side * side)
+        if t:
+            rec[:, sweep:sweep + ms * t] = np.asarray(local_sweep_miou, dtype=np.float64).reshape(n_local, ms * t)
+            rec[:, sweep + ms * t:] = np.asarray(local_sweep_counts, dtype=np.int64).reshape(n_local, ms * t * 768)
     table = D.all_gather_rows(local_indices, rec, num_images, width)
     counts = np.nan_to_num(table[:, m:base]).astype(np.int64).reshape(num_images, m, 3, 256)
     out = (table[:, :m], counts.sum(axis=0))
@@ -234,7 +246,10 @@ def gather_labelmap_records(local_indices, local_miou, local_counts, num_images,
         band_counts = np.nan_to_num(table[:, base + m * b:conf]).astype(np.int64).reshape(num_images, m, b, 3, 256)
         out += (table[:, base:base + m * b].reshape(num_images, m, b), band_counts.sum(axis=0))
     if side:
-        out += (np.nan_to_num(table[:, conf:]).astype(np.int64).reshape(num_images, m, side, side).sum(axis=0),)
+        out += (np.nan_to_num(table[:, conf:sweep]).astype(np.int64).reshape(num_images, m, side, side).sum(axis=0),)
+    if t:
+        sweep_counts = np.nan_to_num(table[:, sweep + ms * t:]).astype(np.int64).reshape(num_images, ms, t, 3, 256)
+        out += (table[:, sweep:sweep + ms * t].reshape(num_images, ms, t), sweep_counts.sum(axis=0))
     return out
 
 
@@ -253,7 +268,7 @@ def dataset_miou(counts):
 
 def evaluate_labelmaps(path, image_paths, gt_paths, class_ids=tuple(range(1, 21)), num_aug=100, angle_max=0.3, shift_max=30,
                        img_size=(512, 512), rank=0, world=1, seed=1234, sr_types=("aug", "max", "mean"), prune=True,
-                       save_dir=None, band_widths=None, band_ignore_label=255, confusion_labels=None):
+                       save_dir=None, band_widths=None, band_ignore_label=255, confusion_labels=None, th_factors=None):
     """One fused label map per image and SR type (HotPath.run_image_labels) and its score.  Returns (rows, counts) on every
     rank: rows [images, 4] per-image Mean_IOU in LABELMAP_KEYS order (the reference's per-image-then-mean convention; NaN for
     an SR type that was not asked for), counts [4, 3, 256] int64 summed over the images (dataset_miou, label_ious).
@@ -270,9 +285,16 @@ def evaluate_labelmaps(path, image_paths, gt_paths, class_ids=tuple(range(1, 21)
     map that was not asked for.  They travel in the same all-gather.
 
     confusion_labels (an integer L in [1, 64]): the same loop also collects each label map's confusion matrix against the
-    ground truth (run_image_labels' confusion_labels) and the return value ends in one more entry: the matrices [4, L+1, L+1]
+    ground truth (run_image_labels' confusion_labels) and the return value gains one more entry: the matrices [4, L+1, L+1]
     int64 in LABELMAP_KEYS order, summed over the images (utils.metrics_from_confusion, write_confusion_csv), all zero for a
-    label map that was not asked for.  They travel in the same all-gather as well."""
+    label map that was not asked for.  They travel in the same all-gather as well.
+
+    th_factors (T threshold factors, 1..64; not in slice_max mode): the same loop also collects the counts of every SR label
+    map under every factor (run_image_labels' th_factors: one more pass over the SR outputs it already holds, no further
+    forward pass or solve) and the return value ends in two more entries: sweep_rows [images, 3, T] per-image Mean_IOU and
+    sweep_counts [3, T, 3, 256] int64 summed over the images, both in the order aug / max / mean and NaN / zero for an SR
+    type that was not asked for (write_labelmap_threshold_csv).  They travel in the same all-gather.  The whole return value is
+    (rows, counts[, band_rows, band_counts][, confusion][, sweep_rows, sweep_counts])."""
     class_ids, params, mine = _class_set_run(class_ids, image_paths, gt_paths, rank, world, num_aug=num_aug,
                                              angle_max=angle_max, shift_max=shift_max, seed=seed)
     n_img = len(image_paths)
@@ -282,13 +304,19 @@ def evaluate_labelmaps(path, image_paths, gt_paths, class_ids=tuple(range(1, 21)
     bands = ops.check_band_widths(band_widths) if band_widths is not None else None
     n_b = len(bands) if bands else 0
     n_conf = ops.check_confusion_labels(confusion_labels) if confusion_labels is not None else 0
-    mious, counts, band_mious, band_counts, confusion = [], [], [], [], []
+    factors = None if th_factors is None else [float(f) for f in np.asarray(th_factors, dtype=np.float64).reshape(-1)]
+    n_t = len(factors) if factors is not None else 0
+    if factors is not None and not 1 <= n_t <= ops.MAX_LABEL_SWEEP_FACTORS:
+        raise ValueError(f"{n_t} threshold factors (1..{ops.MAX_LABEL_SWEEP_FACTORS})")
+    mious, counts, band_mious, band_counts, confusion, sweep_mious, sweep_counts = [], [], [], [], [], [], []
     for g in mine:
         image, gt = _image_and_labels_on_device(image_paths[g], gt_paths[g], img_size)
         angles, shifts = params[g]
         extra = dict(band_widths=bands, band_ignore_label=band_ignore_label) if bands else {}
         if n_conf:
             extra["confusion_labels"] = n_conf
+        if n_t:
+            extra["th_factors"] = factors
         res = path.run_image_labels(image, angles, shifts, class_ids, gt_dev=gt, sr_types=sr_types, prune=prune,
                                     adam_starts={c: int(starts[g, k]) for k, c in enumerate(class_ids)}, **extra)
         mious.append([res["Mean_IOU"].get(key, np.nan) for key in LABELMAP_KEYS])
@@ -298,6 +326,9 @@ def evaluate_labelmaps(path, image_paths, gt_paths, class_ids=tuple(range(1, 21)
             band_counts.append([res["band_counts"].get(key, np.zeros((n_b, 3, 256), np.int64)) for key in LABELMAP_KEYS])
         if n_conf:
             confusion.append([res["confusion"].get(key, np.zeros((n_conf + 1, n_conf + 1), np.int64)) for key in LABELMAP_KEYS])
+        if n_t:
+            sweep_mious.append([res["sweep_Mean_IOU"].get(key, np.full(n_t, np.nan)) for key in LABELMAP_KEYS[1:]])
+            sweep_counts.append([res["sweep_counts"].get(key, np.zeros((n_t, 3, 256), np.int64)) for key in LABELMAP_KEYS[1:]])
         if save_dir:
             from PIL import Image
             stem = os.path.splitext(os.path.basename(image_paths[g]))[0]
@@ -306,7 +337,8 @@ def evaluate_labelmaps(path, image_paths, gt_paths, class_ids=tuple(range(1, 21)
                     Image.fromarray(res[key].cpu().numpy().astype(np.uint8), mode="L").save(
                         os.path.join(save_dir, f"{stem}_{key}.png"))
     return gather_labelmap_records(mine, mious, counts, n_img, band_mious if bands else None, band_counts if bands else None,
-                                   n_b, confusion if n_conf else None, n_conf)
+                                   n_b, confusion if n_conf else None, n_conf, sweep_mious if n_t else None,
+                                   sweep_counts if n_t else None, n_t)
 
 
 def write_labelmap_csv(path, counts, rows):
@@ -327,6 +359,55 @@ def write_labelmap_csv(path, counts, rows):
         wr.writerow(["dataset_mIoU"] + [repr(dataset_miou(counts[j])) for j in range(len(LABELMAP_KEYS))] + [str(len(rows))])
         wr.writerow(["mean_image_mIoU"] + [repr(float(np.mean(rows[:, j]))) if len(rows) else "nan"
                                            for j in range(len(LABELMAP_KEYS))] + [str(len(rows))])
+
+
+THRESHOLD_CSV_COLUMNS = ("th_factor",) + tuple(f"{key}_{kind}" for key in LABELMAP_KEYS[1:] + LABELMAP_KEYS[:1]
+                                                for kind in ("dataset_mIoU", "mean_image_mIoU"))
+
+
+def write_labelmap_threshold_csv(path, factors, sweep_counts, sweep_rows, counts, rows):
+    """The threshold curve of the label maps, one row per factor in the caller's order: "th_factor", then for aug / max / mean
+    "<key>_dataset_mIoU" (dataset_miou of sweep_counts [3, T, 3, 256], the counts summed over the images) and
+    "<key>_mean_image_mIoU" (np.mean of the per-image Mean_IOU, sweep_rows [images, 3, T]; a NaN image propagates), then the
+    same two columns of the standard label map, which does not depend on the factor: constants taken from counts [4, 3, 256]
+    and rows [images, 4], what write_labelmap_csv takes.  The columns of a label map that was not produced (all-zero counts)
+    are nan.  Quoting and repr floats as write_labelmap_csv."""
+    import csv
+    fs = [float(f) for f in np.asarray(factors, dtype=np.float64).reshape(-1)]
+    ms = len(LABELMAP_KEYS) - 1
+    sweep_counts = np.asarray(sweep_counts, dtype=np.int64).reshape(ms, len(fs), 3, 256)
+    sweep_rows = np.asarray(sweep_rows, dtype=np.float64).reshape(-1, ms, len(fs))
+    counts = np.asarray(counts, dtype=np.int64).reshape(len(LABELMAP_KEYS), 3, 256)
+    rows = np.asarray(rows, dtype=np.float64).reshape(-1, len(LABELMAP_KEYS))
+    standard = ["nan", "nan"]
+    if counts[0].any():
+        standard = [repr(dataset_miou(counts[0])), repr(float(np.mean(rows[:, 0]))) if len(rows) else "nan"]
+    with open(path, "w", newline="") as fh:
+        wr = csv.writer(fh, quoting=csv.QUOTE_ALL, lineterminator="\n")
+        wr.writerow(THRESHOLD_CSV_COLUMNS)
+        for j, f in enumerate(fs):
+            cells = []
+            for i in range(ms):
+                made = bool(sweep_counts[i].any())          # an SR type that was not asked for carries all-zero counts
+                cells.append(repr(dataset_miou(sweep_counts[i, j])) if made else "nan")
+                cells.append(repr(float(np.mean(sweep_rows[:, i, j]))) if made and len(sweep_rows) else "nan")
+            wr.writerow([repr(f)] + cells + standard)
+
+
+def best_threshold_factors(factors, sweep_counts):
+    """{key: (factor, dataset mIoU)} for aug / max / mean: the factor of the greatest dataset mIoU (the first on equal values);
+    an SR type that was not produced, or whose mIoU is NaN under every factor, is left out."""
+    fs = [float(f) for f in np.asarray(factors, dtype=np.float64).reshape(-1)]
+    sweep_counts = np.asarray(sweep_counts, dtype=np.int64).reshape(len(LABELMAP_KEYS) - 1, len(fs), 3, 256)
+    best = {}
+    for i, key in enumerate(LABELMAP_KEYS[1:]):
+        if not sweep_counts[i].any():
+            continue
+        curve = np.array([dataset_miou(c) for c in sweep_counts[i]], dtype=np.float64)
+        if not np.all(np.isnan(curve)):
+            j = int(np.nanargmax(curve))
+            best[key] = (fs[j], float(curve[j]))
+    return best
 
 
 TRIMAP_CSV_COLUMNS = tuple(f"{key}_{kind}" for key in LABELMAP_KEYS for kind in ("band_mIoU", "band_mean_image_mIoU"))
@@ -399,7 +480,7 @@ def confusion_label_names(num_labels, class_names=None):
 def write_confusion_csv(path, matrices, class_names=None):
     """The confusion matrices in long form: one row per (key, truth label, predicted label) with its pixels and its share of
     the truth label's row (nan for a label the ground truths do not hold), for every label map that was produced.  matrices:
-    {key: int64 [L+1, L+1]} or an array [4, L+1, L+1] in LABELMAP_KEYS order (evaluate_labelmaps' last entry).  Labels are
+    {key: int64 [L+1, L+1]} or an array [4, L+1, L+1] in LABELMAP_KEYS order (evaluate_labelmaps' confusion entry).  Labels are
     named by class_names (L names) or by their number; bin L is "other".  The shares of a row that holds pixels sum to 1."""
     import csv
     with open(path, "w", newline="") as fh:

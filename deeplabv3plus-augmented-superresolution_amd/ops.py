@@ -592,6 +592,41 @@ def fuse_labels(scores, class_ids, th_factor=0.15, max_scores=None, truth=None, 
     return out, counts
 
 
+MAX_LABEL_SWEEP_FACTORS = 64
+
+
+def fuse_labels_sweep_counts(scores, class_ids, truth, factors, classes=0, out=None):
+    """scores [K, ...] float32, truth int32 label map, factors: T threshold factors (1..64, any order, repeats allowed; a host
+    sequence or a float32 device tensor) ->
+    device int64 [T, 3, 256]: counts[j] = fuse_labels(scores, class_ids, th_factor=factors[j], truth=truth, classes=classes)[1]
+    bit for bit, from one pass over the planes for all factors and without writing a label map
+    (asr_fuse_labels_sweep_counts_f32).  There is no max_scores form: the threshold plays no part there.  out: int64 with
+    T * 768 elements."""
+    ids, k = class_set(class_ids)
+    if scores.dim() < 2 or scores.shape[0] != k:
+        raise AsrError(f"fuse_labels_sweep_counts: scores must have one plane per class ({k}), got {tuple(scores.shape)}")
+    per = scores.numel() // k
+    if truth is None or truth.numel() != per:
+        raise AsrError(f"fuse_labels_sweep_counts: truth has {0 if truth is None else truth.numel()} pixels, expected {per}")
+    if isinstance(factors, torch.Tensor):           # already on the device: one upload serves several calls
+        f = factors.to(device=scores.device, dtype=f32).contiguous().reshape(-1)
+    else:
+        f = to_device(np.asarray(factors, dtype=np.float32).reshape(-1), device=scores.device)
+    t = f.numel()
+    if not 1 <= t <= MAX_LABEL_SWEEP_FACTORS:
+        raise AsrError(f"fuse_labels_sweep_counts: {t} threshold factors (1..{MAX_LABEL_SWEEP_FACTORS})")
+    if out is None:
+        out = torch.empty((t, 3, 256), dtype=torch.int64, device=scores.device)
+    elif out.numel() != t * 768:
+        raise AsrError("fuse_labels_sweep_counts: out size mismatch")
+    lib = _lib.load()
+    ws_bytes = lib.asr_fuse_labels_sweep_workspace_bytes(k, t)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=scores.device)
+    call("asr_fuse_labels_sweep_counts_f32", ptr(scores), ptr(truth, torch.int32), ptr(f), ptr(ws, torch.uint8), ws_bytes,
+         ptr(out, torch.int64), per, k, t, ids, int(classes), stream_ptr())
+    return out.view(t, 3, 256)
+
+
 def standard_labels(logits0, out_hw, class_ids, out=None):
     """logits0 [h,w,C] -> int32 label map [H,W]: the upsampled argmax where it is one of class_ids, else 0 -- the sum of
     standard_mask_classes' K masks (asr_standard_labels_i32)."""

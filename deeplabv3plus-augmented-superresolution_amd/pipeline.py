@@ -291,7 +291,7 @@ class HotPath:
     # ---- label maps: the classes of an image fused into one label map per SR type, and its Mean_IOU -----------------------
     def run_image_labels(self, image_dev, angles, shifts, class_ids=range(1, 21), gt_dev=None, adam_starts=None,
                          sr_types=("aug", "max", "mean"), want_standard=True, prune=True, profile=None, keep_scores=False,
-                         band_widths=None, band_ignore_label=255, confusion_labels=None):
+                         band_widths=None, band_ignore_label=255, confusion_labels=None, th_factors=None):
         """One label map per SR type from one forward pass: stage 1 and the solves are run_image_classes's; stage 2 ends in the
         fusion kernel (ops.fuse_labels) instead of K thresholds.  class_ids: K <= 32 distinct ids, none 0 (the label of "no
         class").  At each pixel the label is the class whose single-class mask is set there and whose SR output is greatest
@@ -321,8 +321,18 @@ class HotPath:
         confusion_labels (with gt_dev; an integer L in [1, 64]): the result gains "confusion" {key: int64 [L+1, L+1] numpy, what
         utils.confusion_matrix(gt, label map, L) gives: truth in the rows, bin L holding void and every other value outside
         0..L-1}.  One launch over all label maps, after the band counts, and the same single copy to the host as "counts".
-        With confusion_labels=None nothing else is launched and nothing else returned."""
+        With confusion_labels=None nothing else is launched and nothing else returned.
+
+        th_factors (with gt_dev; 1..64 threshold factors, any order; not in slice_max mode, where the threshold plays no part):
+        the threshold curve of the label maps.  th_factor is read by the fusion alone, so the SR outputs of this one run hold
+        every factor's label map: the result gains "sweep_counts" {t: int64 [T, 3, 256] numpy, row j the "counts" a
+        HotPath(th_factor=th_factors[j]) gives for SR type t} and "sweep_Mean_IOU" {t: float64 [T]}, keyed by the SR types asked
+        for (the standard map does not depend on the factor).  One sweep call per SR type (ops.fuse_labels_sweep_counts) right
+        after its fusion, on the same score tensors, and the same single copy to the host as "counts"; with no class left
+        after pruning every factor's counts are the zero map's.  With th_factors=None nothing else is launched and nothing
+        else returned."""
         ids = [int(c) for c in class_ids]
+        factors = self._check_th_factors(th_factors, gt_dev) if th_factors is not None else None
         bands = ops.check_band_widths(band_widths) if band_widths is not None else None
         n_conf = ops.check_confusion_labels(confusion_labels) if confusion_labels is not None else 0
         if n_conf and gt_dev is None:
@@ -358,7 +368,11 @@ class HotPath:
         scores = {}
         with self._sr_stage_timed(profile):
             gt = self._gt_int32(gt_dev) if gt_dev is not None else None
-            tally = _LabelCounts(keys, len(bands) if bands else 0, image_dev.device, n_conf) if gt is not None else None
+            tally = None
+            if gt is not None:
+                tally = _LabelCounts(keys, len(bands) if bands else 0, image_dev.device, n_conf,
+                                     sr_types if factors is not None else (), len(factors) if factors is not None else 0)
+            f_dev = ops.to_device(factors, device=image_dev.device) if factors is not None and kept and sr_types else None
             if tally is not None and want_standard:
                 tally.counts[0] = ops.class_counts(gt, maps[0])[0]
             if kept:
@@ -369,6 +383,8 @@ class HotPath:
                                            classes=classes)
                     if c is not None:
                         tally.counts[j] = c
+                    if f_dev is not None:
+                        ops.fuse_labels_sweep_counts(tgt, solved, gt, f_dev, classes=classes, out=tally.sweep[sr_types.index(t)])
                     if keep_scores:
                         scores[t] = (tgt, tmax)
             elif sr_types:
@@ -376,6 +392,8 @@ class HotPath:
                 maps[first:].zero_()
                 if gt is not None:
                     tally.counts[first:] = ops.class_counts(gt, maps[first])[0]          # one count serves every (equal) zero map
+                    if factors is not None:
+                        tally.sweep[:] = tally.counts[first]                             # ... under every factor
             self._advance_past(starts, adam_starts, sr_types)
             if bands is not None and gt is not None:
                 r_max = max(bands)
@@ -390,6 +408,18 @@ class HotPath:
         if keep_scores:
             res["scores"] = scores
         return res
+
+    def _check_th_factors(self, th_factors, gt_dev):
+        """The factors of a label-map threshold sweep as a float32 array (1..ops.MAX_LABEL_SWEEP_FACTORS of them)."""
+        if gt_dev is None:
+            raise ValueError("th_factors needs gt_dev: the sweep counts every factor's label map against a ground truth")
+        if self.mode == "slice_max":
+            raise ValueError("th_factors in slice_max mode: a class passes against its max map there, the threshold plays no "
+                             "part, so there is nothing to sweep")
+        f = np.asarray(th_factors, dtype=np.float32).reshape(-1)
+        if not 1 <= f.size <= ops.MAX_LABEL_SWEEP_FACTORS:
+            raise ValueError(f"{f.size} threshold factors (1..{ops.MAX_LABEL_SWEEP_FACTORS})")
+        return f
 
     def _finish(self, res):
         res.pop("_masks", None)          # the rows stay alive through the per-key views
@@ -423,17 +453,21 @@ class HotPath:
 class _LabelCounts:
     """The counts of run_image_labels on the device, one int64 allocation so that they reach the host in one copy: per label
     map (in the order of keys) the [3, 256] whole-image counts, then, with B band widths, its [B, 3, 256] band counts, then,
-    with L confusion labels, its [L+1, L+1] confusion matrix."""
+    with L confusion labels, its [L+1, L+1] confusion matrix; last, with T threshold factors, the [T, 3, 256] sweep counts of
+    each SR type in sweep_keys."""
 
-    def __init__(self, keys, n_bands, device, n_conf=0):
+    def __init__(self, keys, n_bands, device, n_conf=0, sweep_keys=(), n_factors=0):
         self.keys, self.n_bands, self.n_conf = keys, n_bands, n_conf
+        self.sweep_keys, self.n_factors = list(sweep_keys), n_factors
         self._split = len(keys) * 768
         self._conf = self._split * (1 + n_bands)
         cells = (n_conf + 1) ** 2 if n_conf else 0
-        self._buf = torch.empty(self._conf + len(keys) * cells, dtype=torch.int64, device=device)
+        self._sweep = self._conf + len(keys) * cells
+        self._buf = torch.empty(self._sweep + len(self.sweep_keys) * n_factors * 768, dtype=torch.int64, device=device)
         self.counts = self._buf[:self._split].view(len(keys), 3, 256)
         self.band = self._buf[self._split:self._conf]   # [len(keys), B, 3, 256], flat: ops.band_class_counts's out
-        self.confusion = self._buf[self._conf:]         # [len(keys), L+1, L+1], flat: ops.confusion_counts's out
+        self.confusion = self._buf[self._conf:self._sweep]      # [len(keys), L+1, L+1], flat: ops.confusion_counts's out
+        self.sweep = self._buf[self._sweep:].view(len(self.sweep_keys), n_factors, 3, 256)      # row i: ops.fuse_labels_sweep_counts's out
 
     def to_host(self):
         """The "counts" / "Mean_IOU" (and "band_counts" / "band_Mean_IOU") entries of the result."""
@@ -447,8 +481,13 @@ class _LabelCounts:
             res["band_Mean_IOU"] = {key: np.array([mean_iou_from_counts(c) for c in band[j]], dtype=np.float64)
                                     for j, key in enumerate(self.keys)}
         if self.n_conf:
-            conf = host[self._conf:].reshape(len(self.keys), self.n_conf + 1, self.n_conf + 1)
+            conf = host[self._conf:self._sweep].reshape(len(self.keys), self.n_conf + 1, self.n_conf + 1)
             res["confusion"] = {key: conf[j] for j, key in enumerate(self.keys)}
+        if self.n_factors:
+            sweep = host[self._sweep:].reshape(len(self.sweep_keys), self.n_factors, 3, 256)
+            res["sweep_counts"] = {t: sweep[i] for i, t in enumerate(self.sweep_keys)}
+            res["sweep_Mean_IOU"] = {t: np.array([mean_iou_from_counts(c) for c in sweep[i]], dtype=np.float64)
+                                     for i, t in enumerate(self.sweep_keys)}
         return res
 
 

@@ -116,6 +116,24 @@ def Mean_IOU(y_true, y_pred):
     return mean_iou_from_counts(counts)
 
 
+def labelmap_threshold_sweep(scores, class_ids, y_true, th_factors):
+    """The per-label counts of the fused label map at every threshold factor (include/asr_hip.h,
+    asr_fuse_labels_sweep_counts_f32): host int64 [T, 3, 256], row j what ops.fuse_labels(scores, class_ids,
+    th_factor=th_factors[j], truth=y_true) counts.  scores [K, ...] float32, numpy or tensor: plane k is the SR output of
+    class_ids[k]; y_true: a label map of as many pixels; th_factors: 1..64 factors, any order."""
+    dev = _lib.require_gpu()
+    s = scores.to(device=dev, dtype=torch.float32).contiguous() if isinstance(scores, torch.Tensor) \
+        else ops.to_device(np.asarray(scores, dtype=np.float32), device=dev)
+    return ops.fuse_labels_sweep_counts(s, class_ids, _as_label_tensor(y_true, dev), th_factors).cpu().numpy()
+
+
+def labelmap_threshold_mIoU(scores, class_ids, y_true, th_factors):
+    """float64 [T]: Mean_IOU of the fused label map at every threshold factor (mean_iou_from_counts of
+    labelmap_threshold_sweep)."""
+    counts = labelmap_threshold_sweep(scores, class_ids, y_true, th_factors)
+    return np.array([mean_iou_from_counts(c) for c in counts], dtype=np.float64)
+
+
 def _label_map_shape(a, img_size):
     """(H, W) of a label map given as [H, W], [H, W, 1] or flat with img_size."""
     shape = tuple(a.shape)

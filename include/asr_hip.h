@@ -306,6 +306,30 @@ int asr_fuse_labels_f32(const float* scores, const float* max_scores, float* min
                         int64_t* counts, int64_t pixels, int K, float th_factor, const int* ids, int classes,
                         asr_stream_t stream);
 
+/* Label fusion swept over T = num_factors threshold factors, counts only (the label-map counterpart of
+ * asr_threshold_sweep_iou_counts_f32): th_factor is read by the fusion alone, so the SR outputs of one run hold every factor's
+ * label map.  scores [K, pixels], ids, classes: as asr_fuse_labels_f32 (a bad set is refused through the same check, before
+ * any launch); truth [pixels]: required; factors: T device floats in any order, repeats, negative values and values above 1
+ * allowed, 1 <= T <= 64.
+ *  - Equivalence: counts is int64 [T, 3, 256], zeroed by the call, and counts[j] equals, bit for bit, the counts that
+ *    asr_fuse_labels_f32(scores, NULL, ws, truth, labels, counts_j, pixels, K, factors[j], ids, classes) leaves.
+ *  - Pass rule: class k passes at pixel p for factor j exactly when S_k(p) > max(S_k) * factors[j] (f32 product, strict).
+ *  - Winner: the passing class with the greatest S_k(p) labels the pixel, equal values (-0.0 == +0.0 among them) going to the
+ *    lowest k; the label is 0 when no class passes.  The winner is NOT monotone in the factor: the top-scoring class can fail
+ *    its own, larger, threshold while a lower-scoring class of a smaller maximum still passes and takes the pixel.
+ *  - Counted labels: labels outside 0..255 are not counted, as in asr_class_counts_i32; counts[j][0], the truth histogram, is
+ *    therefore the same for every j.
+ *  - No max-map form: with max maps (slice_max) the threshold plays no part, so there is nothing to sweep.
+ *  - Exact for finite inputs.  No label map is written; only the counts leave the device.
+ * One asr_minmax_f32 over the K planes, one pass in which every plane is read once for all T factors, one small finalize
+ * launch.  workspace: asr_fuse_labels_sweep_workspace_bytes(K, T) = 8 * (T * 2 * (K + 1) + 256) + 8 * K bytes (per factor the
+ * predicted and the agreeing pixels of label 0 and of the K ids, one truth histogram, then the per-plane extrema), 8-byte
+ * aligned, fully rewritten by each call (0 for K <= 0 or T <= 0); a short workspace returns ASR_ERR_WORKSPACE. */
+size_t asr_fuse_labels_sweep_workspace_bytes(int K, int num_factors);
+int asr_fuse_labels_sweep_counts_f32(const float* scores, const int32_t* truth, const float* factors, void* workspace,
+                                     size_t workspace_bytes, int64_t* counts, int64_t pixels, int K, int num_factors,
+                                     const int* ids, int classes, asr_stream_t stream);
+
 /* The standard label map of the same class set: bilinear upsample + argmax of the un-augmented copy's logits (exactly
  * asr_standard_mask_classes_i32's), the winner kept when it is one of ids, else 0 -- bit for bit the sum over k of that
  * entry point's K masks, one int32 [h_out, w_out] written once. */

@@ -19,7 +19,13 @@ w pixels of a ground-truth label boundary (include/asr_hip.h, "trimap"), void (2
 truth, summed over the images, in long form (evaluation.write_confusion_csv: key, truth label, predicted label, pixels, share of
 the truth label's pixels; "other" holds void and every value outside 0..labels-1), and next to it <stem>_metrics.csv with pixel
 accuracy, mean class accuracy, mIoU, frequency-weighted IoU and per-label precision / recall / IoU, once with the other bin left
-out (the VOC protocol) and once with it kept as a label (Mean_IOU's convention).  FILE: one label name per line."""
+out (the VOC protocol) and once with it kept as a label (Mean_IOU's convention).  FILE: one label name per line.
+
+--th_factors 0.1,0.15,... or --th_sweep (the 17 factors 0.10 ... 0.90 of threshold_tests.py) [--th_sweep_out FILE]: the curve of
+label-map mIoU against the threshold factor, from the SR outputs this one run already holds -- no further forward pass or solve
+(include/asr_hip.h at asr_fuse_labels_sweep_counts_f32; not in slice_max mode, where the threshold plays no part).  One CSV row
+per factor (evaluation.write_labelmap_threshold_csv) and the best factor per SR type by dataset mIoU on the console.  Without
+these flags nothing else is computed or written."""
 import argparse
 import os
 import sys
@@ -57,6 +63,10 @@ parser.add_argument("--trimap_out", default=None, help="CSV file for the trimap 
 parser.add_argument("--confusion_out", default=None, help="CSV file for the confusion matrices (not counted when omitted)")
 parser.add_argument("--confusion_labels", type=int, default=21, help="labels 0..N-1 of the confusion matrix (1..64)")
 parser.add_argument("--class_names", default=None, help="text file with one label name per line (default: the numbers)")
+parser.add_argument("--th_factors", default=None,
+                    help="comma-separated threshold factors (at most 64), e.g. 0.1,0.15,0.2: the label maps' threshold curve too")
+parser.add_argument("--th_sweep", action="store_true", help="the 17 factors 0.10 ... 0.90 of threshold_tests.py as --th_factors")
+parser.add_argument("--th_sweep_out", default=None, help="CSV file for the threshold curve (default: <--out stem>_thresholds.csv)")
 parser.add_argument("--no_prune", action="store_true", help="solve every class, also those that win no pixel (same results)")
 
 
@@ -64,8 +74,9 @@ def main():
     args = parser.parse_args()
     import torch
     from asr_amd import distributed as D
-    from asr_amd.evaluation import (LABELMAP_KEYS, dataset_miou, evaluate_labelmaps, write_confusion_csv,
-                                    write_confusion_metrics_csv, write_labelmap_csv, write_trimap_csv)
+    from asr_amd.evaluation import (LABELMAP_KEYS, best_threshold_factors, dataset_miou, evaluate_labelmaps,
+                                    write_confusion_csv, write_confusion_metrics_csv, write_labelmap_csv,
+                                    write_labelmap_threshold_csv, write_trimap_csv)
     from asr_amd.model import DeeplabV3Plus
     from asr_amd.pipeline import HotPath
     from asr_amd.superresolution_scripts.optimizer import Optimizer
@@ -77,6 +88,20 @@ def main():
     bands = [int(v) for v in args.band_widths.split(",")] if args.band_widths else None
     if args.confusion_out and not 1 <= args.confusion_labels <= 64:
         parser.error("--confusion_labels must lie in 1..64")
+    factors = None
+    if args.th_factors and args.th_sweep:
+        parser.error("--th_factors and --th_sweep are two ways to name the factors: give one")
+    if args.th_factors:
+        factors = [float(v) for v in args.th_factors.split(",")]
+    elif args.th_sweep:
+        from asr_amd.sweep import TH_FACTORS
+        factors = [float(v) for v in TH_FACTORS]
+    if args.th_sweep_out and factors is None:
+        parser.error("--th_sweep_out needs --th_factors or --th_sweep")
+    if factors is not None and not 1 <= len(factors) <= 64:
+        parser.error("--th_factors holds 1..64 factors")
+    if factors is not None and args.mode == "slice_max":
+        parser.error("--th_factors / --th_sweep: in slice_max mode the threshold plays no part, there is nothing to sweep")
     names = None
     if args.class_names:
         with open(args.class_names) as fh:
@@ -100,8 +125,10 @@ def main():
     out = evaluate_labelmaps(path, paths, gts, class_ids, num_aug=args.num_aug, angle_max=args.angle_max,
                              shift_max=args.shift_max, img_size=IMG_SIZE, rank=rank, world=world, seed=SEED,
                              prune=not args.no_prune, save_dir=args.save_dir, band_widths=bands,
-                             confusion_labels=args.confusion_labels if args.confusion_out else None)
+                             confusion_labels=args.confusion_labels if args.confusion_out else None,
+                             **(dict(th_factors=factors) if factors is not None else {}))
     rows, counts = out[:2]
+    confusion = out[4 if bands else 2] if args.confusion_out else None
     if rank == 0:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         write_labelmap_csv(args.out, counts, rows)
@@ -116,9 +143,16 @@ def main():
         if args.confusion_out:
             metrics = os.path.splitext(os.path.abspath(args.confusion_out))[0] + "_metrics.csv"
             os.makedirs(os.path.dirname(os.path.abspath(args.confusion_out)), exist_ok=True)
-            write_confusion_csv(args.confusion_out, out[-1], names)
-            write_confusion_metrics_csv(metrics, out[-1], names)
+            write_confusion_csv(args.confusion_out, confusion, names)
+            write_confusion_metrics_csv(metrics, confusion, names)
             print(f"Wrote {args.confusion_out} and {metrics}")
+        if factors is not None:
+            curve = args.th_sweep_out or os.path.splitext(os.path.abspath(args.out))[0] + "_thresholds.csv"
+            os.makedirs(os.path.dirname(os.path.abspath(curve)), exist_ok=True)
+            write_labelmap_threshold_csv(curve, factors, out[-1], out[-2], counts, rows)
+            for key, (f, miou) in best_threshold_factors(factors, out[-1]).items():
+                print(f"{key}: best th_factor {f!r} by dataset mIoU ({miou:.4f})")
+            print(f"Wrote {curve}")
     if world > 1:
         torch.distributed.barrier()
         torch.distributed.destroy_process_group()

@@ -3,6 +3,7 @@
 
     python tools/bench_labelmap.py --what kernel --impl fuse|threshold
     python tools/bench_labelmap.py --what e2e --impl labels|labels_noprune|classes [--root DIR] [--images 10]
+    python tools/bench_labelmap.py --what sweep --impl sweep|fuse17|e2e [--images 10]
 
 --what kernel: 20 calls on the same K = 4 planes of 512 x 512 floats (no max maps, th_factor 0.2): --impl threshold is
 ops.threshold_classes (K int32 masks out), --impl fuse is ops.fuse_labels (one int32 label map out).  Both launch the min/max
@@ -12,6 +13,11 @@ and 15 made to win by logit-bias shifts over a background that wins everywhere e
 warm-up images.  --impl labels: HotPath.run_image_labels(class_ids=1..20); labels_noprune: the same with prune=False; classes:
 HotPath.run_image_classes fed only the three winning ids -- the cheapest way to the same masks without label maps, and it needs
 the answer in advance.  Prints one JSON line with the ms per image and the number of classes each image's solver was given.
+--what sweep (DESIGN.md "Threshold curve of the label maps"): the 17 factors 0.10 ... 0.90 on K = 4 planes of 512 x 512 with a
+ground truth.  --impl sweep: 20 calls of ops.fuse_labels_sweep_counts (all its launches, the min/max among them); --impl fuse17:
+20 times 17 calls of ops.fuse_labels with the truth, one per factor -- the way to the same counts without the sweep.  Run each
+under rocprofv3 --kernel-trace --stats.  --impl e2e: the e2e workload through run_image_labels with and without th_factors,
+alternated A B A B in one process (two blocks of --images images each), the ms per image of both and their difference.
 --root: the tree whose asr_amd is imported (default: this one), so that an older checkout can be measured by the same code.
 """
 import argparse
@@ -24,8 +30,9 @@ import numpy as np
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-ap.add_argument("--what", choices=["kernel", "e2e"], required=True)
-ap.add_argument("--impl", choices=["fuse", "threshold", "labels", "labels_noprune", "classes"], required=True)
+ap.add_argument("--what", choices=["kernel", "e2e", "sweep"], required=True)
+ap.add_argument("--impl", choices=["fuse", "threshold", "labels", "labels_noprune", "classes", "sweep", "fuse17", "e2e"],
+                required=True)
 ap.add_argument("--images", type=int, default=10)
 args = ap.parse_args()
 sys.path.insert(0, os.path.abspath(args.root))
@@ -58,7 +65,29 @@ def kernel():
     print(json.dumps({"what": "kernel", "impl": args.impl, "bytes_per_call_without_minmax": moved}))
 
 
-def e2e():
+def sweep_kernel():
+    from asr_amd.sweep import TH_FACTORS
+    dev = torch.device("cuda", 0)
+    g = torch.Generator(device=dev).manual_seed(0)
+    ids = [3, 8, 12, 15]
+    planes = torch.rand((4, 512, 512), generator=g, device=dev).contiguous()
+    truth = torch.tensor([0] + ids, dtype=torch.int32, device=dev)[torch.randint(0, 5, (512, 512), generator=g, device=dev)]
+    truth = truth.contiguous()
+    factors = [float(f) for f in TH_FACTORS]
+    f_dev = ops.to_device(np.asarray(factors, dtype=np.float32), device=dev)
+    for _ in range(20):
+        if args.impl == "sweep":
+            ops.fuse_labels_sweep_counts(planes, ids, truth, f_dev)
+        else:
+            for f in factors:
+                ops.fuse_labels(planes, ids, th_factor=f, truth=truth)
+    torch.cuda.synchronize()
+    # what one call of the head must move: the planes and the truth in, the [T, 3, 256] counts out (min/max pass not counted)
+    moved = planes.numel() * 4 + truth.numel() * 4 + len(factors) * 768 * 8
+    print(json.dumps({"what": "sweep", "impl": args.impl, "factors": len(factors), "bytes_per_sweep_call_without_minmax": moved}))
+
+
+def e2e_setup():
     dev = torch.device("cuda", 0)
     model = DeeplabModel(W.make_synthetic_weights(1234, 21), (512, 512, 3), 21, False, None,
                          precision=os.environ.get("ASR_PRECISION", "f16x3"))          # bench.py's default
@@ -84,6 +113,38 @@ def e2e():
     for im in imgs:                                 # the model's own standard masks as ground truth
         logits0 = model.predict_device(im[None].contiguous(), batch_size=1)[0].contiguous()
         gts.append(ops.standard_mask_classes(logits0, (512, 512), WIN).sum(dim=0).to(torch.int32).contiguous())
+    return path, imgs, gts, params
+
+
+def sweep_e2e():
+    from asr_amd.sweep import TH_FACTORS
+    path, imgs, gts, params = e2e_setup()
+    factors = [float(f) for f in TH_FACTORS]
+
+    def block(first, last, swept):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for g in range(first, last):
+            angles, shifts = params[g]
+            path.run_image_labels(imgs[g], angles, shifts, ALL, gt_dev=gts[g], adam_starts={c: g * ITERS for c in ALL},
+                                  **(dict(th_factors=factors) if swept else {}))
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3 / (last - first)
+
+    for swept in (False, True):
+        block(0, WARM, swept)
+    ms = {False: [], True: []}
+    for _ in range(2):                              # A B A B
+        for swept in (False, True):
+            ms[swept].append(block(WARM, len(imgs), swept))
+    plain, swept = float(np.mean(ms[False])), float(np.mean(ms[True]))
+    print(json.dumps({"what": "sweep", "impl": "e2e", "images": args.images, "factors": len(factors),
+                      "plain_ms_per_image": [round(v, 3) for v in ms[False]], "swept_ms_per_image": [round(v, 3) for v in ms[True]],
+                      "added_ms_per_image": round(swept - plain, 3), "ratio": round(swept / plain, 4)}))
+
+
+def e2e():
+    path, imgs, gts, params = e2e_setup()
     solved = []
 
     def one(g):
@@ -109,4 +170,7 @@ def e2e():
 
 
 if __name__ == "__main__":
-    kernel() if args.what == "kernel" else e2e()
+    if args.what == "sweep":
+        sweep_e2e() if args.impl == "e2e" else sweep_kernel()
+    else:
+        kernel() if args.what == "kernel" else e2e()
