@@ -71,7 +71,13 @@ int asr_augment_copies_f32(const float* image, float* copies, const float* rot_t
 
 /* ------------------------------------------------------------------------------------------
  * Super-resolution solver (superresolution_scripts/superresolution.py, optimizer.py)
- * x [batch,H,W]; y / resid [batch,n,h,w]; transforms [batch,n,8]; H = f*h, W = f*w, f even.
+ * x [batch,H,W]; y / resid [batch,n,h,w]; transforms [batch,n,8]: any ImageProjectiveTransformV3 vector (the
+ * reference builds rotations and pure translations, which take fast paths; affine-but-not-pure and projective
+ * vectors take generic branches with the same arithmetic), the inv_* ones used as given.
+ * Shapes: asr_sr_forward_residual_f32, asr_sr_backward_*, asr_sr_solve_* need H = f*h, W = f*w with ONE even
+ * factor f >= 2 for both axes; anything else (odd f, f = 1, unequal factors, a non-multiple) returns
+ * ASR_ERR_UNSUPPORTED before anything is launched or written.  asr_sr_init_target_f32 and asr_realign_* resize
+ * with TF's half-pixel bilinear rule at any ratio: every positive H, W, h, w is accepted.
  * ------------------------------------------------------------------------------------------ */
 
 /* x = tf.image.resize(y[:, 0], (H, W)) -- superresolution.py:112-113. */
@@ -173,7 +179,8 @@ int asr_sr_solve_cfg_f32(float* x, const float* y, const float* rot_tf, const fl
 
 /* out[b] = max / mean over copies of rotate(translate(resize(y[b,i], (H,W)), trans_tf), rot_tf)
  * -- max_superresolution / mean_superresolution, superresolution.py:139-161 (trans_tf built
- * from -shifts, rot_tf from -angles).  out [batch,H,W]. */
+ * from -shifts, rot_tf from -angles).  out [batch,H,W]; (H, W) need not be a multiple of (h, w).  The maximum runs
+ * over the warped copies as they are, zero fill included: where every copy is negative or out of frame it is 0. */
 int asr_realign_max_f32(const float* y, float* out, const float* trans_tf, const float* rot_tf, int batch, int n,
                         int H, int W, int h, int w, asr_stream_t stream);
 int asr_realign_mean_f32(const float* y, float* out, const float* trans_tf, const float* rot_tf, int batch, int n,

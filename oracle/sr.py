@@ -291,15 +291,24 @@ class Superresolution:
         return self._drop_masks[n_drop]
 
     # -- superresolution.py:44-100 ---------------------------------------------------
-    def forward_model(self, target, angles, shifts):
-        n = len(angles)
+    # Every stage exists twice: the *_tf twin takes explicit [n,8] ImageProjectiveTransformV3 vectors (any projective
+    # transform, the inverses of the gradient AS GIVEN, never re-inverted); the angle/shift method builds the vectors the
+    # way tfa.image.rotate / translate and TF's registered gradient do and calls the twin.  Same float32 operations in
+    # the same order either way.
+    def forward_model_tf(self, target, rot_tf, trans_tf):
+        n = len(rot_tf)
         tiled = target.expand(n, *target.shape[1:])
-        rot = tf_ops.rotate(tiled, angles)
-        aug = tf_ops.translate(rot, shifts)
+        rot = tf_ops.projective_transform(tiled, rot_tf)
+        aug = tf_ops.projective_transform(rot, trans_tf)
         return tf_ops.resize_bilinear(aug, self.feature_size)
 
-    def loss_terms(self, target, samples, angles, shifts):
-        d = self.forward_model(target, angles, shifts)
+    def forward_model(self, target, angles, shifts):
+        h, w = target.shape[1:3]
+        return self.forward_model_tf(target, tf_ops.angles_to_projective_transforms(angles, h, w),
+                                     tf_ops.translations_to_projective_transforms(shifts))
+
+    def loss_terms_tf(self, target, samples, rot_tf, trans_tf):
+        d = self.forward_model_tf(target, rot_tf, trans_tf)
         resid = d - samples
         df = torch.sum(resid * resid)
         dy, dx = tf_ops.image_gradients(target)
@@ -310,6 +319,11 @@ class Superresolution:
         l2 = torch.sum(target * target)
         l1 = torch.sum(torch.abs(target))
         return resid, dy, dx, df, tv, l2, l1
+
+    def loss_terms(self, target, samples, angles, shifts):
+        h, w = target.shape[1:3]
+        return self.loss_terms_tf(target, samples, tf_ops.angles_to_projective_transforms(angles, h, w),
+                                  tf_ops.translations_to_projective_transforms(shifts))
 
     def loss_function(self, target, samples, angles, shifts, n_drop=0):
         target = torch.as_tensor(np.asarray(target, dtype=np.float32))
@@ -324,21 +338,26 @@ class Superresolution:
             loss = loss + self.lambda_L1 * l1
         return float(loss)
 
-    def loss_and_grad(self, target, samples, angles, shifts):
+    def data_grad_copies_tf(self, resid, inv_rot_tf, inv_trans_tf):
+        """Per-copy data-term gradient [n,H,W,1] that reaches the (tiled) target: ResizeBilinearGrad of 2*lambda_df*resid,
+        then ImageProjectiveTransformV3 with the inverse translate and the inverse rotation vectors as given."""
+        h, w = self.output_size
+        g_d = (2.0 * self.lambda_df) * resid
+        g_t = tf_ops.resize_bilinear_grad(g_d, (h, w))
+        g_r = tf_ops.projective_transform(g_t, inv_trans_tf, output_shape=(h, w))
+        return tf_ops.projective_transform(g_r, inv_rot_tf, output_shape=(h, w))
+
+    def loss_and_grad_tf(self, target, samples, rot_tf, trans_tf, inv_rot_tf, inv_trans_tf):
         """What tf.GradientTape.gradient(loss, [target]) yields at superresolution.py:133, with
         TF's registered gradients: SquaredDifference -> 2*g*(x-y); ResizeBilinearGrad (exact
         adjoint); ImageProjectiveTransformV3 grad (inverse-warp of the upstream gradient, twice:
         translate then rotate); Tile grad (sum over copies); Abs grad (sign); Square grad (2x)."""
-        h, w = self.output_size
-        resid, dy, dx, df, tv, l2, l1 = self.loss_terms(target, samples, angles, shifts)
+        resid, dy, dx, df, tv, l2, l1 = self.loss_terms_tf(target, samples, rot_tf, trans_tf)
         loss = self.lambda_df * df + self.lambda_tv * tv
         loss = loss + self.lambda_L2 * l2
         if self.lambda_L1 > 0.0:
             loss = loss + self.lambda_L1 * l1
-        g_d = (2.0 * self.lambda_df) * resid
-        g_t = tf_ops.resize_bilinear_grad(g_d, (h, w))
-        g_r = tf_ops.projective_transform_grad(g_t, tf_ops.translations_to_projective_transforms(shifts), (h, w))
-        g_x = tf_ops.projective_transform_grad(g_r, tf_ops.angles_to_projective_transforms(angles, h, w), (h, w))
+        g_x = self.data_grad_copies_tf(resid, inv_rot_tf, inv_trans_tf)
         g_df = torch.zeros_like(target)
         for i in range(g_x.shape[0]):          # fixed order n = 0..N-1 (the HIP kernel's order)
             g_df[0] += g_x[i]
@@ -354,6 +373,13 @@ class Superresolution:
         if self.lambda_L1 > 0.0:
             grad = grad + self.lambda_L1 * torch.sign(target)
         return loss, grad
+
+    def loss_and_grad(self, target, samples, angles, shifts):
+        h, w = self.output_size
+        rot_tf = tf_ops.angles_to_projective_transforms(angles, h, w)
+        trans_tf = tf_ops.translations_to_projective_transforms(shifts)
+        return self.loss_and_grad_tf(target, samples, rot_tf, trans_tf, tf_ops.invert_transforms(rot_tf),
+                                     tf_ops.invert_transforms(trans_tf))
 
     # -- superresolution.py:102-137 --------------------------------------------------
     def augmented_superresolution(self, augmented_copies, angles, shifts, return_trajectory=False):
@@ -386,21 +412,35 @@ class Superresolution:
         return out, float(loss)
 
     # -- superresolution.py:139-161 --------------------------------------------------
-    def _realign(self, augmented_copies, angles, shifts):
+    def _realign_tf(self, augmented_copies, trans_tf, rot_tf):
+        """trans_tf / rot_tf: the vectors of translate(-shifts) / rotate(-angles), applied as given."""
         samples = _stack(augmented_copies)
         up = tf_ops.resize_bilinear(samples, self.output_size)
-        tr = tf_ops.translate(up, -np.asarray(shifts, dtype=np.float32))
-        return tf_ops.rotate(tr, -np.asarray(angles, dtype=np.float32))
+        tr = tf_ops.projective_transform(up, trans_tf)
+        return tf_ops.projective_transform(tr, rot_tf)
+
+    def _realign(self, augmented_copies, angles, shifts):
+        h, w = self.output_size
+        return self._realign_tf(augmented_copies,
+                                tf_ops.translations_to_projective_transforms(-np.asarray(shifts, dtype=np.float32)),
+                                tf_ops.angles_to_projective_transforms(-np.asarray(angles, dtype=np.float32), h, w))
+
+    @staticmethod
+    def max_of(realigned):
+        return torch.amax(realigned, dim=0).numpy()
+
+    @staticmethod
+    def mean_of(realigned):
+        acc = torch.zeros_like(realigned[0])
+        for i in range(realigned.shape[0]):    # fixed order, then one divide (tf.reduce_mean)
+            acc += realigned[i]
+        return (acc / np.float32(realigned.shape[0])).numpy()
 
     def max_superresolution(self, augmented_copies, angles, shifts):
-        return torch.amax(self._realign(augmented_copies, angles, shifts), dim=0).numpy(), None
+        return self.max_of(self._realign(augmented_copies, angles, shifts)), None
 
     def mean_superresolution(self, augmented_copies, angles, shifts):
-        r = self._realign(augmented_copies, angles, shifts)
-        acc = torch.zeros_like(r[0])
-        for i in range(r.shape[0]):            # fixed order, then one divide (tf.reduce_mean)
-            acc += r[i]
-        return (acc / np.float32(r.shape[0])).numpy(), None
+        return self.mean_of(self._realign(augmented_copies, angles, shifts)), None
 
 
 def min_max_normalization(image, new_min=0.0, new_max=255.0, global_min=None, global_max=None):

@@ -275,3 +275,76 @@ def test_nearest_warp_and_mean_iou_known_answers():
     assert set(np.unique(r.numpy())) <= set(np.unique(x.numpy())) | {0.0}               # labels are never blended
     assert o_aug.Mean_IOU(np.array([0, 0, 8, 8, 255]), np.array([0, 8, 8, 8, 0])) == 0.5  # (1/3 + 2/3) / 2
     assert np.isnan(o_aug.Mean_IOU(np.array([255, 255]), np.array([0, 0])))
+
+
+def _tf_level_problem(seed, n, H, W, h, w):
+    rng = np.random.default_rng(seed)
+    x = torch.from_numpy(rng.standard_normal((1, H, W, 1)).astype(np.float32))
+    y = torch.from_numpy(rng.random((n, h, w, 1), dtype=np.float32))
+    ang = rng.uniform(-0.6, 0.6, n).astype(np.float32)
+    sh = (rng.uniform(-0.3, 0.3, (n, 2)) * [W, H]).astype(np.float32)
+    ang[0] = 0
+    sh[0] = 0
+    return x, y, ang, sh
+
+
+def test_transform_level_oracle_equals_angle_level_bit_for_bit():
+    """The *_tf twins of the SR oracle, fed the vectors tfa builds from the angles / shifts and their TF-style inverses, give
+    the angle-level results bit for bit: residual, loss terms, gradient (TV and bilateral TV) and both realign modes."""
+    n, H, W, h, w = 6, 64, 64, 16, 16
+    x, y, ang, sh = _tf_level_problem(40, n, H, W, h, w)
+    rot, tr = tf_ops.angles_to_projective_transforms(ang, H, W), tf_ops.translations_to_projective_transforms(sh)
+    irot, itr = tf_ops.invert_transforms(rot), tf_ops.invert_transforms(tr)
+    for btv in (False, True):
+        sr = o_sr.Superresolution(1.0, 0.3, 0.7, 0.05, num_aug=n, feature_size=(h, w), output_size=(H, W), use_BTV=btv)
+        assert torch.equal(sr.forward_model_tf(x, rot, tr), sr.forward_model(x, ang, sh))
+        for a, b in zip(sr.loss_terms_tf(x, y, rot, tr), sr.loss_terms(x, y, ang, sh)):
+            assert torch.equal(a, b)
+        loss_tf, g_tf = sr.loss_and_grad_tf(x, y, rot, tr, irot, itr)
+        loss, g = sr.loss_and_grad(x, y, ang, sh)
+        assert torch.equal(g_tf, g) and float(loss_tf) == float(loss)
+        # the angle-level gradient is the pre-split composition, restated here from the primitives
+        resid = sr.loss_terms(x, y, ang, sh)[0]
+        g_x = tf_ops.projective_transform_grad(
+            tf_ops.projective_transform_grad(tf_ops.resize_bilinear_grad(2.0 * resid, (H, W)), tr, (H, W)), rot, (H, W))
+        assert torch.equal(sr.data_grad_copies_tf(resid, irot, itr), g_x)
+    r_tf = sr._realign_tf(y, tf_ops.translations_to_projective_transforms(-sh), tf_ops.angles_to_projective_transforms(-ang, H, W))
+    up = tf_ops.resize_bilinear(y, (H, W))
+    r = tf_ops.rotate(tf_ops.translate(up, -sh), -ang)                       # superresolution.py:140-147 as written
+    assert torch.equal(r_tf, r) and torch.equal(sr._realign(y, ang, sh), r)
+    assert np.array_equal(sr.max_superresolution(y, ang, sh)[0], torch.amax(r, dim=0).numpy())
+    acc = torch.zeros_like(r[0])
+    for i in range(n):
+        acc += r[i]
+    assert np.array_equal(sr.mean_superresolution(y, ang, sh)[0], (acc / np.float32(n)).numpy())
+    assert np.array_equal(sr.max_of(r_tf), sr.max_superresolution(y, ang, sh)[0])
+    assert np.array_equal(sr.mean_of(r_tf), sr.mean_superresolution(y, ang, sh)[0])
+
+
+def test_transform_level_gradient_on_a_rectangle_with_projective_terms():
+    """40 x 72 <- 10 x 18, projective terms in both stages: the transform-level gradient is ResizeBilinearGrad, then
+    ImageProjectiveTransformV3 with the inverse translate vectors, then with the inverse rotation vectors (both as given, not
+    re-inverted), then the sum over the copies in copy order."""
+    n, H, W, h, w = 5, 40, 72, 10, 18
+    x, y, ang, sh = _tf_level_problem(41, n, H, W, h, w)
+    rot, tr = tf_ops.angles_to_projective_transforms(ang, H, W), tf_ops.translations_to_projective_transforms(sh)
+    rot[1::2, 6:] = [[1.0e-3, -0.8e-3], [-1.2e-3, 0.6e-3]]
+    tr[2, :2] = [1.05, 0.03]
+    tr[4, 6:] = [-0.7e-3, 1.1e-3]
+    irot, itr = tf_ops.invert_transforms(rot), tf_ops.invert_transforms(tr)
+    sr = o_sr.Superresolution(1.0, 0.0, 0.0, 0.0, num_aug=n, feature_size=(h, w), output_size=(H, W))
+    resid = sr.loss_terms_tf(x, y, rot, tr)[0]
+    tiled = x.expand(n, H, W, 1)
+    fwd = tf_ops.resize_bilinear(tf_ops.projective_transform(tf_ops.projective_transform(tiled, rot), tr), (h, w))
+    assert torch.equal(resid, fwd - y)
+    g_t = tf_ops.resize_bilinear_grad(2.0 * resid, (H, W))
+    g_x = tf_ops.projective_transform(tf_ops.projective_transform(g_t, itr, output_shape=(H, W)), irot, output_shape=(H, W))
+    want = torch.zeros_like(x)
+    for i in range(n):
+        want[0] += g_x[i]
+    _, grad = sr.loss_and_grad_tf(x, y, rot, tr, irot, itr)
+    assert torch.isfinite(grad).all() and float(want.abs().max()) > 0.1
+    assert torch.equal(grad, want)                                           # the priors are switched off: +-0 only
+    # a wrong inverse must show: the inverses are used, and used as given
+    _, other = sr.loss_and_grad_tf(x, y, rot, tr, tf_ops.invert_transforms(irot), itr)
+    assert not torch.equal(other, grad)
