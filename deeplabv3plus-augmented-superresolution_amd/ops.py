@@ -762,14 +762,20 @@ def dwconv3x3_split(x, w_33c, bias, stride=1, rate=1, pre_relu=False, post_relu=
     return y, (b, ho, wo), chunks
 
 
-def pwconv_presplit(x_split, w_packed16, bias, k, n, chunks, out=None, residual=None, relu=0):
-    """Pointwise conv on a split-f16 operand (dwconv3x3_split); w_packed16 from pack_pw_weights_f16x3."""
-    m = x_split.shape[0]
+def pwconv_presplit(x_split, w_packed16, bias, k, n, chunks, out=None, residual=None, relu=0, ldx_chunks=None, ldy=None,
+                    ldres=None, m=None):
+    """Pointwise conv on a split-f16 operand (dwconv3x3_split); w_packed16 from pack_pw_weights_f16x3.  ldx_chunks: chunks
+    per row of x_split (default `chunks`, of which the first ceil(k / 32) are used); ldy / ldres: floats per row of out /
+    residual (default: their last dimension); m: rows (default: x_split's)."""
+    ldx_chunks = ldx_chunks or chunks
+    m = m if m is not None else x_split.shape[0]
     if out is None:
         out = torch.empty((m, n), dtype=f32, device=x_split.device)
+        ldy = n
+    ldy = ldy or out.shape[-1]
+    ldres = ldres or (residual.shape[-1] if residual is not None else 0)
     call("asr_pwconv_mfma_f16x3_presplit", ptr(x_split), ptr(w_packed16), ptr(bias, allow_none=True),
-         ptr(residual, allow_none=True), ptr(out), m, k, n, chunks, out.shape[-1], residual.shape[-1] if residual is not None else 0,
-         int(relu), stream_ptr())
+         ptr(residual, allow_none=True), ptr(out), m, k, n, ldx_chunks, ldy, ldres, int(relu), stream_ptr())
     return out
 
 

@@ -352,7 +352,7 @@ def test_presplit_sepconv_matches_the_f32_handoff(dev, c, n, hw, stride, rate):
     assert float(rec[:, c:].abs().max()) == 0.0 if chunks * 32 > c else True
 
 
-@pytest.mark.parametrize("k,n,relu", [(728, 728, 0), (256, 256, 1), (128, 256, 2), (1024, 1536, 1)])
+@pytest.mark.parametrize("k,n,relu", [(728, 728, 0), (256, 256, 1), (128, 256, 2), (1024, 1536, 1), (160, 256, 1), (192, 440, 0)])
 def test_presplit_gemm_persistent_walk_is_bit_identical_to_one_tile_per_workgroup(dev, k, n, relu):
     """Rows are independent: one launch over all rows must equal, bit for bit, launches over row blocks of <= 256 tiles --
     ragged M, the padded last N-tile of 728, every activation mode -- and sit within the f32-grade bound of the float64
