@@ -32,7 +32,8 @@ _i = C.c_int
 _i64 = C.c_int64
 _fl = C.c_float
 _sz = C.c_size_t
-_ip = C.POINTER(C.c_int)         # host int arrays read during the call (class sets)
+_ip = C.POINTER(C.c_int)         # host int arrays read during the call (class sets, the ranks of asr_realign_select_f32)
+MAX_SELECT_PLANES = 8            # asr_realign_select_f32: num_q <= 8
 MAX_CLASS_SET = 32               # ASR_MAX_CLASS_SET
 MAX_BAND_WIDTH, MAX_BAND_WIDTHS, MAX_BAND_PREDS = 64, 16, 8     # asr_band_class_counts_i32's limits
 MAX_CONFUSION_LABELS, MAX_CONFUSION_PREDS = 64, 8               # ASR_CONFUSION_MAX_LABELS / _MAX_PREDS
@@ -73,6 +74,8 @@ SIGNATURES = {
     "asr_realign_max_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "asr_realign_mean_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "asr_realign_max_mean_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "asr_realign_select_max_copies": (_i, []),
+    "asr_realign_select_f32": (_i, [_vp, _vp, _vp, _ip, _ip, _f, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "asr_minmax_f32": (_i, [_vp, _vp, _i64, _i, _vp]),
     "asr_class_activation_f32": (_i, [_vp, _vp, _i64, _i, _i, _vp]),
     "asr_argmax_i32": (_i, [_vp, _vp, _i64, _i, _vp]),

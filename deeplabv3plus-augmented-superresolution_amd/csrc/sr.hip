@@ -791,7 +791,75 @@ __global__ __launch_bounds__(256) void sr_loss_prior_kernel(const float* __restr
     }
 }
 
-// ---- realign: max / mean over copies of InvWarp(upsample(y_n)) (superresolution.py:139-161) --
+// ---- realign: max / mean / order statistics over copies of InvWarp(upsample(y_n)) (superresolution.py:139-161) --
+// The value of copy bn = b * n + i at output pixel (X, Y): rotate(translate(resize(y[bn], (H,W)), trans_tf[bn]), rot_tf[bn]),
+// zero fill included.  The ONE statement of that arithmetic: sr_realign_kernel folds it into a max / a sum and
+// sr_realign_select_kernel selects from it, so the two agree bit for bit.
+__device__ __forceinline__ float sr_realign_copy_value(const float* __restrict__ y, const float* __restrict__ trans_tf,
+                                                       const float* __restrict__ rot_tf, int bn, int X, int Y, int H, int W,
+                                                       int lh, int lw, float scale_y, float scale_x) {
+    const float* src = y + (int64_t)bn * lh * lw;
+    const AsrTf8 tt = asr_load_tf(trans_tf + (int64_t)bn * 8);
+    const AsrTf8 tr = asr_load_tf(rot_tf + (int64_t)bn * 8);
+    auto rd_up = [&](int yu, int xu) -> float {  // tf.image.resize(y_n, (H,W)) at integer (yu,xu)
+        if (!(yu >= 0 && yu < H && xu >= 0 && xu < W)) return 0.0f;
+        const AsrLerp ly = asr_half_pixel(yu, scale_y, lh);
+        const AsrLerp lx = asr_half_pixel(xu, scale_x, lw);
+        const float tl = src[ly.lo * lw + lx.lo], trv = src[ly.lo * lw + lx.hi];
+        const float bl = src[ly.hi * lw + lx.lo], br = src[ly.hi * lw + lx.hi];
+        const float top = tl + (trv - tl) * lx.t;
+        const float bot = bl + (br - bl) * lx.t;
+        return top + (bot - top) * ly.t;
+    };
+    auto rd_tr = [&](int yt, int xt) -> float {
+        if (!(yt >= 0 && yt < H && xt >= 0 && xt < W)) return 0.0f;
+        return asr_tf_sample(tt, rd_up, xt, yt);
+    };
+    float val;
+    // Pure translation (always, for tfa.image.translate): the 2 x 2 translate-stage pixels under the rotation sample
+    // read a 3 x 3 block of upsampled pixels (2 x 2 taps each, shifted by one); evaluate those 9 resize samples once
+    // instead of 16 times.  Same per-tap arithmetic as the generic path (bit-identical); the generic path stays for
+    // other transforms and for the float-rounding case where the two tap columns / rows do not abut.
+    float ix, iy;
+    const bool ok = asr_tf_map(tr, (float)X, (float)Y, ix, iy);
+    const float xf = floorf(ix), yf = floorf(iy);
+    const int x0 = asr_coord_to_int(xf), y0 = asr_coord_to_int(yf);
+    const bool pure_translation = (tt.a0 == 1.0f) & (tt.a1 == 0.0f) & (tt.b0 == 0.0f) & (tt.b1 == 1.0f) &
+                                  (tt.c0 == 0.0f) & (tt.c1 == 0.0f);
+    const float jx0 = (float)x0 + tt.a2, jx1 = (float)(x0 + 1) + tt.a2;
+    const float jy0 = (float)y0 + tt.b2, jy1 = (float)(y0 + 1) + tt.b2;
+    const float fx0 = floorf(jx0), fx1 = floorf(jx1), fy0 = floorf(jy0), fy1 = floorf(jy1);
+    const int cx0 = asr_coord_to_int(fx0), cx1 = asr_coord_to_int(fx1);
+    const int cy0 = asr_coord_to_int(fy0), cy1 = asr_coord_to_int(fy1);
+    if (ok && pure_translation && cx1 == cx0 + 1 && cy1 == cy0 + 1) {
+        float uv[3][3];
+#pragma unroll
+        for (int a = 0; a < 3; ++a)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) uv[a][c] = rd_up(cy0 + a, cx0 + c);
+        const float wxl0 = (fx0 + 1.0f) - jx0, wxh0 = jx0 - fx0, wxl1 = (fx1 + 1.0f) - jx1, wxh1 = jx1 - fx1;
+        const float wyl0 = (fy0 + 1.0f) - jy0, wyh0 = jy0 - fy0, wyl1 = (fy1 + 1.0f) - jy1, wyh1 = jy1 - fy1;
+        auto Tq = [&](int a, int c, float wxl, float wxh, float wyl, float wyh) -> float {
+            const float vyf = wxl * uv[a][c] + wxh * uv[a][c + 1];
+            const float vyc = wxl * uv[a + 1][c] + wxh * uv[a + 1][c + 1];
+            return wyl * vyf + wyh * vyc;
+        };
+        const bool vx0 = x0 >= 0 && x0 < W, vx1 = x0 + 1 >= 0 && x0 + 1 < W;
+        const bool vy0 = y0 >= 0 && y0 < H, vy1 = y0 + 1 >= 0 && y0 + 1 < H;
+        const float v00 = (vy0 && vx0) ? Tq(0, 0, wxl0, wxh0, wyl0, wyh0) : 0.0f;
+        const float v01 = (vy0 && vx1) ? Tq(0, 1, wxl1, wxh1, wyl0, wyh0) : 0.0f;
+        const float v10 = (vy1 && vx0) ? Tq(1, 0, wxl0, wxh0, wyl1, wyh1) : 0.0f;
+        const float v11 = (vy1 && vx1) ? Tq(1, 1, wxl1, wxh1, wyl1, wyh1) : 0.0f;
+        const float wxl = (xf + 1.0f) - ix, wxh = ix - xf;
+        const float vyf = wxl * v00 + wxh * v01;
+        const float vyc = wxl * v10 + wxh * v11;
+        val = ((yf + 1.0f) - iy) * vyf + (iy - yf) * vyc;
+    } else {
+        val = asr_tf_sample(tr, rd_tr, X, Y);
+    }
+    return val;
+}
+
 // MODE 0: mean -> out_a; 1: max -> out_a; 2: both in one pass (max -> out_a, mean -> out_b): the reference calls
 // max_superresolution and mean_superresolution on the same copies (SR_single_class.py:103-110), and the per-copy value
 // is the expensive part.
@@ -808,66 +876,7 @@ __global__ __launch_bounds__(256) void sr_realign_kernel(const float* __restrict
     const int H = d.H, W = d.W, lh = d.h, lw = d.w;
     float acc_sum = 0.0f, acc_max = 0.0f;
     for (int n = 0; n < d.n; ++n) {
-        const int bn = b * d.n + n;
-        const float* src = y + (int64_t)bn * lh * lw;
-        const AsrTf8 tt = asr_load_tf(trans_tf + (int64_t)bn * 8);
-        const AsrTf8 tr = asr_load_tf(rot_tf + (int64_t)bn * 8);
-        auto rd_up = [&](int yu, int xu) -> float {  // tf.image.resize(y_n, (H,W)) at integer (yu,xu)
-            if (!(yu >= 0 && yu < H && xu >= 0 && xu < W)) return 0.0f;
-            const AsrLerp ly = asr_half_pixel(yu, scale_y, lh);
-            const AsrLerp lx = asr_half_pixel(xu, scale_x, lw);
-            const float tl = src[ly.lo * lw + lx.lo], trv = src[ly.lo * lw + lx.hi];
-            const float bl = src[ly.hi * lw + lx.lo], br = src[ly.hi * lw + lx.hi];
-            const float top = tl + (trv - tl) * lx.t;
-            const float bot = bl + (br - bl) * lx.t;
-            return top + (bot - top) * ly.t;
-        };
-        auto rd_tr = [&](int yt, int xt) -> float {
-            if (!(yt >= 0 && yt < H && xt >= 0 && xt < W)) return 0.0f;
-            return asr_tf_sample(tt, rd_up, xt, yt);
-        };
-        float val;
-        // Pure translation (always, for tfa.image.translate): the 2 x 2 translate-stage pixels under the rotation sample
-        // read a 3 x 3 block of upsampled pixels (2 x 2 taps each, shifted by one); evaluate those 9 resize samples once
-        // instead of 16 times.  Same per-tap arithmetic as the generic path (bit-identical); the generic path stays for
-        // other transforms and for the float-rounding case where the two tap columns / rows do not abut.
-        float ix, iy;
-        const bool ok = asr_tf_map(tr, (float)X, (float)Y, ix, iy);
-        const float xf = floorf(ix), yf = floorf(iy);
-        const int x0 = asr_coord_to_int(xf), y0 = asr_coord_to_int(yf);
-        const bool pure_translation = (tt.a0 == 1.0f) & (tt.a1 == 0.0f) & (tt.b0 == 0.0f) & (tt.b1 == 1.0f) &
-                                      (tt.c0 == 0.0f) & (tt.c1 == 0.0f);
-        const float jx0 = (float)x0 + tt.a2, jx1 = (float)(x0 + 1) + tt.a2;
-        const float jy0 = (float)y0 + tt.b2, jy1 = (float)(y0 + 1) + tt.b2;
-        const float fx0 = floorf(jx0), fx1 = floorf(jx1), fy0 = floorf(jy0), fy1 = floorf(jy1);
-        const int cx0 = asr_coord_to_int(fx0), cx1 = asr_coord_to_int(fx1);
-        const int cy0 = asr_coord_to_int(fy0), cy1 = asr_coord_to_int(fy1);
-        if (ok && pure_translation && cx1 == cx0 + 1 && cy1 == cy0 + 1) {
-            float uv[3][3];
-#pragma unroll
-            for (int a = 0; a < 3; ++a)
-#pragma unroll
-                for (int c = 0; c < 3; ++c) uv[a][c] = rd_up(cy0 + a, cx0 + c);
-            const float wxl0 = (fx0 + 1.0f) - jx0, wxh0 = jx0 - fx0, wxl1 = (fx1 + 1.0f) - jx1, wxh1 = jx1 - fx1;
-            const float wyl0 = (fy0 + 1.0f) - jy0, wyh0 = jy0 - fy0, wyl1 = (fy1 + 1.0f) - jy1, wyh1 = jy1 - fy1;
-            auto Tq = [&](int a, int c, float wxl, float wxh, float wyl, float wyh) -> float {
-                const float vyf = wxl * uv[a][c] + wxh * uv[a][c + 1];
-                const float vyc = wxl * uv[a + 1][c] + wxh * uv[a + 1][c + 1];
-                return wyl * vyf + wyh * vyc;
-            };
-            const bool vx0 = x0 >= 0 && x0 < W, vx1 = x0 + 1 >= 0 && x0 + 1 < W;
-            const bool vy0 = y0 >= 0 && y0 < H, vy1 = y0 + 1 >= 0 && y0 + 1 < H;
-            const float v00 = (vy0 && vx0) ? Tq(0, 0, wxl0, wxh0, wyl0, wyh0) : 0.0f;
-            const float v01 = (vy0 && vx1) ? Tq(0, 1, wxl1, wxh1, wyl0, wyh0) : 0.0f;
-            const float v10 = (vy1 && vx0) ? Tq(1, 0, wxl0, wxh0, wyl1, wyh1) : 0.0f;
-            const float v11 = (vy1 && vx1) ? Tq(1, 1, wxl1, wxh1, wyl1, wyh1) : 0.0f;
-            const float wxl = (xf + 1.0f) - ix, wxh = ix - xf;
-            const float vyf = wxl * v00 + wxh * v01;
-            const float vyc = wxl * v10 + wxh * v11;
-            val = ((yf + 1.0f) - iy) * vyf + (iy - yf) * vyc;
-        } else {
-            val = asr_tf_sample(tr, rd_tr, X, Y);
-        }
+        const float val = sr_realign_copy_value(y, trans_tf, rot_tf, b * d.n + n, X, Y, H, W, lh, lw, scale_y, scale_x);
         if (MODE != 0) acc_max = (n == 0) ? val : fmaxf(acc_max, val);
         if (MODE != 1) acc_sum += val;
     }
@@ -875,6 +884,113 @@ __global__ __launch_bounds__(256) void sr_realign_kernel(const float* __restrict
     if (MODE == 0) out_a[o] = acc_sum / (float)d.n;
     if (MODE == 1) out_a[o] = acc_max;
     if (MODE == 2) { out_a[o] = acc_max; out_b[o] = acc_sum / (float)d.n; }
+}
+
+// ---- order statistics over the same copies: quantiles and the trimmed mean (include/asr_hip.h: the rule) --------------
+// One thread per output pixel, one wave per workgroup (32 x 2 pixels).  The thread parks its n per-copy values in LDS as
+// [copy][pixel], pixel fastest: lane l only ever touches dword l of a 64-dword row, so a column walks ONE bank, no two
+// lanes share a bank, and no barrier is needed (nobody reads another lane's column).  256 bytes per copy: 25.6 KB at
+// n = 100, 51.2 KB at n = 200, 160 KiB at the cap of 640 copies; LDS, not registers, bounds the waves per CU (640 / n).
+// The values are parked as order-preserving keys (sign bit flipped for x >= 0, all bits for x < 0; -0 parked as +0), so
+// every comparison below is one unsigned compare.  s[rank] comes from a 32-step bisection on the key's bits: the largest
+// p with #(key < p) <= rank IS the key of s[rank]; each step counts its column once, the update is a select -- no sort,
+// no data-dependent branch, the same instruction stream for every lane.
+constexpr int kSelX = 32, kSelY = 2, kSelPix = kSelX * kSelY;
+constexpr int kSelMaxQ = 8;
+constexpr int kSelLdsMax = 160 * 1024;
+constexpr int kSelMaxCopies = kSelLdsMax / (kSelPix * (int)sizeof(unsigned));      // 640
+
+struct SrSelect {
+    int num_q, trim_k;
+    int lo[kSelMaxQ], hi[kSelMaxQ];
+    float t[kSelMaxQ];
+};
+
+__device__ __forceinline__ unsigned sr_sel_key(float v) {
+    const unsigned u = __float_as_uint(v == 0.0f ? 0.0f : v);
+    return u ^ ((u >> 31) ? 0xffffffffu : 0x80000000u);
+}
+__device__ __forceinline__ float sr_sel_value(unsigned k) {
+    return __uint_as_float(k ^ ((k >> 31) ? 0x80000000u : 0xffffffffu));
+}
+// key of s[rank], 0 <= rank < n; col: this lane's column (stride kSelPix)
+__device__ __forceinline__ unsigned sr_sel_rank(const unsigned* col, int n, int rank) {
+    unsigned prefix = 0u;
+    for (int bit = 31; bit >= 0; --bit) {
+        const unsigned cand = prefix | (1u << bit);
+        int below = 0;
+#pragma unroll 8
+        for (int i = 0; i < n; ++i) below += (col[i * kSelPix] < cand) ? 1 : 0;
+        prefix = (below <= rank) ? cand : prefix;
+    }
+    return prefix;
+}
+
+__global__ __launch_bounds__(kSelPix) void sr_realign_select_kernel(const float* __restrict__ y, float* __restrict__ out_q,
+                                                                    float* __restrict__ out_trim,
+                                                                    const float* __restrict__ trans_tf,
+                                                                    const float* __restrict__ rot_tf, SrDims d, SrSelect sel,
+                                                                    int tiles_x, float scale_y, float scale_x) {
+    extern __shared__ unsigned sel_keys[];                 // [n][kSelPix]
+    const int tile_y = blockIdx.x / tiles_x, tile_x = blockIdx.x - tile_y * tiles_x;
+    const int X = tile_x * kSelX + threadIdx.x;
+    const int Y = tile_y * kSelY + threadIdx.y;
+    const int b = blockIdx.z;
+    if (X >= d.W || Y >= d.H) return;
+    const int H = d.H, W = d.W, lh = d.h, lw = d.w, n = d.n;
+    unsigned* col = sel_keys + threadIdx.y * kSelX + threadIdx.x;
+    for (int i = 0; i < n; ++i) {
+        const float val = sr_realign_copy_value(y, trans_tf, rot_tf, b * n + i, X, Y, H, W, lh, lw, scale_y, scale_x);
+        col[i * kSelPix] = sr_sel_key(val);
+    }
+    const int64_t plane = (int64_t)d.batch * H * W;
+    const int64_t o = ((int64_t)b * H + Y) * W + X;
+    for (int j = 0; j < sel.num_q; ++j) {
+        const int lo = sel.lo[j], hi = sel.hi[j];
+        const unsigned ka = sr_sel_rank(col, n, lo);
+        float r = sr_sel_value(ka);
+        if (hi != lo) {
+            unsigned kb;
+            if (hi == lo + 1) {
+                // the next rank in one more pass: s[lo + 1] is s[lo] again while copies of it remain, else the least key above
+                int le = 0;
+                unsigned next = 0xffffffffu;
+#pragma unroll 8
+                for (int i = 0; i < n; ++i) {
+                    const unsigned k = col[i * kSelPix];
+                    le += (k <= ka) ? 1 : 0;
+                    next = (k > ka && k < next) ? k : next;
+                }
+                kb = (hi < le) ? ka : next;
+            } else {
+                kb = sr_sel_rank(col, n, hi);
+            }
+            r = r + (sr_sel_value(kb) - r) * sel.t[j];
+        }
+        out_q[j * plane + o] = r;
+    }
+    if (out_trim) {
+        const int k = sel.trim_k, m = n - 2 * k;
+        const unsigned ka = sr_sel_rank(col, n, k);
+        const unsigned kc = (m == 1) ? ka : sr_sel_rank(col, n, n - 1 - k);
+        const float a = sr_sel_value(ka), c = sr_sel_value(kc);
+        float sum = 0.0f;
+        int le_a = 0, lt_c = 0;
+#pragma unroll 8
+        for (int i = 0; i < n; ++i) {                      // copy order
+            const unsigned key = col[i * kSelPix];
+            sum += (key > ka && key < kc) ? sr_sel_value(key) : 0.0f;
+            le_a += (key <= ka) ? 1 : 0;
+            lt_c += (key < kc) ? 1 : 0;
+        }
+        if (ka == kc) {
+            sum = (float)m * a;
+        } else {
+            sum = sum + (float)(le_a - k) * a;             // the copies of a at ranks k ..
+            sum = sum + (float)(n - k - lt_c) * c;         // the copies of c at ranks .. n - 1 - k
+        }
+        out_trim[o] = sum / (float)m;
+    }
 }
 
 int check_dims(const char* fn, int batch, int n, int H, int W, int h, int w, SrDims* d) {
@@ -1180,6 +1296,43 @@ extern "C" int asr_realign_max_mean_f32(const float* y, float* out_max, float* o
                                         const float* rot_tf, int batch, int n, int H, int W, int h, int w,
                                         asr_stream_t stream) {
     return realign_common(2, y, out_max, out_mean, trans_tf, rot_tf, batch, n, H, W, h, w, stream);
+}
+
+extern "C" int asr_realign_select_max_copies(void) { return kSelMaxCopies; }
+
+extern "C" int asr_realign_select_f32(const float* y, float* out_q, float* out_trim, const int* lo_rank, const int* hi_rank,
+                                      const float* t, int num_q, int trim_k, const float* trans_tf, const float* rot_tf,
+                                      int batch, int n, int H, int W, int h, int w, asr_stream_t stream) {
+    ASR_REQUIRE(y && trans_tf && rot_tf, "asr_realign_select_f32: null pointer");
+    ASR_REQUIRE(num_q >= 0 && num_q <= kSelMaxQ, "asr_realign_select_f32: num_q=%d (0..%d)", num_q, kSelMaxQ);
+    ASR_REQUIRE(num_q > 0 || out_trim, "asr_realign_select_f32: nothing to compute (num_q = 0 and no out_trim)");
+    ASR_REQUIRE(num_q == 0 || (out_q && lo_rank && hi_rank && t), "asr_realign_select_f32: null pointer");
+    ASR_REQUIRE(batch > 0 && batch <= 65535 && n > 0 && H > 0 && W > 0 && h > 0 && w > 0, "asr_realign_select_f32: bad shape");
+    ASR_UNSUPPORTED(n > kSelMaxCopies, "asr_realign_select_f32: n=%d copies, at most %d (256 bytes of LDS per copy, 160 KiB per workgroup)",
+                    n, kSelMaxCopies);
+    SrSelect sel = {};
+    sel.num_q = num_q;
+    for (int j = 0; j < num_q; ++j) {
+        ASR_REQUIRE(lo_rank[j] >= 0 && lo_rank[j] <= hi_rank[j] && hi_rank[j] <= n - 1,
+                    "asr_realign_select_f32: ranks[%d] = (%d, %d) need 0 <= lo <= hi <= n - 1 = %d", j, lo_rank[j], hi_rank[j], n - 1);
+        sel.lo[j] = lo_rank[j]; sel.hi[j] = hi_rank[j]; sel.t[j] = t[j];
+    }
+    ASR_REQUIRE(trim_k >= 0 && 2 * (int64_t)trim_k < n, "asr_realign_select_f32: trim_k=%d needs 0 <= 2k < n = %d", trim_k, n);
+    ASR_REQUIRE(out_trim || trim_k == 0, "asr_realign_select_f32: trim_k=%d without out_trim", trim_k);
+    sel.trim_k = trim_k;
+    const int64_t tiles_x = asr_cdiv(W, kSelX), tiles = tiles_x * asr_cdiv(H, kSelY);
+    ASR_REQUIRE(tiles <= 0x7fffffff, "asr_realign_select_f32: %dx%d output exceeds the grid", H, W);
+    SrDims d;
+    d.batch = batch; d.n = n; d.H = H; d.W = W; d.h = h; d.w = w; d.f = 0;
+    const float sy = (float)h / (float)H, sx = (float)w / (float)W;
+    const size_t lds = sizeof(unsigned) * (size_t)n * kSelPix;
+    static AsrDeviceOnce once;
+    if (lds > 64 * 1024)
+        ASR_HIP_CHECK(asr_allow_dynamic_lds(once, reinterpret_cast<const void*>(sr_realign_select_kernel), kSelLdsMax));
+    hipLaunchKernelGGL(sr_realign_select_kernel, dim3((unsigned)tiles, 1, (unsigned)batch), dim3(kSelX, kSelY), lds,
+                       asr_stream(stream), y, out_q, out_trim, trans_tf, rot_tf, d, sel, (int)tiles_x, sy, sx);
+    ASR_LAUNCH_CHECK();
+    return ASR_OK;
 }
 
 #ifdef ASR_DIAG_KFWD_CHECK

@@ -10,7 +10,7 @@ import torch
 
 from . import distributed as D, ops
 from .superresolution_scripts.augmentation_utils import _image_to_device
-from .superresolution_scripts.superres_utils import DATA_EXTS, compute_SR, load_SR_data, probe_SR_data
+from .superresolution_scripts.superres_utils import DATA_EXTS, EXTRA_SR_TYPES, compute_SR, load_SR_data, probe_SR_data
 from .utils import compute_IoU, load_image
 
 
@@ -36,7 +36,8 @@ def interchange_files(root_dir):
 
 
 def evaluate_precomputed(sr, paths, gt_dir, standard_dir=None, num_aug=100, class_id=8, th_factor=0.65,
-                         img_size=(512, 512), out_dir=None, rank=0, world=1, save_final_output=False):
+                         img_size=(512, 512), out_dir=None, rank=0, world=1, save_final_output=False, extra_sr_types=(),
+                         save_extra_output=False):
     """Returns (table, valid) on every rank: the [len(paths), 6] IoU table (distributed.IOU_FIELDS order) and the bool
     mask of the files that were evaluated.  The row of an invalid file is all-NaN and never enters a mean, like the
     reference's ``continue`` (SR_single_class.py:85-90); a VALID image whose IoUs are NaN (class absent from both masks)
@@ -48,7 +49,22 @@ def evaluate_precomputed(sr, paths, gt_dir, standard_dir=None, num_aug=100, clas
     (two for slice_max files: class map and max map).  Each valid file is then loaded once, when its turn comes.  ``sr.optimizer``'s global step
     counter is then set per image to what the reference's sequential loop would have reached: num_iter * (solves of the
     valid files before it); a skipped file runs no solve there, so it does not advance the counter here either, and
-    sharding changes no update."""
+    sharding changes no update.
+
+    extra_sr_types: any of "median" and "trimmed_mean" (compute_SR's one-pass robust fusions; sr.trim is the trimmed
+    fraction).  When it is not empty a THIRD value is returned: the [len(paths), len(extra_sr_types)] table of their
+    single-class IoUs (compute_IoU without background, like the max and mean columns), gathered like the main table, an
+    invalid file's row NaN.  They run after the three reference types and use no optimizer state, so the first two return
+    values are what they are without extras.  save_extra_output writes their masks as PNGs under out_dir.  Like the three
+    reference types, each extra type goes through compute_SR, which creates its ``{type}_SR`` folder under out_dir whether
+    or not anything is saved there: with extras, out_dir must be a folder path (None is refused before any work)."""
+    extra = tuple(extra_sr_types)
+    for t in extra:
+        if t not in EXTRA_SR_TYPES:
+            raise ValueError(f"extra_sr_types: {t!r} is not one of {EXTRA_SR_TYPES}")
+    if extra and paths and out_dir is None:
+        raise ValueError("extra_sr_types needs out_dir: compute_SR creates each type's folder under it")
+    extra_records = []
     mine = D.shard_indices(len(paths), rank, world)
     flags = []
     for g in mine:
@@ -64,6 +80,7 @@ def evaluate_precomputed(sr, paths, gt_dir, standard_dir=None, num_aug=100, clas
     for g in mine:
         if not valid[g]:
             records.append([np.nan] * len(D.IOU_FIELDS))
+            extra_records.append([np.nan] * len(extra))
             continue
         class_masks, max_masks, angles, shifts, filename = load_SR_data(paths[g], num_aug=num_aug)
         sr.optimizer.optimizer.iterations = int(before[g]) * sr.num_iter
@@ -83,7 +100,14 @@ def evaluate_precomputed(sr, paths, gt_dir, standard_dir=None, num_aug=100, clas
                               compute_IoU(true_mask, out["aug"], img_size=img_size, class_id=class_id, include_bg=True),
                               compute_IoU(true_mask, out["max"], img_size=img_size, class_id=class_id),
                               compute_IoU(true_mask, out["mean"], img_size=img_size, class_id=class_id)])
-    return D.all_gather_iou(mine, records, len(paths)), valid
+        extra_records.append([compute_IoU(true_mask, compute_SR(sr, class_masks, angles, shifts, filename, max_masks=mm,
+                                                                SR_type=t, class_id=class_id, dest_folder=out_dir,
+                                                                th_factor=th_factor, save_final_output=save_extra_output),
+                                          img_size=img_size, class_id=class_id) for t in extra])
+    table = D.all_gather_iou(mine, records, len(paths))
+    if not extra:
+        return table, valid
+    return table, valid, D.all_gather_rows(mine, extra_records, len(paths), len(extra))
 
 
 CLASS_CSV_COLUMNS = ("aug_iou_multiple", "standard_iou_multiple", "aug_iou_single", "standard_iou_single", "max_iou",

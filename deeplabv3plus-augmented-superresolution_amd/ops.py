@@ -342,6 +342,47 @@ def realign(y, trans_tf, rot_tf, out_hw, mode):
     return out
 
 
+def quantile_ranks(n, q):
+    """The linear-interpolation quantile q in [0, 1] of n sorted values as (lo, hi, t): p = q * (n - 1) in float64,
+    lo = floor(p), hi = ceil(p), t = float32(p - lo), to be read as s[lo] + (s[hi] - s[lo]) * t (numpy's default rule).
+    The median of an even n is (n/2 - 1, n/2, 0.5)."""
+    n = int(n)
+    q = float(q)
+    if n < 1:
+        raise ValueError(f"quantile_ranks: n={n} (>= 1)")
+    if not 0.0 <= q <= 1.0:
+        raise ValueError(f"quantile_ranks: q={q} outside [0, 1]")
+    p = np.float64(q) * np.float64(n - 1)
+    lo, hi = int(np.floor(p)), int(np.ceil(p))
+    return lo, hi, float(np.float32(p - lo))
+
+
+def realign_select(y, trans_tf, rot_tf, out_hw, ranks=None, trim_k=None):
+    """Order statistics over the realigned copies in one launch (asr_realign_select_f32; the rule: include/asr_hip.h).
+    y [B,N,h,w]; ranks: a list of up to 8 (lo, hi, t) -- plane j is s[lo] + (s[hi] - s[lo]) * t of the N sorted values of a
+    pixel, s[lo] itself when lo == hi (quantile_ranks builds them); trim_k: None for no trimmed mean, else k >= 0, the mean
+    of s[k] .. s[N-1-k] (k = 0: the mean of all N sorted values).  Returns (q [Q,B,H,W] or None, trim [B,H,W] or None)."""
+    if y.dim() != 4:
+        raise AsrError("realign_select: y must be [B,N,h,w]")
+    b, n, h, w = y.shape
+    _check_tf(trans_tf, b, n, "trans_tf")
+    _check_tf(rot_tf, b, n, "rot_tf")
+    ranks = list(ranks or [])
+    nq = len(ranks)
+    if nq > _lib.MAX_SELECT_PLANES:
+        raise AsrError(f"realign_select: {nq} rank triples (at most {_lib.MAX_SELECT_PLANES})")
+    want_trim = trim_k is not None
+    H, W = int(out_hw[0]), int(out_hw[1])
+    q = torch.empty((nq, b, H, W), dtype=f32, device=y.device) if nq else None
+    trim = torch.empty((b, H, W), dtype=f32, device=y.device) if want_trim else None
+    lo = (C.c_int * max(nq, 1))(*[int(r[0]) for r in ranks])
+    hi = (C.c_int * max(nq, 1))(*[int(r[1]) for r in ranks])
+    t = (C.c_float * max(nq, 1))(*[float(r[2]) for r in ranks])
+    call("asr_realign_select_f32", ptr(y), ptr(q, allow_none=True), ptr(trim, allow_none=True), lo, hi, t, nq,
+         int(trim_k) if want_trim else 0, ptr(trans_tf), ptr(rot_tf), b, n, H, W, h, w, stream_ptr())
+    return q, trim
+
+
 # ---------------------------------------------------------------------------------------------
 # OPM / threshold / IoU
 # ---------------------------------------------------------------------------------------------

@@ -1,6 +1,8 @@
 """``Superresolution`` with the reference's surface (superresolution_scripts/superresolution.py:26-161):
 ``loss_function``, ``augmented_superresolution``, ``max_superresolution``, ``mean_superresolution``
--- plus batched variants that solve many images in one sequence of launches.  All arithmetic
+-- plus batched variants that solve many images in one sequence of launches, and the robust one-pass fusions
+``median_superresolution``, ``quantile_superresolution`` and ``trimmed_mean_superresolution`` (order statistics over the
+realigned copies, ``realign_select_batch``).  All arithmetic
 runs in the fused HIP kernels of csrc/sr.hip; this class only prepares float32 parameters.
 
 ``use_BTV`` swaps the TV prior for the bilateral TV of superresolution.py:8-23 (inside the same
@@ -64,7 +66,9 @@ def bilateral_tv(target_image, alpha=0.6, shift_factor=2):
 class Superresolution:
     def __init__(self, lambda_df, lambda_tv, lambda_L2, lambda_L1, num_iter=200, num_aug=100,
                  optimizer: Optimizer = None, feature_size=(64, 64), output_size=(512, 512), use_BTV=False,
-                 verbose=False, copy_dropout=0.0):
+                 verbose=False, copy_dropout=0.0, trim=0.1):
+        if not 0.0 <= float(trim) < 0.5:
+            raise ValueError(f"trim must be in [0, 0.5), got {trim}")
         self.lambda_df = lambda_df
         self.lambda_tv = lambda_tv
         self.lambda_L2 = lambda_L2
@@ -77,6 +81,7 @@ class Superresolution:
         self.use_BTV = use_BTV
         self.verbose = verbose
         self.copy_dropout = copy_dropout
+        self.trim = float(trim)      # trimmed-mean SR drops int(trim * n) copies at each end (scipy.stats.trim_mean's rule)
         self._drop_masks = {}        # n_drop -> bool [num_aug], frozen at first use (tf.function trace time)
 
     # -- parameter preparation ----------------------------------------------------------------
@@ -242,3 +247,36 @@ class Superresolution:
 
     def mean_superresolution(self, augmented_copies, angles, shifts):
         return self._realign_single(augmented_copies, angles, shifts, "mean")
+
+    # -- order statistics over the realigned copies (not in the reference) -------------------------------------------
+    def realign_select_batch(self, copies, angles, shifts, qs=(), trim=None):
+        """copies [B,N,h,w] device, realigned as in realign_batch -> (device [len(qs),B,H,W] or None, device [B,H,W] or
+        None): the pixel-wise quantiles qs (linear interpolation between the two nearest ranks, numpy's default; 0.5 is the
+        median) and, with trim (a fraction in [0, 0.5)), the mean of the sorted copies without the int(trim * N) smallest
+        and the int(trim * N) largest.  One launch; the N realigned planes are never written."""
+        n = copies.shape[1]
+        k = None
+        if trim is not None:
+            if not 0.0 <= float(trim) < 0.5:
+                raise ValueError(f"trim must be in [0, 0.5), got {trim}")
+            k = int(float(trim) * n)
+        rot, tr = self._transforms(angles, shifts, copies.device, negate=True)
+        ranks = [ops.quantile_ranks(n, q) for q in qs]
+        return ops.realign_select(copies, tr, rot, self.output_size, ranks=ranks, trim_k=k)
+
+    def _select_single(self, augmented_copies, angles, shifts, qs=(), trim=None):
+        dev = _lib.require_gpu()
+        y = _stack_copies(augmented_copies, dev)[None]
+        a, s = self._batchify(angles, shifts)
+        q_out, t_out = self.realign_select_batch(y, a, s, qs=qs, trim=trim)
+        out = q_out[0, 0] if trim is None else t_out[0]
+        return out.cpu().numpy()[..., None], None
+
+    def quantile_superresolution(self, augmented_copies, angles, shifts, q):
+        return self._select_single(augmented_copies, angles, shifts, qs=(q,))
+
+    def median_superresolution(self, augmented_copies, angles, shifts):
+        return self.quantile_superresolution(augmented_copies, angles, shifts, 0.5)
+
+    def trimmed_mean_superresolution(self, augmented_copies, angles, shifts):
+        return self._select_single(augmented_copies, angles, shifts, trim=self.trim)

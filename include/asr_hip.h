@@ -191,6 +191,33 @@ int asr_realign_mean_f32(const float* y, float* out, const float* trans_tf, cons
 int asr_realign_max_mean_f32(const float* y, float* out_max, float* out_mean, const float* trans_tf,
                              const float* rot_tf, int batch, int n, int H, int W, int h, int w, asr_stream_t stream);
 
+/* Order statistics over the realigned copies: the pixel-wise median, other quantiles and the trimmed mean, the robust
+ * fusions of multi-frame super-resolution, in ONE launch that never writes the N warped planes to memory.
+ * y, trans_tf, rot_tf, batch, n, H, W, h, w are exactly those of asr_realign_max_f32: any positive sizes at any ratio,
+ * any ImageProjectiveTransformV3 vector.  lo_rank, hi_rank, t are HOST arrays of num_q entries, read during the call
+ * (like asr_sr_config).
+ *
+ * The rule.  For output pixel (b, Y, X) let v_0 .. v_(n-1) be the values sr_realign_kernel folds, that is
+ * rotate(translate(resize(y[b,i]))) at that pixel, zero fill included: an out-of-frame copy contributes 0 to the order
+ * statistics, as it does to max and mean.  Let s_0 <= .. <= s_(n-1) be the same values sorted.
+ *  - out_q is [num_q, batch, H, W], 0 <= num_q <= 8.  Plane j is s[lo] when lo == hi, otherwise
+ *    s[lo] + (s[hi] - s[lo]) * t[j], in f32 with two roundings and no contraction (lo = lo_rank[j], hi = hi_rank[j]).
+ *    It needs 0 <= lo <= hi <= n - 1.
+ *  - out_trim is [batch, H, W] and optional: pass NULL and trim_k = 0 to skip it.  It is the mean of s[k] .. s[n-1-k]
+ *    with k = trim_k, 0 <= 2k < n.
+ *  - The trimmed mean is computed as follows.  Let a = s[k] and c = s[n-1-k].  The sum is (the sum of the v_i with
+ *    a < v_i < c, in copy order) + c_a * a + c_c * c, where c_a and c_c are how many copies of each boundary value lie
+ *    inside the kept ranks.  When a == c the sum is (n - 2k) * a.  The result is that sum divided by (float)(n - 2k).
+ *  - -0 and +0 compare equal, and either may be returned.  Results for NaN inputs are unspecified.
+ * num_q == 0 with out_trim == NULL, a bad rank, null pointers and bad shapes return ASR_ERR_INVALID_ARG before any
+ * launch; n above asr_realign_select_max_copies() returns ASR_ERR_UNSUPPORTED (the message names the cap) and nothing is
+ * launched.  Each thread owns one output pixel and keeps its n values in LDS (256 bytes per copy and workgroup of 64
+ * pixels), so the cap is what fits a workgroup's 160 KiB. */
+int asr_realign_select_max_copies(void);      /* host arithmetic, no GPU: the largest n accepted below (>= 256) */
+int asr_realign_select_f32(const float* y, float* out_q, float* out_trim, const int* lo_rank, const int* hi_rank,
+                           const float* t, int num_q, int trim_k, const float* trans_tf, const float* rot_tf, int batch,
+                           int n, int H, int W, int h, int w, asr_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * Output processing, thresholding, IoU
  * ------------------------------------------------------------------------------------------ */

@@ -26,12 +26,18 @@ def main():
     ap.add_argument("--th_factor", type=float, default=0.65)
     ap.add_argument("--feature_size", type=int, default=FEATURE_SIZE[0],
                     help="side of the stored model outputs: 128 for the Xception copies, 64 for MobileNet (OS 8)")
-    ap.add_argument("--out", default=os.path.join(ROOT, "data", "superres_root", "superres_output"))
+    ap.add_argument("--out", default=None, help="output folder (default: data/superres_root/superres_output); when given, "
+                    "the masks of --extra_sr_types are written there as PNGs")
+    ap.add_argument("--extra_sr_types", default="", help="comma-separated one-pass robust fusions to score after the "
+                    "reference's six means: median, trimmed_mean")
+    ap.add_argument("--trim", type=float, default=0.1, help="fraction of the copies the trimmed mean drops at each end")
     args = ap.parse_args()
+    extra = tuple(t for t in args.extra_sr_types.split(",") if t)
+    out_dir = args.out or os.path.join(ROOT, "data", "superres_root", "superres_output")
 
     import torch
     from asr_amd import distributed as D
-    from asr_amd.evaluation import evaluate_precomputed, interchange_files, mean_over_valid
+    from asr_amd.evaluation import evaluate_precomputed, interchange_files, mean_over_valid, valid_rows
     from asr_amd.superresolution_scripts.optimizer import Optimizer
     from asr_amd.superresolution_scripts.superresolution import Superresolution
 
@@ -42,15 +48,23 @@ def main():
                               decay_rate=HYPER["decay_rate"])
     sr = Superresolution(lambda_df=HYPER["lambda_df"], lambda_tv=HYPER["lambda_tv"], lambda_L2=HYPER["lambda_L2"],
                          lambda_L1=HYPER["lambda_L1"], num_iter=HYPER["num_iter"], num_aug=args.num_aug,
-                         optimizer=optimizer_obj, feature_size=(args.feature_size, args.feature_size))
+                         optimizer=optimizer_obj, feature_size=(args.feature_size, args.feature_size), trim=args.trim)
     paths = interchange_files(args.data)[:args.num_samples]
-    table, valid = evaluate_precomputed(sr, paths, args.gt, args.standard, num_aug=args.num_aug, class_id=args.class_id,
-                                        th_factor=args.th_factor, img_size=IMG_SIZE, out_dir=args.out, rank=rank, world=world)
+    res = evaluate_precomputed(sr, paths, args.gt, args.standard, num_aug=args.num_aug, class_id=args.class_id,
+                               th_factor=args.th_factor, img_size=IMG_SIZE, out_dir=out_dir, rank=rank, world=world,
+                               extra_sr_types=extra, save_extra_output=bool(extra) and args.out is not None)
+    table, valid = res[0], res[1]
     if rank == 0:
         m = mean_over_valid(table, valid)
         print(f"Avg. Standard IoUs (No bg): {m['standard_single']},  Avg. Augmented SR IoUs (No bg): {m['aug_single']}")
         print(f"Avg. Standard IoUs (with bg): {m['standard_bg']},  Avg. Augmented SR IoUs (with bg): {m['aug_bg']}")
         print(f"Avg. Max SR IoUs: {m['max']}, Avg. Mean SR IoUs: {m['mean']}")
+        if extra:
+            import numpy as np
+            rows = valid_rows(res[2], valid)
+            for j, t in enumerate(extra):
+                mean = float(np.mean(rows[:, j])) if len(rows) else float("nan")
+                print(f"Avg. {t.replace('_', ' ').capitalize()} SR IoUs: {mean}")
     if world > 1:
         torch.distributed.destroy_process_group()
 
