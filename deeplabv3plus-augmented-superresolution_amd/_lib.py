@@ -76,6 +76,7 @@ SIGNATURES = {
     "asr_realign_max_mean_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "asr_realign_select_max_copies": (_i, []),
     "asr_realign_select_f32": (_i, [_vp, _vp, _vp, _ip, _ip, _f, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "asr_realign_covered_f32": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _fl, _fl, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "asr_minmax_f32": (_i, [_vp, _vp, _i64, _i, _vp]),
     "asr_class_activation_f32": (_i, [_vp, _vp, _i64, _i, _i, _vp]),
     "asr_argmax_i32": (_i, [_vp, _vp, _i64, _i, _vp]),

@@ -24,25 +24,29 @@ __device__ __forceinline__ bool asr_tf_map(const AsrTf8& t, float x, float y, fl
     return proj != 0.0f;
 }
 
-// Bilinear read with TF's weight order; rd(yi, xi) must return 0 for out-of-bounds taps.
+// Bilinear read with TF's weight order; rd(yi, xi) must return 0 for out-of-bounds taps.  The value type is what rd
+// returns: float everywhere but in the realign kernels of sr.hip, which also sample several planes at once through ONE set
+// of coordinates and weights (a small struct of floats with element-wise float * V, V + V).
 template <class Read>
-__device__ __forceinline__ float asr_tf_bilinear(Read rd, float ix, float iy) {
+__device__ __forceinline__ auto asr_tf_bilinear(Read rd, float ix, float iy) -> decltype(rd(0, 0)) {
+    using V = decltype(rd(0, 0));
     const float xf = floorf(ix), yf = floorf(iy);
     const float xc = xf + 1.0f, yc = yf + 1.0f;
     const int x0 = asr_coord_to_int(xf), y0 = asr_coord_to_int(yf);
-    const float v00 = rd(y0, x0), v01 = rd(y0, x0 + 1);
-    const float v10 = rd(y0 + 1, x0), v11 = rd(y0 + 1, x0 + 1);
+    const V v00 = rd(y0, x0), v01 = rd(y0, x0 + 1);
+    const V v10 = rd(y0 + 1, x0), v11 = rd(y0 + 1, x0 + 1);
     const float wxl = xc - ix, wxh = ix - xf;
-    const float vyf = wxl * v00 + wxh * v01;
-    const float vyc = wxl * v10 + wxh * v11;
+    const V vyf = wxl * v00 + wxh * v01;
+    const V vyc = wxl * v10 + wxh * v11;
     return (yc - iy) * vyf + (iy - yf) * vyc;
 }
 
 // Sample rd through transform t at output pixel (x, y).
 template <class Read>
-__device__ __forceinline__ float asr_tf_sample(const AsrTf8& t, Read rd, int x, int y) {
+__device__ __forceinline__ auto asr_tf_sample(const AsrTf8& t, Read rd, int x, int y) -> decltype(rd(0, 0)) {
+    using V = decltype(rd(0, 0));
     float ix, iy;
-    if (!asr_tf_map(t, (float)x, (float)y, ix, iy)) return 0.0f;
+    if (!asr_tf_map(t, (float)x, (float)y, ix, iy)) return V{};
     return asr_tf_bilinear(rd, ix, iy);
 }
 

@@ -792,30 +792,74 @@ __global__ __launch_bounds__(256) void sr_loss_prior_kernel(const float* __restr
 }
 
 // ---- realign: max / mean / order statistics over copies of InvWarp(upsample(y_n)) (superresolution.py:139-161) --
+// NP values that go through the per-copy arithmetic side by side: plane p of a copy sampled at ONE set of coordinates with
+// ONE set of weights.  The operators are element-wise, each the single f32 operation it spells, so every plane's value is
+// what the same statements give on floats (NP = 1 IS a float).
+template <int NP>
+struct SrPlanes {
+    float v[NP];
+};
+template <int NP>
+__device__ __forceinline__ SrPlanes<NP> operator+(const SrPlanes<NP>& a, const SrPlanes<NP>& b) {
+    SrPlanes<NP> r;
+#pragma unroll
+    for (int p = 0; p < NP; ++p) r.v[p] = a.v[p] + b.v[p];
+    return r;
+}
+template <int NP>
+__device__ __forceinline__ SrPlanes<NP> operator-(const SrPlanes<NP>& a, const SrPlanes<NP>& b) {
+    SrPlanes<NP> r;
+#pragma unroll
+    for (int p = 0; p < NP; ++p) r.v[p] = a.v[p] - b.v[p];
+    return r;
+}
+template <int NP>
+__device__ __forceinline__ SrPlanes<NP> operator*(const SrPlanes<NP>& a, float s) {
+    SrPlanes<NP> r;
+#pragma unroll
+    for (int p = 0; p < NP; ++p) r.v[p] = a.v[p] * s;
+    return r;
+}
+template <int NP>
+__device__ __forceinline__ SrPlanes<NP> operator*(float s, const SrPlanes<NP>& a) {
+    SrPlanes<NP> r;
+#pragma unroll
+    for (int p = 0; p < NP; ++p) r.v[p] = s * a.v[p];
+    return r;
+}
+
 // The value of copy bn = b * n + i at output pixel (X, Y): rotate(translate(resize(y[bn], (H,W)), trans_tf[bn]), rot_tf[bn]),
-// zero fill included.  The ONE statement of that arithmetic: sr_realign_kernel folds it into a max / a sum and
-// sr_realign_select_kernel selects from it, so the two agree bit for bit.
-__device__ __forceinline__ float sr_realign_copy_value(const float* __restrict__ y, const float* __restrict__ trans_tf,
-                                                       const float* __restrict__ rot_tf, int bn, int X, int Y, int H, int W,
-                                                       int lh, int lw, float scale_y, float scale_x) {
-    const float* src = y + (int64_t)bn * lh * lw;
+// zero fill included.  The ONE statement of that arithmetic: sr_realign_kernel folds it into a max / a sum,
+// sr_realign_select_kernel selects from it, and the covered kernels take it for the copy's plane of y (.v[0], src[0]) AND
+// for its weight plane (.v[1], src[1]) -- the geometry (both coordinate maps, floors, tap weights, in-frame tests, the choice
+// of the fast path) is computed once and serves every plane -- so all of them agree bit for bit.  src[p]: plane p of THIS copy.
+template <int NP>
+__device__ __forceinline__ SrPlanes<NP> sr_realign_copy_value(const float* const (&src)[NP], const float* __restrict__ trans_tf,
+                                                              const float* __restrict__ rot_tf, int bn, int X, int Y, int H, int W,
+                                                              int lh, int lw, float scale_y, float scale_x) {
+    typedef SrPlanes<NP> V;
+    const V zero = {};
     const AsrTf8 tt = asr_load_tf(trans_tf + (int64_t)bn * 8);
     const AsrTf8 tr = asr_load_tf(rot_tf + (int64_t)bn * 8);
-    auto rd_up = [&](int yu, int xu) -> float {  // tf.image.resize(y_n, (H,W)) at integer (yu,xu)
-        if (!(yu >= 0 && yu < H && xu >= 0 && xu < W)) return 0.0f;
+    auto rd_up = [&](int yu, int xu) -> V {  // tf.image.resize(y_n, (H,W)) at integer (yu,xu)
+        if (!(yu >= 0 && yu < H && xu >= 0 && xu < W)) return zero;
         const AsrLerp ly = asr_half_pixel(yu, scale_y, lh);
         const AsrLerp lx = asr_half_pixel(xu, scale_x, lw);
-        const float tl = src[ly.lo * lw + lx.lo], trv = src[ly.lo * lw + lx.hi];
-        const float bl = src[ly.hi * lw + lx.lo], br = src[ly.hi * lw + lx.hi];
-        const float top = tl + (trv - tl) * lx.t;
-        const float bot = bl + (br - bl) * lx.t;
+        V tl, trv, bl, br;
+#pragma unroll
+        for (int p = 0; p < NP; ++p) {
+            tl.v[p] = src[p][ly.lo * lw + lx.lo]; trv.v[p] = src[p][ly.lo * lw + lx.hi];
+            bl.v[p] = src[p][ly.hi * lw + lx.lo]; br.v[p] = src[p][ly.hi * lw + lx.hi];
+        }
+        const V top = tl + (trv - tl) * lx.t;
+        const V bot = bl + (br - bl) * lx.t;
         return top + (bot - top) * ly.t;
     };
-    auto rd_tr = [&](int yt, int xt) -> float {
-        if (!(yt >= 0 && yt < H && xt >= 0 && xt < W)) return 0.0f;
+    auto rd_tr = [&](int yt, int xt) -> V {
+        if (!(yt >= 0 && yt < H && xt >= 0 && xt < W)) return zero;
         return asr_tf_sample(tt, rd_up, xt, yt);
     };
-    float val;
+    V val;
     // Pure translation (always, for tfa.image.translate): the 2 x 2 translate-stage pixels under the rotation sample
     // read a 3 x 3 block of upsampled pixels (2 x 2 taps each, shifted by one); evaluate those 9 resize samples once
     // instead of 16 times.  Same per-tap arithmetic as the generic path (bit-identical); the generic path stays for
@@ -832,32 +876,39 @@ __device__ __forceinline__ float sr_realign_copy_value(const float* __restrict__
     const int cx0 = asr_coord_to_int(fx0), cx1 = asr_coord_to_int(fx1);
     const int cy0 = asr_coord_to_int(fy0), cy1 = asr_coord_to_int(fy1);
     if (ok && pure_translation && cx1 == cx0 + 1 && cy1 == cy0 + 1) {
-        float uv[3][3];
+        V uv[3][3];
 #pragma unroll
         for (int a = 0; a < 3; ++a)
 #pragma unroll
             for (int c = 0; c < 3; ++c) uv[a][c] = rd_up(cy0 + a, cx0 + c);
         const float wxl0 = (fx0 + 1.0f) - jx0, wxh0 = jx0 - fx0, wxl1 = (fx1 + 1.0f) - jx1, wxh1 = jx1 - fx1;
         const float wyl0 = (fy0 + 1.0f) - jy0, wyh0 = jy0 - fy0, wyl1 = (fy1 + 1.0f) - jy1, wyh1 = jy1 - fy1;
-        auto Tq = [&](int a, int c, float wxl, float wxh, float wyl, float wyh) -> float {
-            const float vyf = wxl * uv[a][c] + wxh * uv[a][c + 1];
-            const float vyc = wxl * uv[a + 1][c] + wxh * uv[a + 1][c + 1];
+        auto Tq = [&](int a, int c, float wxl, float wxh, float wyl, float wyh) -> V {
+            const V vyf = wxl * uv[a][c] + wxh * uv[a][c + 1];
+            const V vyc = wxl * uv[a + 1][c] + wxh * uv[a + 1][c + 1];
             return wyl * vyf + wyh * vyc;
         };
         const bool vx0 = x0 >= 0 && x0 < W, vx1 = x0 + 1 >= 0 && x0 + 1 < W;
         const bool vy0 = y0 >= 0 && y0 < H, vy1 = y0 + 1 >= 0 && y0 + 1 < H;
-        const float v00 = (vy0 && vx0) ? Tq(0, 0, wxl0, wxh0, wyl0, wyh0) : 0.0f;
-        const float v01 = (vy0 && vx1) ? Tq(0, 1, wxl1, wxh1, wyl0, wyh0) : 0.0f;
-        const float v10 = (vy1 && vx0) ? Tq(1, 0, wxl0, wxh0, wyl1, wyh1) : 0.0f;
-        const float v11 = (vy1 && vx1) ? Tq(1, 1, wxl1, wxh1, wyl1, wyh1) : 0.0f;
+        const V v00 = (vy0 && vx0) ? Tq(0, 0, wxl0, wxh0, wyl0, wyh0) : zero;
+        const V v01 = (vy0 && vx1) ? Tq(0, 1, wxl1, wxh1, wyl0, wyh0) : zero;
+        const V v10 = (vy1 && vx0) ? Tq(1, 0, wxl0, wxh0, wyl1, wyh1) : zero;
+        const V v11 = (vy1 && vx1) ? Tq(1, 1, wxl1, wxh1, wyl1, wyh1) : zero;
         const float wxl = (xf + 1.0f) - ix, wxh = ix - xf;
-        const float vyf = wxl * v00 + wxh * v01;
-        const float vyc = wxl * v10 + wxh * v11;
+        const V vyf = wxl * v00 + wxh * v01;
+        const V vyc = wxl * v10 + wxh * v11;
         val = ((yf + 1.0f) - iy) * vyf + (iy - yf) * vyc;
     } else {
         val = asr_tf_sample(tr, rd_tr, X, Y);
     }
     return val;
+}
+// the one-plane form: plane bn of y
+__device__ __forceinline__ float sr_realign_copy_value(const float* __restrict__ y, const float* __restrict__ trans_tf,
+                                                       const float* __restrict__ rot_tf, int bn, int X, int Y, int H, int W,
+                                                       int lh, int lw, float scale_y, float scale_x) {
+    const float* const src[1] = {y + (int64_t)bn * lh * lw};
+    return sr_realign_copy_value<1>(src, trans_tf, rot_tf, bn, X, Y, H, W, lh, lw, scale_y, scale_x).v[0];
 }
 
 // MODE 0: mean -> out_a; 1: max -> out_a; 2: both in one pass (max -> out_a, mean -> out_b): the reference calls
@@ -991,6 +1042,92 @@ __global__ __launch_bounds__(kSelPix) void sr_realign_select_kernel(const float*
         }
         out_trim[o] = sum / (float)m;
     }
+}
+
+// ---- coverage-normalised fusions over the same copies (include/asr_hip.h: the rule) -----------------------------------
+// Each copy's weight plane goes through the statements of its plane of y (sr_realign_copy_value<2>: one geometry, two
+// planes); C = sum of the realigned weights, S = sum of the realigned values, both in copy order like acc_sum above.
+// No packed f32 in these kernels: the unit's default is switched off for them (the two planes invite pairing, and the
+// compiler picks op_sel by itself -- isa_guard.py).
+#if defined(__HIP_DEVICE_COMPILE__)
+#define SR_NO_PK_F32 __attribute__((target("no-packed-fp32-ops")))
+#else
+#define SR_NO_PK_F32
+#endif
+
+struct SrCover {
+    float cov_min, valid_min;
+    int64_t wgt_stride;        // floats between the weight planes of two copies: lh * lw, or 0 for one shared plane
+};
+
+// Mean and / or coverage: the shape of sr_realign_kernel, registers only.
+__global__ __launch_bounds__(256) SR_NO_PK_F32 void sr_realign_covered_kernel(
+    const float* __restrict__ y, const float* __restrict__ wgt, float* __restrict__ out_mean, float* __restrict__ out_cov,
+    const float* __restrict__ trans_tf, const float* __restrict__ rot_tf, SrDims d, SrCover cv, float scale_y, float scale_x) {
+    const int X = blockIdx.x * kTileX + threadIdx.x;
+    const int Y = blockIdx.y * kTileY + threadIdx.y;
+    const int b = blockIdx.z;
+    if (X >= d.W || Y >= d.H) return;
+    const int H = d.H, W = d.W, lh = d.h, lw = d.w;
+    float acc_sum = 0.0f, acc_cov = 0.0f;
+    for (int n = 0; n < d.n; ++n) {
+        const int bn = b * d.n + n;
+        const float* const src[2] = {y + (int64_t)bn * lh * lw, wgt + (int64_t)bn * cv.wgt_stride};
+        const SrPlanes<2> val = sr_realign_copy_value<2>(src, trans_tf, rot_tf, bn, X, Y, H, W, lh, lw, scale_y, scale_x);
+        acc_sum += val.v[0];
+        acc_cov += val.v[1];
+    }
+    const int64_t o = ((int64_t)b * H + Y) * W + X;
+    if (out_cov) out_cov[o] = acc_cov;
+    if (out_mean) out_mean[o] = (acc_cov >= cv.cov_min) ? acc_sum / acc_cov : 0.0f;
+}
+
+// With the median over the valid copies (c_i >= valid_min): the select kernel's LDS layout ([copy][pixel] keys, one wave per
+// workgroup, no barrier) and its bisection.  An invalid copy is parked as 0xffffffff, above the key of every finite value
+// (and of +inf), so the nv valid keys are the nv smallest of the column and s[rank], rank < nv, is found among all n; the
+// ranks come from the pixel's own nv, and the even / odd and nv = 0 cases are selects.
+__global__ __launch_bounds__(kSelPix) SR_NO_PK_F32 void sr_realign_covered_median_kernel(
+    const float* __restrict__ y, const float* __restrict__ wgt, float* __restrict__ out_mean, float* __restrict__ out_median,
+    float* __restrict__ out_cov, const float* __restrict__ trans_tf, const float* __restrict__ rot_tf, SrDims d, SrCover cv,
+    int tiles_x, float scale_y, float scale_x) {
+    extern __shared__ unsigned sel_keys[];                 // [n][kSelPix]
+    const int tile_y = blockIdx.x / tiles_x, tile_x = blockIdx.x - tile_y * tiles_x;
+    const int X = tile_x * kSelX + threadIdx.x;
+    const int Y = tile_y * kSelY + threadIdx.y;
+    const int b = blockIdx.z;
+    if (X >= d.W || Y >= d.H) return;
+    const int H = d.H, W = d.W, lh = d.h, lw = d.w, n = d.n;
+    unsigned* col = sel_keys + threadIdx.y * kSelX + threadIdx.x;
+    float acc_sum = 0.0f, acc_cov = 0.0f;
+    int nv = 0;
+    for (int i = 0; i < n; ++i) {
+        const int bn = b * n + i;
+        const float* const src[2] = {y + (int64_t)bn * lh * lw, wgt + (int64_t)bn * cv.wgt_stride};
+        const SrPlanes<2> val = sr_realign_copy_value<2>(src, trans_tf, rot_tf, bn, X, Y, H, W, lh, lw, scale_y, scale_x);
+        acc_sum += val.v[0];
+        acc_cov += val.v[1];
+        const bool valid = val.v[1] >= cv.valid_min;
+        nv += valid ? 1 : 0;
+        col[i * kSelPix] = valid ? sr_sel_key(val.v[0]) : 0xffffffffu;
+    }
+    const int64_t o = ((int64_t)b * H + Y) * W + X;
+    if (out_cov) out_cov[o] = acc_cov;
+    if (out_mean) out_mean[o] = (acc_cov >= cv.cov_min) ? acc_sum / acc_cov : 0.0f;
+    const int lo = max(nv - 1, 0) / 2, hi = nv / 2;        // nv = 0: rank 0 of a column of parked keys, discarded below
+    const unsigned ka = sr_sel_rank(col, n, lo);
+    int le = 0;
+    unsigned next = 0xffffffffu;
+#pragma unroll 8
+    for (int i = 0; i < n; ++i) {                          // s[lo + 1]: s[lo] again while copies of it remain, else the least key above
+        const unsigned k = col[i * kSelPix];
+        le += (k <= ka) ? 1 : 0;
+        next = (k > ka && k < next) ? k : next;
+    }
+    const unsigned kb = (hi < le) ? ka : next;
+    const float a = sr_sel_value(ka);
+    const float mid = a + (sr_sel_value(kb) - a) * 0.5f;
+    const float r = (hi != lo) ? mid : a;
+    out_median[o] = (nv > 0) ? r : 0.0f;
 }
 
 int check_dims(const char* fn, int batch, int n, int H, int W, int h, int w, SrDims* d) {
@@ -1331,6 +1468,41 @@ extern "C" int asr_realign_select_f32(const float* y, float* out_q, float* out_t
         ASR_HIP_CHECK(asr_allow_dynamic_lds(once, reinterpret_cast<const void*>(sr_realign_select_kernel), kSelLdsMax));
     hipLaunchKernelGGL(sr_realign_select_kernel, dim3((unsigned)tiles, 1, (unsigned)batch), dim3(kSelX, kSelY), lds,
                        asr_stream(stream), y, out_q, out_trim, trans_tf, rot_tf, d, sel, (int)tiles_x, sy, sx);
+    ASR_LAUNCH_CHECK();
+    return ASR_OK;
+}
+
+extern "C" int asr_realign_covered_f32(const float* y, const float* wgt, int wgt_shared, float* out_mean, float* out_median,
+                                       float* out_cov, float cov_min, float valid_min, const float* trans_tf,
+                                       const float* rot_tf, int batch, int n, int H, int W, int h, int w, asr_stream_t stream) {
+    ASR_REQUIRE(y && wgt && trans_tf && rot_tf, "asr_realign_covered_f32: null pointer");
+    ASR_REQUIRE(out_mean || out_median || out_cov, "asr_realign_covered_f32: nothing to compute (out_mean, out_median and out_cov are NULL)");
+    ASR_REQUIRE(batch > 0 && batch <= 65535 && n > 0 && H > 0 && W > 0 && h > 0 && w > 0, "asr_realign_covered_f32: bad shape");
+    ASR_REQUIRE(cov_min > 0.0f && cov_min < __builtin_inff(), "asr_realign_covered_f32: cov_min=%g must be finite and > 0", (double)cov_min);
+    ASR_REQUIRE(valid_min > 0.0f && valid_min < __builtin_inff(), "asr_realign_covered_f32: valid_min=%g must be finite and > 0",
+                (double)valid_min);
+    ASR_UNSUPPORTED(out_median && n > kSelMaxCopies,
+                    "asr_realign_covered_f32: n=%d copies with out_median, at most %d (256 bytes of LDS per copy, 160 KiB per workgroup)",
+                    n, kSelMaxCopies);
+    SrDims d;
+    d.batch = batch; d.n = n; d.H = H; d.W = W; d.h = h; d.w = w; d.f = 0;
+    SrCover cv;
+    cv.cov_min = cov_min; cv.valid_min = valid_min; cv.wgt_stride = wgt_shared ? 0 : (int64_t)h * w;
+    const float sy = (float)h / (float)H, sx = (float)w / (float)W;
+    hipStream_t s = asr_stream(stream);
+    if (!out_median) {
+        hipLaunchKernelGGL(sr_realign_covered_kernel, hr_grid(d), kBlock, 0, s, y, wgt, out_mean, out_cov, trans_tf, rot_tf, d, cv, sy, sx);
+        ASR_LAUNCH_CHECK();
+        return ASR_OK;
+    }
+    const int64_t tiles_x = asr_cdiv(W, kSelX), tiles = tiles_x * asr_cdiv(H, kSelY);
+    ASR_REQUIRE(tiles <= 0x7fffffff, "asr_realign_covered_f32: %dx%d output exceeds the grid", H, W);
+    const size_t lds = sizeof(unsigned) * (size_t)n * kSelPix;
+    static AsrDeviceOnce once;
+    if (lds > 64 * 1024)
+        ASR_HIP_CHECK(asr_allow_dynamic_lds(once, reinterpret_cast<const void*>(sr_realign_covered_median_kernel), kSelLdsMax));
+    hipLaunchKernelGGL(sr_realign_covered_median_kernel, dim3((unsigned)tiles, 1, (unsigned)batch), dim3(kSelX, kSelY), lds, s,
+                       y, wgt, out_mean, out_median, out_cov, trans_tf, rot_tf, d, cv, (int)tiles_x, sy, sx);
     ASR_LAUNCH_CHECK();
     return ASR_OK;
 }

@@ -51,8 +51,8 @@ def evaluate_precomputed(sr, paths, gt_dir, standard_dir=None, num_aug=100, clas
     valid files before it); a skipped file runs no solve there, so it does not advance the counter here either, and
     sharding changes no update.
 
-    extra_sr_types: any of "median" and "trimmed_mean" (compute_SR's one-pass robust fusions; sr.trim is the trimmed
-    fraction).  When it is not empty a THIRD value is returned: the [len(paths), len(extra_sr_types)] table of their
+    extra_sr_types: any of "median", "trimmed_mean", "covered_mean" and "covered_median" (compute_SR's one-pass fusions
+    beyond the reference's; sr.trim is the trimmed fraction, sr.cover / sr.cov_min / sr.valid_min rule the covered ones).  When it is not empty a THIRD value is returned: the [len(paths), len(extra_sr_types)] table of their
     single-class IoUs (compute_IoU without background, like the max and mean columns), gathered like the main table, an
     invalid file's row NaN.  They run after the three reference types and use no optimizer state, so the first two return
     values are what they are without extras.  save_extra_output writes their masks as PNGs under out_dir.  Like the three

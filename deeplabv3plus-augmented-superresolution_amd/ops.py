@@ -383,6 +383,45 @@ def realign_select(y, trans_tf, rot_tf, out_hw, ranks=None, trim_k=None):
     return q, trim
 
 
+COVERED_OUTPUTS = ("mean", "median", "cov")
+
+
+def realign_covered(y, wgt, trans_tf, rot_tf, out_hw, want=("mean",), cov_min=0.5, valid_min=0.5):
+    """Coverage-normalised fusions of the realigned copies in one launch (asr_realign_covered_f32; the rule:
+    include/asr_hip.h).  y [B,N,h,w]; wgt [B,N,h,w], or [h,w]: one plane shared by every copy.  Both go through the same
+    realign; y is NOT multiplied by wgt here (pass y already weighted for sum R(w y) / sum R(w)).  want: any of "mean"
+    (sum of the realigned values / sum of the realigned weights where that sum is >= cov_min, else 0), "median" (over the
+    copies whose realigned weight is >= valid_min at the pixel, 0 where there is none) and "cov" (the sum of the realigned
+    weights).  Returns a dict of [B,H,W] tensors with the keys asked for."""
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or len(set(want)) != len(want) or any(k not in COVERED_OUTPUTS for k in want):
+        raise AsrError(f"realign_covered: want must be a non-empty selection of {COVERED_OUTPUTS} without repeats, got {want!r}")
+    for name, v in (("cov_min", cov_min), ("valid_min", valid_min)):
+        if not (np.isfinite(float(v)) and float(v) > 0.0):
+            raise AsrError(f"realign_covered: {name}={v} must be finite and > 0")
+    if y.dim() != 4:
+        raise AsrError("realign_covered: y must be [B,N,h,w]")
+    b, n, h, w = y.shape
+    if wgt.dim() == 2:
+        shared = 1
+        if tuple(wgt.shape) != (h, w):
+            raise AsrError(f"realign_covered: the shared wgt plane must be [{h},{w}], got {tuple(wgt.shape)}")
+    elif wgt.dim() == 4:
+        shared = 0
+        if tuple(wgt.shape) != (b, n, h, w):
+            raise AsrError(f"realign_covered: wgt must be [{b},{n},{h},{w}] like y, got {tuple(wgt.shape)}")
+    else:
+        raise AsrError(f"realign_covered: wgt must be [B,N,h,w] or [h,w], got {tuple(wgt.shape)}")
+    _check_tf(trans_tf, b, n, "trans_tf")
+    _check_tf(rot_tf, b, n, "rot_tf")
+    H, W = int(out_hw[0]), int(out_hw[1])
+    out = {k: torch.empty((b, H, W), dtype=f32, device=y.device) for k in want}
+    call("asr_realign_covered_f32", ptr(y), ptr(wgt), shared, ptr(out.get("mean"), allow_none=True),
+         ptr(out.get("median"), allow_none=True), ptr(out.get("cov"), allow_none=True), float(cov_min), float(valid_min),
+         ptr(trans_tf), ptr(rot_tf), b, n, H, W, h, w, stream_ptr())
+    return out
+
+
 # ---------------------------------------------------------------------------------------------
 # OPM / threshold / IoU
 # ---------------------------------------------------------------------------------------------

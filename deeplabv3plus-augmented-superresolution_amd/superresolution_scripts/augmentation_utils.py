@@ -37,6 +37,23 @@ def augment_on_device(image_dev, angles, shifts, out=None):
     return ops.augment_copies(image_dev.contiguous(), rot, tr, out=out)
 
 
+def copy_validity(angles, shifts, image_size, size):
+    """The part of each low-resolution copy that came from inside the image: device [N,h,w], (h, w) = size.  It is
+    augment_on_device of an all-ones [h,w,1] image under the copies' own angles and their shifts, drawn in pixels of
+    image_size = (image_h, image_w), taken to the (h, w) frame: [dx, dy] * (w / image_w, h / image_h), the scaling
+    HotPath._sr_frame does for the SR frame.  1 inside, 0 where the rotate / translate of the copy filled zeros, a ramp
+    at the seam."""
+    h, w = int(size[0]), int(size[1])
+    ih, iw = int(image_size[0]), int(image_size[1])
+    dev = _lib.require_gpu()
+    angles = np.asarray(angles, dtype=np.float32).reshape(-1)
+    shifts = np.asarray(shifts, dtype=np.float32).reshape(-1, 2)
+    if (h, w) != (ih, iw):
+        shifts = (shifts * np.array([w / iw, h / ih], dtype=np.float32)).astype(np.float32)
+    ones = torch.ones((h, w, 1), dtype=torch.float32, device=dev)
+    return augment_on_device(ones, angles, shifts)[..., 0].contiguous()
+
+
 def _image_to_device(image):
     dev = _lib.require_gpu()
     if isinstance(image, torch.Tensor):

@@ -246,16 +246,17 @@ def _save_png(path, image, scale=True):
     Image.fromarray(a.astype(np.uint8)).save(path)
 
 
-SR_TYPES = ("aug", "mean", "max", "median", "trimmed_mean")      # compute_SR's SR_type
-EXTRA_SR_TYPES = ("median", "trimmed_mean")                       # the ones beyond the reference's three
+SR_TYPES = ("aug", "mean", "max", "median", "trimmed_mean")      # compute_SR's SR_type ...
+COVERED_SR_TYPES = ("covered_mean", "covered_median")             # ... and the coverage-normalised fusions it also accepts
+EXTRA_SR_TYPES = ("median", "trimmed_mean") + COVERED_SR_TYPES    # the ones beyond the reference's three
 
 
 def compute_SR(superresolution_obj, class_masks, angles, shifts, filename, dest_folder,
                SR_type="aug", max_masks=[], save_intermediate_output=False, save_final_output=False, class_id=8,
                th_factor=0.15):
-    """Dispatch aug / mean / max / median / trimmed_mean SR, then threshold to a {0, class_id} mask [H,W,1] (host int32)."""
-    if SR_type not in SR_TYPES:
-        raise ValueError("SR_type must be one of " + ", ".join(repr(t) for t in SR_TYPES))
+    """Dispatch aug / mean / max / median / trimmed_mean / covered_mean / covered_median SR, then threshold to a {0, class_id} mask [H,W,1] (host int32)."""
+    if SR_type not in SR_TYPES + COVERED_SR_TYPES:
+        raise ValueError("SR_type must be one of " + ", ".join(repr(t) for t in SR_TYPES + COVERED_SR_TYPES))
     out_folder = os.path.join(dest_folder, f"{SR_type}_SR")
     if not os.path.exists(out_folder):
         os.makedirs(out_folder)
@@ -267,6 +268,10 @@ def compute_SR(superresolution_obj, class_masks, angles, shifts, filename, dest_
         SR_function = superresolution_obj.max_superresolution
     elif SR_type == "median":
         SR_function = superresolution_obj.median_superresolution
+    elif SR_type == "covered_mean":
+        SR_function = superresolution_obj.covered_mean_superresolution
+    elif SR_type == "covered_median":
+        SR_function = superresolution_obj.covered_median_superresolution
     else:
         SR_function = superresolution_obj.trimmed_mean_superresolution
 

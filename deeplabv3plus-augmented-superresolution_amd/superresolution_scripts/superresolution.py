@@ -2,7 +2,8 @@
 ``loss_function``, ``augmented_superresolution``, ``max_superresolution``, ``mean_superresolution``
 -- plus batched variants that solve many images in one sequence of launches, and the robust one-pass fusions
 ``median_superresolution``, ``quantile_superresolution`` and ``trimmed_mean_superresolution`` (order statistics over the
-realigned copies, ``realign_select_batch``).  All arithmetic
+realigned copies, ``realign_select_batch``), and their coverage-normalised forms ``covered_mean_superresolution``,
+``covered_median_superresolution`` and ``coverage_map`` (``realign_covered_batch``).  All arithmetic
 runs in the fused HIP kernels of csrc/sr.hip; this class only prepares float32 parameters.
 
 ``use_BTV`` swaps the TV prior for the bilateral TV of superresolution.py:8-23 (inside the same
@@ -63,12 +64,20 @@ def bilateral_tv(target_image, alpha=0.6, shift_factor=2):
     return float(terms[0, 1].item())
 
 
+COVER_MODES = ("frame", "validity")
+
+
 class Superresolution:
     def __init__(self, lambda_df, lambda_tv, lambda_L2, lambda_L1, num_iter=200, num_aug=100,
                  optimizer: Optimizer = None, feature_size=(64, 64), output_size=(512, 512), use_BTV=False,
-                 verbose=False, copy_dropout=0.0, trim=0.1):
+                 verbose=False, copy_dropout=0.0, trim=0.1, cover="frame", cov_min=0.5, valid_min=0.5):
         if not 0.0 <= float(trim) < 0.5:
             raise ValueError(f"trim must be in [0, 0.5), got {trim}")
+        if cover not in COVER_MODES:
+            raise ValueError(f"cover must be one of {COVER_MODES}, got {cover!r}")
+        for name, v in (("cov_min", cov_min), ("valid_min", valid_min)):
+            if not (np.isfinite(float(v)) and float(v) > 0.0):
+                raise ValueError(f"{name} must be finite and > 0, got {v}")
         self.lambda_df = lambda_df
         self.lambda_tv = lambda_tv
         self.lambda_L2 = lambda_L2
@@ -82,6 +91,11 @@ class Superresolution:
         self.verbose = verbose
         self.copy_dropout = copy_dropout
         self.trim = float(trim)      # trimmed-mean SR drops int(trim * n) copies at each end (scipy.stats.trim_mean's rule)
+        # the covered fusions: "frame" counts only what the realign itself moved out of the output frame (a shared all-ones
+        # weight plane), "validity" also what each copy lost when it was made (augmentation_utils.copy_validity)
+        self.cover = cover
+        self.cov_min = float(cov_min)
+        self.valid_min = float(valid_min)
         self._drop_masks = {}        # n_drop -> bool [num_aug], frozen at first use (tf.function trace time)
 
     # -- parameter preparation ----------------------------------------------------------------
@@ -280,3 +294,37 @@ class Superresolution:
 
     def trimmed_mean_superresolution(self, augmented_copies, angles, shifts):
         return self._select_single(augmented_copies, angles, shifts, trim=self.trim)
+
+    # -- coverage-normalised fusions over the realigned copies (not in the reference) --------------------------------
+    def realign_covered_batch(self, copies, angles, shifts, want):
+        """copies [B,N,h,w] device, realigned as in realign_batch -> dict of device [B,H,W] with the keys of want, any of
+        "mean", "median", "cov" (ops.realign_covered): the weights go through the realign of the copies, the mean is the sum
+        of the realigned values over the sum of the realigned weights (0 below cov_min), the median runs over the copies
+        whose realigned weight reaches valid_min, and "cov" is the sum of the realigned weights: on how many copies any
+        fusion of them rests at each pixel.  One launch."""
+        b, n, h, w = copies.shape
+        if self.cover == "frame":
+            y, wgt = copies, torch.ones((h, w), dtype=torch.float32, device=copies.device)
+        else:
+            from .augmentation_utils import copy_validity
+            a, s = np.asarray(angles, dtype=np.float32), np.asarray(shifts, dtype=np.float32)
+            wgt = torch.stack([copy_validity(a[i], s[i], self.output_size, (h, w)) for i in range(b)]).contiguous()
+            y = (copies * wgt).contiguous()
+        rot, tr = self._transforms(angles, shifts, copies.device, negate=True)
+        return ops.realign_covered(y, wgt, tr, rot, self.output_size, want=want, cov_min=self.cov_min,
+                                   valid_min=self.valid_min)
+
+    def _covered_single(self, augmented_copies, angles, shifts, key):
+        dev = _lib.require_gpu()
+        y = _stack_copies(augmented_copies, dev)[None]
+        a, s = self._batchify(angles, shifts)
+        return self.realign_covered_batch(y, a, s, (key,))[key][0].cpu().numpy()[..., None], None
+
+    def covered_mean_superresolution(self, augmented_copies, angles, shifts):
+        return self._covered_single(augmented_copies, angles, shifts, "mean")
+
+    def covered_median_superresolution(self, augmented_copies, angles, shifts):
+        return self._covered_single(augmented_copies, angles, shifts, "median")
+
+    def coverage_map(self, augmented_copies, angles, shifts):
+        return self._covered_single(augmented_copies, angles, shifts, "cov")

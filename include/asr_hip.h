@@ -218,6 +218,34 @@ int asr_realign_select_f32(const float* y, float* out_q, float* out_trim, const 
                            const float* t, int num_q, int trim_k, const float* trans_tf, const float* rot_tf, int batch,
                            int n, int H, int W, int h, int w, asr_stream_t stream);
 
+/* Coverage-normalised fusions over the realigned copies: the shift-and-add mean of multi-frame super-resolution (sum of
+ * the realigned values over the sum of the realigned weights), the median over the copies that saw the pixel, and the
+ * coverage map itself, in ONE launch.  y, trans_tf, rot_tf, batch, n, H, W, h, w are exactly those of
+ * asr_realign_max_f32.  wgt holds the weight planes: [batch, n, h, w] when wgt_shared == 0, ONE [h, w] plane used for every
+ * copy of every image when wgt_shared != 0.  out_mean, out_median, out_cov are [batch, H, W]; each is optional (NULL), at
+ * least one must be given.
+ *
+ * The rule.  For output pixel (b, Y, X) and copy i, v_i is the value sr_realign_kernel folds for plane (b, i) of y, and
+ * c_i is the value the SAME statements give for that copy's weight plane, same transforms, zero fill included: a copy that
+ * left the frame has c_i = 0 instead of counting as a measurement of 0.  y is NOT multiplied by wgt: a caller who wants
+ * sum R(w y) / sum R(w) passes y already weighted.
+ *  - C = c_0 + .. + c_(n-1) and S = v_0 + .. + v_(n-1), each in copy order, in f32, no contraction (the sum of
+ *    asr_realign_mean_f32).
+ *  - out_cov is C.
+ *  - out_mean is S / C (one IEEE f32 division) where C >= cov_min, otherwise 0.
+ *  - Copy i is valid at the pixel when c_i >= valid_min.  Let nv be the number of valid copies and
+ *    s_0 <= .. <= s_(nv-1) their v_i sorted.  out_median is 0 when nv == 0; otherwise, with lo = (nv - 1) / 2 and
+ *    hi = nv / 2 (integer division), it is s[lo] when lo == hi, else s[lo] + (s[hi] - s[lo]) * 0.5f, in f32 with two
+ *    roundings and no contraction (the rule of asr_realign_select_f32).
+ *  - -0 and +0 compare equal, and either may be returned.  Results for NaN inputs are unspecified.
+ * Null y / wgt / transforms, all three outputs NULL, a bad shape, and a cov_min or valid_min that is not finite and > 0
+ * return ASR_ERR_INVALID_ARG before any launch.  With out_median, n above asr_realign_select_max_copies() returns
+ * ASR_ERR_UNSUPPORTED (the message names the cap) and nothing is launched: the median keeps a pixel's n values in LDS like
+ * asr_realign_select_f32.  Without out_median any n is accepted and no LDS is used. */
+int asr_realign_covered_f32(const float* y, const float* wgt, int wgt_shared, float* out_mean, float* out_median,
+                            float* out_cov, float cov_min, float valid_min, const float* trans_tf, const float* rot_tf,
+                            int batch, int n, int H, int W, int h, int w, asr_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * Output processing, thresholding, IoU
  * ------------------------------------------------------------------------------------------ */

@@ -29,7 +29,9 @@ def main():
     ap.add_argument("--out", default=None, help="output folder (default: data/superres_root/superres_output); when given, "
                     "the masks of --extra_sr_types are written there as PNGs")
     ap.add_argument("--extra_sr_types", default="", help="comma-separated one-pass robust fusions to score after the "
-                    "reference's six means: median, trimmed_mean")
+                    "reference's six means: median, trimmed_mean, covered_mean, covered_median")
+    ap.add_argument("--cover", choices=["frame", "validity"], default="frame", help="what the covered fusions count as "
+                    "seen: the output frame only, or also the part of each copy that came from inside the image")
     ap.add_argument("--trim", type=float, default=0.1, help="fraction of the copies the trimmed mean drops at each end")
     args = ap.parse_args()
     extra = tuple(t for t in args.extra_sr_types.split(",") if t)
@@ -48,7 +50,8 @@ def main():
                               decay_rate=HYPER["decay_rate"])
     sr = Superresolution(lambda_df=HYPER["lambda_df"], lambda_tv=HYPER["lambda_tv"], lambda_L2=HYPER["lambda_L2"],
                          lambda_L1=HYPER["lambda_L1"], num_iter=HYPER["num_iter"], num_aug=args.num_aug,
-                         optimizer=optimizer_obj, feature_size=(args.feature_size, args.feature_size), trim=args.trim)
+                         optimizer=optimizer_obj, feature_size=(args.feature_size, args.feature_size), trim=args.trim,
+                         cover=args.cover)
     paths = interchange_files(args.data)[:args.num_samples]
     res = evaluate_precomputed(sr, paths, args.gt, args.standard, num_aug=args.num_aug, class_id=args.class_id,
                                th_factor=args.th_factor, img_size=IMG_SIZE, out_dir=out_dir, rank=rank, world=world,
