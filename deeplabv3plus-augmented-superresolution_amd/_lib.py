@@ -102,6 +102,10 @@ SIGNATURES = {
     "asr_boundary_dist2_u16": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "asr_band_class_counts_i32": (_i, [_vp, _vp, _vp, _ip, _vp, _i64, _i, _i, _i, _i, _vp]),
     "asr_confusion_counts_i32": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp]),
+    "asr_guided_state_bytes": (_sz, [_i, _i]),
+    "asr_guided_workspace_bytes": (_sz, [_i, _i, _i]),
+    "asr_guided_prepare_f32": (_i, [_vp, _vp, _i, _i, _i, _fl, _vp]),
+    "asr_guided_apply_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "asr_pwconv_packed_floats": (_sz, [_i, _i]),
     "asr_pwconv_pack_weights_f32": (_i, [_vp, _vp, _i, _i, _vp]),
     "asr_pwconv_mfma_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),

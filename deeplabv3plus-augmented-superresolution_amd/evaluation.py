@@ -292,7 +292,8 @@ def dataset_miou(counts):
 
 def evaluate_labelmaps(path, image_paths, gt_paths, class_ids=tuple(range(1, 21)), num_aug=100, angle_max=0.3, shift_max=30,
                        img_size=(512, 512), rank=0, world=1, seed=1234, sr_types=("aug", "max", "mean"), prune=True,
-                       save_dir=None, band_widths=None, band_ignore_label=255, confusion_labels=None, th_factors=None):
+                       save_dir=None, band_widths=None, band_ignore_label=255, confusion_labels=None, th_factors=None,
+                       guide=None):
     """One fused label map per image and SR type (HotPath.run_image_labels) and its score.  Returns (rows, counts) on every
     rank: rows [images, 4] per-image Mean_IOU in LABELMAP_KEYS order (the reference's per-image-then-mean convention; NaN for
     an SR type that was not asked for), counts [4, 3, 256] int64 summed over the images (dataset_miou, label_ious).
@@ -318,7 +319,10 @@ def evaluate_labelmaps(path, image_paths, gt_paths, class_ids=tuple(range(1, 21)
     forward pass or solve) and the return value ends in two more entries: sweep_rows [images, 3, T] per-image Mean_IOU and
     sweep_counts [3, T, 3, 256] int64 summed over the images, both in the order aug / max / mean and NaN / zero for an SR
     type that was not asked for (write_labelmap_threshold_csv).  They travel in the same all-gather.  The whole return value is
-    (rows, counts[, band_rows, band_counts][, confusion][, sweep_rows, sweep_counts])."""
+    (rows, counts[, band_rows, band_counts][, confusion][, sweep_rows, sweep_counts]).
+
+    guide ((radius, eps)): every SR score map is refined with the guided filter against its image before the fusion
+    (run_image_labels' guide; img_size must be the SR output size).  The return value keeps its form."""
     class_ids, params, mine = _class_set_run(class_ids, image_paths, gt_paths, rank, world, num_aug=num_aug,
                                              angle_max=angle_max, shift_max=shift_max, seed=seed)
     n_img = len(image_paths)
@@ -341,6 +345,8 @@ def evaluate_labelmaps(path, image_paths, gt_paths, class_ids=tuple(range(1, 21)
             extra["confusion_labels"] = n_conf
         if n_t:
             extra["th_factors"] = factors
+        if guide is not None:
+            extra["guide"] = guide
         res = path.run_image_labels(image, angles, shifts, class_ids, gt_dev=gt, sr_types=sr_types, prune=prune,
                                     adam_starts={c: int(starts[g, k]) for k, c in enumerate(class_ids)}, **extra)
         mious.append([res["Mean_IOU"].get(key, np.nan) for key in LABELMAP_KEYS])

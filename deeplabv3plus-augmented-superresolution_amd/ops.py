@@ -721,6 +721,80 @@ def standard_labels(logits0, out_hw, class_ids, out=None):
     return out
 
 
+# ---------------------------------------------------------------------------------------------
+# guided filter: score planes refined against the image (asr_guided_prepare_f32 / asr_guided_apply_f32)
+# ---------------------------------------------------------------------------------------------
+MAX_GUIDED_RADIUS = 32
+
+
+def check_guided(radius, eps):
+    """(radius, eps) of a guided filter as (int, float32-rounded float): 0 <= radius <= MAX_GUIDED_RADIUS, eps finite and > 0."""
+    if isinstance(radius, bool) or int(radius) != radius:
+        raise ValueError(f"guided filter: the radius must be an integer, got {radius!r}")
+    radius = int(radius)
+    if not 0 <= radius <= MAX_GUIDED_RADIUS:
+        raise ValueError(f"guided filter: radius {radius} outside 0..{MAX_GUIDED_RADIUS}")
+    eps = float(np.float32(eps))
+    if not (np.isfinite(eps) and eps > 0.0):
+        raise ValueError(f"guided filter: eps must be finite and > 0, got {eps!r}")
+    return radius, eps
+
+
+class GuidedState:
+    """What asr_guided_prepare_f32 leaves for one guide: the state tensor with the H, W, radius (and eps) it belongs to."""
+    __slots__ = ("tensor", "H", "W", "radius", "eps")
+
+    def __init__(self, tensor, H, W, radius, eps):
+        self.tensor, self.H, self.W, self.radius, self.eps = tensor, H, W, radius, eps
+
+
+def _check_guide(guide, name):
+    if not isinstance(guide, torch.Tensor) or guide.dim() != 3 or guide.shape[2] != 3 or guide.shape[0] < 1 or guide.shape[1] < 1:
+        shape = tuple(guide.shape) if isinstance(guide, torch.Tensor) else type(guide)
+        raise ValueError(f"{name}: the guide must be an [H, W, 3] tensor, got {shape}")
+    return int(guide.shape[0]), int(guide.shape[1])
+
+
+def guided_prepare(guide, radius, eps):
+    """guide [H, W, 3] float32 -> GuidedState: the guide-only pass of the guided filter (window means of the guide and the
+    factorised 3x3 covariances), run once per image and shared by every plane filtered against it."""
+    H, W = _check_guide(guide, "guided_prepare")
+    radius, eps = check_guided(radius, eps)
+    lib = _lib.load()
+    state = torch.empty(lib.asr_guided_state_bytes(H, W) // 4, dtype=f32, device=guide.device)
+    call("asr_guided_prepare_f32", ptr(guide), ptr(state), H, W, radius, eps, stream_ptr())
+    return GuidedState(state, H, W, radius, eps)
+
+
+def guided_apply(state, guide, p, out=None):
+    """p [H, W] or [P, H, W] float32 -> q of the same shape: the guided filter of include/asr_hip.h with the guide that
+    `state` was prepared from.  out may be p itself (in place).  The workspace (16 bytes per pixel and plane) comes from
+    torch's caching allocator, which hands the same block back for the same shape on the same stream."""
+    if not isinstance(state, GuidedState):
+        raise ValueError(f"guided_apply: state must come from guided_prepare, got {type(state)}")
+    H, W = _check_guide(guide, "guided_apply")
+    if (H, W) != (state.H, state.W):
+        raise ValueError(f"guided_apply: the state was prepared for {state.H} x {state.W}, the guide is {H} x {W}")
+    if not isinstance(p, torch.Tensor) or p.dim() not in (2, 3) or tuple(p.shape[-2:]) != (H, W) or p.shape[0] < 1:
+        shape = tuple(p.shape) if isinstance(p, torch.Tensor) else type(p)
+        raise ValueError(f"guided_apply: p must be [{H}, {W}] or [P, {H}, {W}], got {shape}")
+    planes = 1 if p.dim() == 2 else int(p.shape[0])
+    if out is None:
+        out = torch.empty_like(p)
+    elif tuple(out.shape) != tuple(p.shape):
+        raise ValueError(f"guided_apply: out must be {tuple(p.shape)}, got {tuple(out.shape)}")
+    lib = _lib.load()
+    ws = torch.empty(lib.asr_guided_workspace_bytes(planes, H, W) // 4, dtype=f32, device=p.device)
+    call("asr_guided_apply_f32", ptr(state.tensor), ptr(guide), ptr(p), ptr(out), ptr(ws), planes, H, W, state.radius,
+         stream_ptr())
+    return out
+
+
+def guided_filter(guide, p, radius=8, eps=1e-3, out=None):
+    """guided_apply(guided_prepare(guide, radius, eps), guide, p, out): one-shot use."""
+    return guided_apply(guided_prepare(guide, radius, eps), guide, p, out=out)
+
+
 MAX_SWEEP_FACTORS = 256
 
 

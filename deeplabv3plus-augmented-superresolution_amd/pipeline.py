@@ -291,7 +291,7 @@ class HotPath:
     # ---- label maps: the classes of an image fused into one label map per SR type, and its Mean_IOU -----------------------
     def run_image_labels(self, image_dev, angles, shifts, class_ids=range(1, 21), gt_dev=None, adam_starts=None,
                          sr_types=("aug", "max", "mean"), want_standard=True, prune=True, profile=None, keep_scores=False,
-                         band_widths=None, band_ignore_label=255, confusion_labels=None, th_factors=None):
+                         band_widths=None, band_ignore_label=255, confusion_labels=None, th_factors=None, guide=None):
         """One label map per SR type from one forward pass: stage 1 and the solves are run_image_classes's; stage 2 ends in the
         fusion kernel (ops.fuse_labels) instead of K thresholds.  class_ids: K <= 32 distinct ids, none 0 (the label of "no
         class").  At each pixel the label is the class whose single-class mask is set there and whose SR output is greatest
@@ -330,8 +330,23 @@ class HotPath:
         for (the standard map does not depend on the factor).  One sweep call per SR type (ops.fuse_labels_sweep_counts) right
         after its fusion, on the same score tensors, and the same single copy to the host as "counts"; with no class left
         after pruning every factor's counts are the zero map's.  With th_factors=None nothing else is launched and nothing
-        else returned."""
+        else returned.
+
+        guide ((radius, eps); image_dev must be [H, W, 3] at the SR output size): the guided filter of include/asr_hip.h with
+        the image itself as the guide moves each score map's boundary onto the image's edges.  The guide-only pass
+        (ops.guided_prepare) runs once per image inside the timed SR stage; each SR type's scores (and in slice_max its max
+        maps' scores) are refined in place (ops.guided_apply) before the fusion, the sweep counts and keep_scores see them.
+        With guide=None nothing else is launched and every result is what it was."""
         ids = [int(c) for c in class_ids]
+        if guide is not None:
+            try:
+                g_radius, g_eps = guide
+            except (TypeError, ValueError):
+                raise ValueError(f"guide must be (radius, eps), got {guide!r}") from None
+            g_radius, g_eps = ops.check_guided(g_radius, g_eps)
+            if image_dev.dim() != 3 or tuple(image_dev.shape) != tuple(self.sr.output_size) + (3,):
+                raise ValueError(f"guide needs the image as [H, W, 3] at the SR output size {tuple(self.sr.output_size)}, got "
+                                 f"{tuple(image_dev.shape)}")
         factors = self._check_th_factors(th_factors, gt_dev) if th_factors is not None else None
         bands = ops.check_band_widths(band_widths) if band_widths is not None else None
         n_conf = ops.check_confusion_labels(confusion_labels) if confusion_labels is not None else 0
@@ -375,10 +390,18 @@ class HotPath:
             f_dev = ops.to_device(factors, device=image_dev.device) if factors is not None and kept and sr_types else None
             if tally is not None and want_standard:
                 tally.counts[0] = ops.class_counts(gt, maps[0])[0]
+            g_state = None
+            if guide is not None and kept and sr_types:
+                g_image = image_dev.to(torch.float32).contiguous()
+                g_state = ops.guided_prepare(g_image, g_radius, g_eps)
             if kept:
                 for t, tgt, tmax in self._classes_scores(y, ymax, angles, self._sr_frame(image_dev, shifts),
                                                          [starts[k] for k in kept], sr_types):
                     j = keys.index(t)
+                    if g_state is not None:
+                        ops.guided_apply(g_state, g_image, tgt, out=tgt)
+                        if tmax is not None:
+                            ops.guided_apply(g_state, g_image, tmax, out=tmax)
                     _, c = ops.fuse_labels(tgt, solved, th_factor=self.th_factor, max_scores=tmax, truth=gt, out=maps[j],
                                            classes=classes)
                     if c is not None:

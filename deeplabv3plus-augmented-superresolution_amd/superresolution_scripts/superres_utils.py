@@ -124,6 +124,29 @@ def threshold_image(image, th_value, th_factor=.15, th_mask=None):
     return out if was_tensor else out.cpu().numpy()
 
 
+def guided_refine(image, guide, radius=8, eps=1e-3):
+    """The guided filter of include/asr_hip.h on a score map: ``image`` [H, W], [H, W, 1] or [P, H, W] float32 refined against
+    the colour ``guide`` [H, W, 3] (the RGB image at the score map's size, values in [0, 1]), same shape out.  It moves the
+    boundary of an upsampled score map onto the image's own edges before the map is thresholded.  Runs on the device
+    (ops.guided_filter); returns a host array for a host ``image``, a device tensor otherwise."""
+    was_tensor = isinstance(image, torch.Tensor)
+    radius, eps = ops.check_guided(radius, eps)
+    g = guide if isinstance(guide, torch.Tensor) else torch.as_tensor(np.asarray(guide, dtype=np.float32))
+    if g.dim() != 3 or g.shape[2] != 3:
+        raise ValueError(f"guided_refine: the guide must be [H, W, 3], got {tuple(g.shape)}")
+    H, W = int(g.shape[0]), int(g.shape[1])
+    img = image if was_tensor else torch.as_tensor(np.asarray(image, dtype=np.float32))
+    shape = tuple(img.shape)
+    if shape not in ((H, W), (H, W, 1)) and not (len(shape) == 3 and shape[0] >= 1 and shape[1:] == (H, W)):
+        raise ValueError(f"guided_refine: image must be [{H}, {W}], [{H}, {W}, 1] or [P, {H}, {W}], got {shape}")
+    dev = _lib.require_gpu()
+    g = g.to(device=dev, dtype=torch.float32).contiguous()
+    img = img.to(device=dev, dtype=torch.float32).contiguous()
+    planes = img.reshape(1, H, W) if shape in ((H, W), (H, W, 1)) else img
+    out = ops.guided_filter(g, planes, radius, eps).reshape(shape)
+    return out if was_tensor else out.cpu().numpy()
+
+
 def threshold_sweep_IoU(true_image, image, class_id, th_factors, include_bg=False):
     """float64 [K]: the single-class IoU of ``image`` thresholded at each factor of ``th_factors`` (threshold_tests.py:113-121),
     i.e. ``[compute_IoU(true_image, threshold_image(image, class_id, th_factor=f), class_id=class_id, include_bg=include_bg)
@@ -253,8 +276,10 @@ EXTRA_SR_TYPES = ("median", "trimmed_mean") + COVERED_SR_TYPES    # the ones bey
 
 def compute_SR(superresolution_obj, class_masks, angles, shifts, filename, dest_folder,
                SR_type="aug", max_masks=[], save_intermediate_output=False, save_final_output=False, class_id=8,
-               th_factor=0.15):
-    """Dispatch aug / mean / max / median / trimmed_mean / covered_mean / covered_median SR, then threshold to a {0, class_id} mask [H,W,1] (host int32)."""
+               th_factor=0.15, guide=None, guide_radius=8, guide_eps=1e-3):
+    """Dispatch aug / mean / max / median / trimmed_mean / covered_mean / covered_median SR, then threshold to a {0, class_id} mask [H,W,1] (host int32).
+    guide ([H, W, 3] at the output size, the RGB image in [0, 1]): the target (and in slice_max the max map's target) goes
+    through guided_refine(., guide, guide_radius, guide_eps) before it is thresholded and saved; None: nothing changes."""
     if SR_type not in SR_TYPES + COVERED_SR_TYPES:
         raise ValueError("SR_type must be one of " + ", ".join(repr(t) for t in SR_TYPES + COVERED_SR_TYPES))
     out_folder = os.path.join(dest_folder, f"{SR_type}_SR")
@@ -276,10 +301,14 @@ def compute_SR(superresolution_obj, class_masks, angles, shifts, filename, dest_
         SR_function = superresolution_obj.trimmed_mean_superresolution
 
     target_image_class, _ = SR_function(class_masks, angles, shifts)
+    if guide is not None:
+        target_image_class = guided_refine(target_image_class, guide, guide_radius, guide_eps)
     target_image_max = None
     # the max mask is super-resolved only when it was produced, i.e. in slice_max OPM
     if max_masks is not None and len(max_masks) == len(class_masks):
         target_image_max, _ = SR_function(max_masks, angles, shifts)
+        if guide is not None:
+            target_image_max = guided_refine(target_image_max, guide, guide_radius, guide_eps)
         th_mask = threshold_image(target_image_class, class_id, th_mask=target_image_max)
     else:
         th_mask = threshold_image(target_image_class, class_id, th_factor=th_factor)

@@ -457,6 +457,45 @@ int asr_band_class_counts_i32(const int32_t* truth, const int32_t* preds, const 
 int asr_confusion_counts_i32(const int32_t* truth, const int32_t* preds, int64_t* counts, int64_t pixels, int num_preds,
                              int num_labels, asr_stream_t stream);
 
+/* --- guided filter: score planes refined against the image before they are thresholded or fused ----------------------------
+ * The guided filter of He, Sun and Tang ("Guided Image Filtering", ECCV 2010 / TPAMI 2013) with a colour guide: one
+ * deterministic pass that moves the boundary of an upsampled score map onto the edges of the image it was computed from.
+ *  - guide I [H, W, 3] f32 (the project's images are in [0, 1]); input p [P, H, W] f32; output q [P, H, W] f32;
+ *  - radius r, an integer, 0 <= r <= 32; eps finite and > 0;
+ *  - the window w_k is the (2r+1)^2 square centred at pixel k, CLIPPED to the image; N_k is the number of pixels it keeps.
+ *    No padding, no reflection.
+ * The rule, for every pixel k and every plane (U = 3x3 identity):
+ *    mu_k = (1/N_k) sum_{j in w_k} I_j                          (3-vector)
+ *    S_k  = (1/N_k) sum_{j in w_k} I_j I_j^T - mu_k mu_k^T      (3x3, symmetric)
+ *    m_k  = (1/N_k) sum_{j in w_k} p_j
+ *    c_k  = (1/N_k) sum_{j in w_k} I_j p_j - mu_k m_k           (3-vector)
+ *    a_k  = (S_k + eps U)^-1 c_k
+ *    b_k  = m_k - a_k^T mu_k
+ *    q_i  = ((1/N_i) sum_{k in w_i} a_k)^T I_i + (1/N_i) sum_{k in w_i} b_k
+ * Everything is f32.  The implementation centres the guide (tile by tile, on a guide value of the tile: covariances do not
+ * change with a shift) and sums each window's terms directly in a fixed order -- never a running sum or a summed-area table,
+ * whose cancellation (S + eps U)^-1 would amplify by up to 1/eps.  No atomics: the same input gives the same bits on every
+ * call, and every plane of a P-plane call is bit for bit what a one-plane call gives for it.
+ *
+ * asr_guided_prepare_f32: the guide-only pass, once per image whatever the number of planes.  state receives
+ * asr_guided_state_bytes(H, W) = 9 * 4 * H * W bytes: per pixel the window mean of the (centred) guide and the six numbers
+ * of the factorisation S_k + eps U = L diag(d) L^T (l10, l20, l21, 1/d0, 1/d1, 1/d2), from which a_k is two triangular
+ * solves; its layout is private to the library and belongs to this (H, W, r, eps) and this guide.
+ * asr_guided_apply_f32: p -> q with the state and the guide it was prepared from, and the same H, W, r.  Two launches: window
+ * sums of p and I p give a_k and b_k, 4 floats per pixel and plane, into workspace (asr_guided_workspace_bytes(planes, H, W)
+ * = 16 * planes * H * W bytes, fully rewritten by each call); window means of those give q.  q may alias p.
+ * Null pointers, H or W < 1, planes < 1, r < 0 and an eps that is not finite and > 0 return ASR_ERR_INVALID_ARG; r > 32
+ * returns ASR_ERR_UNSUPPORTED (the message names the cap), as do more than 65535 planes in one call (a plane is a grid
+ * layer).  Refusals happen before any launch and nothing is written.  The two size functions are host arithmetic (no GPU)
+ * and return 0 for a size below 1.
+ * A workgroup owns a 32 x 32 tile and stages it with its r-wide halo in LDS: with R = 32 + 2r, 4 * (4 * R * (R + 1) + 33 * R)
+ * bytes in asr_guided_apply_f32, 43 KiB at r = 8, 158 KiB (one workgroup per CU) at r = 32. */
+size_t asr_guided_state_bytes(int H, int W);
+size_t asr_guided_workspace_bytes(int planes, int H, int W);
+int asr_guided_prepare_f32(const float* guide, void* state, int H, int W, int r, float eps, asr_stream_t stream);
+int asr_guided_apply_f32(const void* state, const float* guide, const float* p, float* q, void* workspace, int planes, int H,
+                         int W, int r, asr_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * DeepLabV3+ (Xception-65, OS16) layers -- model.py.  BatchNorm is folded by the caller.
  * ------------------------------------------------------------------------------------------ */

@@ -25,7 +25,12 @@ out (the VOC protocol) and once with it kept as a label (Mean_IOU's convention).
 label-map mIoU against the threshold factor, from the SR outputs this one run already holds -- no further forward pass or solve
 (include/asr_hip.h at asr_fuse_labels_sweep_counts_f32; not in slice_max mode, where the threshold plays no part).  One CSV row
 per factor (evaluation.write_labelmap_threshold_csv) and the best factor per SR type by dataset mIoU on the console.  Without
-these flags nothing else is computed or written."""
+these flags nothing else is computed or written.
+
+--guide_radius R [--guide_eps E]: every SR score map is refined with the guided filter (include/asr_hip.h, "guided filter";
+window radius R in 0..32, regulariser E, default 1e-3) against its own image before the label fusion, which moves the maps'
+boundaries onto the image's edges; compare the --band_widths curve with and without it.  Off when omitted: every CSV keeps its
+columns either way."""
 import argparse
 import os
 import sys
@@ -67,6 +72,9 @@ parser.add_argument("--th_factors", default=None,
                     help="comma-separated threshold factors (at most 64), e.g. 0.1,0.15,0.2: the label maps' threshold curve too")
 parser.add_argument("--th_sweep", action="store_true", help="the 17 factors 0.10 ... 0.90 of threshold_tests.py as --th_factors")
 parser.add_argument("--th_sweep_out", default=None, help="CSV file for the threshold curve (default: <--out stem>_thresholds.csv)")
+parser.add_argument("--guide_radius", type=int, default=None,
+                    help="refine the SR score maps with the guided filter of this window radius (0..32) against the image")
+parser.add_argument("--guide_eps", type=float, default=None, help="the guided filter's regulariser (default 1e-3)")
 parser.add_argument("--no_prune", action="store_true", help="solve every class, also those that win no pixel (same results)")
 
 
@@ -102,6 +110,15 @@ def main():
         parser.error("--th_factors holds 1..64 factors")
     if factors is not None and args.mode == "slice_max":
         parser.error("--th_factors / --th_sweep: in slice_max mode the threshold plays no part, there is nothing to sweep")
+    if args.guide_eps is not None and args.guide_radius is None:
+        parser.error("--guide_eps needs --guide_radius")
+    guide = None
+    if args.guide_radius is not None:
+        if not 0 <= args.guide_radius <= 32:
+            parser.error("--guide_radius must lie in 0..32")
+        guide = (args.guide_radius, 1e-3 if args.guide_eps is None else args.guide_eps)
+        if not 0.0 < guide[1] < float("inf"):
+            parser.error("--guide_eps must be finite and > 0")
     names = None
     if args.class_names:
         with open(args.class_names) as fh:
@@ -126,7 +143,8 @@ def main():
                              shift_max=args.shift_max, img_size=IMG_SIZE, rank=rank, world=world, seed=SEED,
                              prune=not args.no_prune, save_dir=args.save_dir, band_widths=bands,
                              confusion_labels=args.confusion_labels if args.confusion_out else None,
-                             **(dict(th_factors=factors) if factors is not None else {}))
+                             **(dict(th_factors=factors) if factors is not None else {}),
+                             **(dict(guide=guide) if guide is not None else {}))
     rows, counts = out[:2]
     confusion = out[4 if bands else 2] if args.confusion_out else None
     if rank == 0:

@@ -127,13 +127,13 @@ def main():
         s = os.path.join(CSRC, src)
         deps = [s] + [os.path.join(CSRC, h) for h in B.HEADERS] + [os.path.abspath(__file__)]
         if B._stale(o, deps):
-            extra = dict(B.SOURCES)[src]
+            extra = dict(B.ALL_SOURCES)[src]
             if src == "sr.hip":        # the sr variants state their own flags (with or without packed-f32)
                 extra = [f for f in extra if f not in B.NO_PK_F32 and f not in FP]
             cmd = [hipcc] + B.COMMON + extra + flags + ["-c", s, "-o", o]
             print(" ".join(cmd), flush=True)
             B._compile(cmd)
-    prod = {os.path.splitext(src)[0]: os.path.join(CSRC, "build", os.path.splitext(src)[0] + ".o") for src, _ in B.SOURCES}
+    prod = {os.path.splitext(src)[0]: os.path.join(CSRC, "build", os.path.splitext(src)[0] + ".o") for src, _ in B.ALL_SOURCES}
     for lib, repl in LIBS.items():
         objs = [os.path.join(OBJ, repl[k] + ".o") if k in repl else o for k, o in prod.items()]
         out = os.path.join(PKG, f"libasr_hz_{lib}.so")

@@ -74,7 +74,7 @@ def build(nop, defines=("-DASR_DIAG_KFWD_WAIT",), tag="pk_wait", before=False, f
          "-output=" + stem + ".hipfb"])
     run([B._hipcc()] + flags + ["-x", "hip", "--cuda-host-only", "-Xclang", "-fcuda-include-gpubinary", "-Xclang", stem + ".hipfb", "-c", src,
          "-o", stem + ".o"])
-    prod = [os.path.join(CSRC, "build", os.path.splitext(s)[0] + ".o") for s, _ in B.SOURCES]
+    prod = [os.path.join(CSRC, "build", os.path.splitext(s)[0] + ".o") for s, _ in B.ALL_SOURCES]
     objs = [stem + ".o" if os.path.basename(o) == "sr.o" else o for o in prod]
     lib = os.path.join(PKG, f"libasr_hz_{tag}_fixsel.so" if fix_opsel else f"libasr_hz_{tag}_nop{nop}.so")
     subprocess.check_call([B._hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib] + objs)
