@@ -601,7 +601,11 @@ int asr_sepconv_fused_f16x3(const float* x, const float* w_dw, const float* bias
 /* DepthwiseConv2D 3x3 (+ ZeroPadding2D, folded BN, ReLU before and/or after): the depthwise half
  * of _SepConv_BN, model.py:478-495, and of _inverted_res_block, model.py:442-449 (post_relu = 2: ReLU6).
  * w [3,3,c] with the BN scale folded, bias [c].
- * mode: 0 = auto, 1 = direct (any stride / rate), 2 = register-window streaming ((stride 1, rate 1|2) or (stride 2, rate 1)). */
+ * mode: 0 = auto, 1 = direct (any stride / rate), 2 = register-window streaming ((stride 1, rate 1|2) or (stride 2, rate 1)).
+ * Every output is acc = bias; for (ky, kx) row-major: acc = fma(x, w, acc), whichever kernel runs (a tap outside the image
+ * leaves acc unchanged).  INPUTS MUST BE FINITE, for this entry, asr_dwconv3x3_nhwc_split_f16 and the two fused ASPP entries:
+ * the full-strip kernels multiply a clamped edge value by a zeroed weight, so an infinity (or NaN) in an edge column yields
+ * NaN in the neighbouring outputs where the other kernels, which skip the tap, yield a finite value. */
 int asr_dwconv3x3_nhwc_f32(const float* x, const float* w, const float* bias, float* y, int batch, int h_in,
                            int w_in, int c, int stride, int rate, int pad_top, int pad_left, int h_out, int w_out,
                            int ldx, int ldy, int pre_relu, int post_relu, int mode, asr_stream_t stream);

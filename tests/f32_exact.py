@@ -9,6 +9,9 @@ k1 = 8*kk + 4 + t.  With k0 accumulated before k1 (what tests/test_gpu_exact_f32
 establishes on the device) the chain order inside a tile is 0,4,1,5,2,6,3,7, 8,12,9,13, ...; the zero-padded k of the
 last tile are fmas with a zero product.  The epilogue is ((acc + bias) -> ReLU -> ReLU6) + residual, one f32 rounding per
 add (gemm_common.h, pw_epilogue).
+
+The depthwise kernels (csrc/dwconv.hip) are one nine-step fmaf chain from the bias per output, taps in (ky, kx) order:
+dwconv_exact; split_f16_exact restates the hi / lo split of their split-f16 outputs (tests/dw_shapes.py builds on both).
 """
 from __future__ import annotations
 
@@ -134,3 +137,57 @@ def scaled(weights, s):
     input also scaled by s, every activation of a ReLU network scales by s (BN folding: b - m * scale commutes)."""
     s = np.float32(s)
     return {k: (np.asarray(v, np.float32) * s if k.endswith(BIAS_LIKE) else v) for k, v in weights.items()}
+
+
+# ---- depthwise 3x3 (csrc/dwconv.hip): one fmaf chain per output, from the bias, over the taps in (ky, kx) order -------------
+TAPS = tuple((ky, kx) for ky in range(3) for kx in range(3))
+
+
+def _tap_range(n_out, n_in, stride, pad, off):
+    """The outputs o in [0, n_out) whose tap o * stride - pad + off lies inside [0, n_in): (first o, one past the last o)."""
+    lo = max(0, -(-(pad - off) // stride))
+    hi = min(n_out, (n_in - 1 + pad - off) // stride + 1)
+    return lo, max(hi, lo)
+
+
+def dwconv_exact(x, w, bias, stride, rate, pad_top, pad_left, out_hw, pre_relu=0, post_relu=0, rows=None, taps=TAPS, fma=fmaf):
+    """What every depthwise kernel must return, bit for bit: x [B,H,W,C], w [3,3,C], bias [C] -> [B,h_out,w_out,C] with
+    acc = bias; for (ky, kx) row-major: acc = fmaf(act(x[oy*stride - pad_top + ky*rate, ox*stride - pad_left + kx*rate]), w[ky, kx], acc),
+    a tap outside the image skipped (a zero tap value, or a zero weight on a finite value, leaves acc unchanged as well);
+    act = ReLU if pre_relu; then post_relu 1: max(acc, 0), 2: min(max(acc, 0), 6).
+    rows = (r0, r1): output rows r0 .. r1 - 1 only.  taps / fma: the tap order and the multiply-add, for tests that need a
+    deliberately different chain (fma is called once per tap, in order)."""
+    x = np.asarray(x, np.float32)
+    w = np.asarray(w, np.float32)
+    b, h, wd, c = x.shape
+    ho, wo = out_hw
+    r0, r1 = rows if rows is not None else (0, ho)
+    if pre_relu:
+        x = np.maximum(x, np.float32(0.0))
+    acc = np.broadcast_to(np.asarray(bias, np.float32), (b, r1 - r0, wo, c)).copy()
+    for ky, kx in taps:
+        ya, yb = _tap_range(ho, h, stride, pad_top, ky * rate)
+        ya, yb = max(ya, r0), max(min(yb, r1), max(ya, r0))
+        xa, xb = _tap_range(wo, wd, stride, pad_left, kx * rate)
+        iy0, ix0 = ya * stride - pad_top + ky * rate, xa * stride - pad_left + kx * rate
+        xv = x[:, iy0:iy0 + (yb - ya - 1) * stride + 1:stride, ix0:ix0 + (xb - xa - 1) * stride + 1:stride] if yb > ya and xb > xa \
+            else np.zeros((b, 0, 0, c), np.float32)
+        region = (slice(None), slice(ya - r0, ya - r0 + xv.shape[1]), slice(xa, xa + xv.shape[2]))
+        acc[region] = fma(xv, w[ky, kx], acc[region])
+    if post_relu:
+        acc = np.maximum(acc, np.float32(0.0))
+    if post_relu == 2:
+        acc = np.minimum(acc, np.float32(6.0))
+    return acc
+
+
+F16_MAX = np.float32(65504.0)
+
+
+def split_f16_exact(v):
+    """asr_split_f16 (csrc/asr_common.h) restated: hi = f16(clip(v, +-65504)), lo = f16(clip(v - f32(hi), +-65504)), the
+    subtraction in float32, both conversions round-to-nearest-even with f16 subnormals kept -> (hi, lo) as uint16 bit patterns."""
+    v = np.asarray(v, np.float32)
+    hi = np.clip(v, -F16_MAX, F16_MAX).astype(np.float16)
+    lo = np.clip(v - hi.astype(np.float32), -F16_MAX, F16_MAX).astype(np.float16)
+    return hi.view(np.uint16), lo.view(np.uint16)
