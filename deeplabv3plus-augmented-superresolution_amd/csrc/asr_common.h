@@ -87,6 +87,16 @@ static inline int asr_class_set(const char* fn, const int* ids, int K, int class
     return ASR_OK;
 }
 
+// The set {class_id} of a single-class entry point, which has checked 0 <= class_id < classes itself: what asr_class_set
+// makes of K = 1, so that the call runs the class-set kernel on the very arguments of a one-id class-set call.
+static inline AsrClassSet asr_one_class(int class_id) {
+    AsrClassSet set;
+    set.n = 1;
+    set.id[0] = class_id;
+    for (int k = 1; k < ASR_MAX_CLASS_SET; ++k) set.id[k] = -1;
+    return set;
+}
+
 // The set of a label map (asr_fuse_labels_f32, asr_standard_labels_i32): a class set without 0, the label of "no class".
 static inline int asr_label_set(const char* fn, const int* ids, int K, int classes, AsrClassSet* set) {
     const int rc = asr_class_set(fn, ids, K, classes, set);

@@ -523,17 +523,8 @@ __device__ __forceinline__ int upsampled_argmax(const float* __restrict__ logits
     return arg;
 }
 
-__global__ __launch_bounds__(256) void standard_mask_kernel(const float* __restrict__ logits, int* __restrict__ out, int h_in,
-                                                            int w_in, int classes, int h_out, int w_out, float scale_y,
-                                                            float scale_x, int class_id) {
-    const int ox = blockIdx.x * 256 + threadIdx.x, oy = blockIdx.y;
-    if (ox >= w_out) return;
-    const int arg = upsampled_argmax(logits, h_in, w_in, classes, scale_y, scale_x, ox, oy);
-    out[(long long)oy * w_out + ox] = (arg == class_id) ? class_id : 0;
-}
-
-// The same for a class set (asr_standard_mask_classes_i32): one upsample + argmax per output pixel, K masks
-// [K, h_out, w_out].  Kept in this unit so that the interpolation compiles exactly as standard_mask_kernel's does.
+// For a class set (asr_standard_mask_classes_i32; asr_standard_mask_i32 is its set of one): one upsample + argmax per output
+// pixel, K masks [K, h_out, w_out].
 __global__ __launch_bounds__(256) void standard_mask_classes_kernel(const float* __restrict__ logits, int* __restrict__ out,
                                                                     int h_in, int w_in, int classes, int h_out, int w_out,
                                                                     float scale_y, float scale_x, AsrClassSet set) {
@@ -666,8 +657,8 @@ extern "C" int asr_standard_mask_i32(const float* logits, int32_t* mask, int h_i
                     class_id < classes,
                 "asr_standard_mask_i32: bad shape / class");
     const float sy = (float)h_in / (float)h_out, sx = (float)w_in / (float)w_out;
-    hipLaunchKernelGGL(standard_mask_kernel, dim3((unsigned)asr_cdiv(w_out, 256), (unsigned)h_out), dim3(256), 0, asr_stream(stream),
-                       logits, mask, h_in, w_in, classes, h_out, w_out, sy, sx, class_id);
+    hipLaunchKernelGGL(standard_mask_classes_kernel, dim3((unsigned)asr_cdiv(w_out, 256), (unsigned)h_out), dim3(256), 0,
+                       asr_stream(stream), logits, mask, h_in, w_in, classes, h_out, w_out, sy, sx, asr_one_class(class_id));
     ASR_LAUNCH_CHECK();
     return ASR_OK;
 }

@@ -93,59 +93,13 @@ __global__ __launch_bounds__(256) void argmax_kernel(const float* __restrict__ l
     }
 }
 
-__global__ __launch_bounds__(256) void opm_argmax_kernel(const float* __restrict__ logits, float* __restrict__ out,
-                                                         int64_t pixels, int classes, int class_id) {
-    __shared__ float tile[256 * kMaxStageClasses];
-    for (int64_t first = (int64_t)blockIdx.x * 256; first < pixels; first += (int64_t)gridDim.x * 256) {
-        const float* row = stage_rows(logits, first, pixels, classes, tile);
-        const int64_t p = first + threadIdx.x;
-        if (p < pixels) out[p] = (argmax_row(row, classes) == class_id) ? (float)class_id : 0.0f;
-        __syncthreads();
-    }
-}
-
-// opm_argmax_kernel's walk straight from global memory, for class counts beyond the LDS tile
-__global__ __launch_bounds__(256) void opm_argmax_direct_kernel(const float* __restrict__ logits, float* __restrict__ out,
-                                                                int64_t pixels, int classes, int class_id) {
-    for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < pixels; p += (int64_t)gridDim.x * 256)
-        out[p] = (argmax_row(logits + p * classes, classes) == class_id) ? (float)class_id : 0.0f;
-}
-
-__global__ __launch_bounds__(256) void opm_slice_max_kernel(const float* __restrict__ logits, float* __restrict__ cls,
-                                                            float* __restrict__ mx, int64_t pixels, int classes,
-                                                            int class_id) {
-    for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < pixels; p += (int64_t)gridDim.x * 256) {
-        const float* row = logits + p * classes;
-        float best = -INFINITY;
-        for (int c = 0; c < classes; ++c)
-            if (c != class_id) best = fmaxf(best, row[c]);
-        cls[p] = row[class_id];
-        mx[p] = best;
-    }
-}
-
-// slice OPM: class logit min-max normalised by the per-copy global min/max (seg_minmax[copy])
-__global__ __launch_bounds__(256) void opm_slice_kernel(const float* __restrict__ logits, float* __restrict__ out,
-                                                        const float* __restrict__ seg_minmax, int64_t pixels_per_copy,
-                                                        int classes, int class_id, float new_min, float new_max) {
-    const int copy = blockIdx.y;
-    const float mn = seg_minmax[copy * 2 + 0], mxv = seg_minmax[copy * 2 + 1];
-    const float den = ((mxv - mn) != 0.0f) ? (mxv - mn) : 1.0f;
-    const float span = new_max - new_min;
-    const float* base = logits + (int64_t)copy * pixels_per_copy * classes;
-    float* o = out + (int64_t)copy * pixels_per_copy;
-    for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < pixels_per_copy; p += (int64_t)gridDim.x * 256) {
-        const float num = (base[p * classes + class_id] - mn) * span;
-        o[p] = new_min + num / den;
-    }
-}
-
-// ---- OPM of a class set (asr_opm_classes_f32) ---------------------------------------------------------------------
+// ---- OPM of a class set (asr_opm_classes_f32; asr_opm_argmax_f32 / _slice_f32 / _slice_max_f32 are its sets of one) ------
 // Each pixel's row is read once -- through LDS like argmax_kernel when it fits (STAGED), else straight from global memory --
-// and every class of the set gets the statements of its single-class kernel on it: argmax_row once per pixel, then one
-// compare per class (opm_argmax_kernel); opm_slice_kernel's per-copy constants and expression (SLICE, one copy per grid
-// row); opm_slice_max_kernel's fold over the other classes, in the same order, once per class (SLICE_MAX).  Plane k of the
-// output lies class_stride floats after plane k-1.  argmax / slice_max launch one "copy" of all pixels.
+// and every class of the set gets the same statements on it: argmax_row once per pixel, then one compare per class
+// (ARGMAX: the id where it wins, else 0); the class logit min-max normalised by its copy's global minimum / maximum
+// seg_minmax[copy] (SLICE, one copy per grid row); the class logit and the maximum over the other classes, folded in class
+// order, once per class (SLICE_MAX).  Plane k of the output lies class_stride floats after plane k-1.  argmax / slice_max
+// launch one "copy" of all pixels.
 template <int MODE, bool STAGED>
 __global__ __launch_bounds__(256) void opm_classes_kernel(const float* __restrict__ logits, float* __restrict__ cls,
                                                           float* __restrict__ mx, const float* __restrict__ seg_minmax,
@@ -877,28 +831,55 @@ extern "C" int asr_argmax_i32(const float* logits, int32_t* out, int64_t pixels,
     return ASR_OK;
 }
 
+// Every OPM entry point launches here, after its own argument checks: the single-class ones with a set of one, so that they
+// and asr_opm_classes_f32 with K = 1 cannot run different kernels.  argmax / slice_max take all copies * pixels_per_copy pixels
+// as one copy; slice computes the per-copy extrema first (once for all classes of the set).
+static int opm_launch(int mode, const float* logits, const AsrClassSet& set, float* class_masks, float* max_masks, float* minmax_ws,
+                      int copies, int64_t pixels_per_copy, int classes, int64_t class_stride, float new_min, float new_max,
+                      asr_stream_t stream) {
+    hipStream_t s = asr_stream(stream);
+    const int64_t pixels = (int64_t)copies * pixels_per_copy;
+    // A slice of one class reads one float per row: on logits [16, 128, 128, 21] staging whole rows through LDS takes 8.68 us, the
+    // walk from global memory 4.20 us (measured, DESIGN.md "Class sets"), so a set of one takes <SLICE, false>.  Chosen here, so
+    // that asr_opm_slice_f32 and a one-id asr_opm_classes_f32 launch the same instantiation.
+    const bool staged = classes <= kMaxStageClasses && !(mode == ASR_OPM_SLICE && set.n == 1);
+#define ASR_OPM_CLASSES_LAUNCH(M, grid, per, ws)                                                                              \
+    do {                                                                                                                    \
+        if (staged)                                                                                                         \
+            hipLaunchKernelGGL((opm_classes_kernel<M, true>), grid, dim3(256), 0, s, logits, class_masks, max_masks, ws, per, \
+                               classes, class_stride, set, new_min, new_max);                                               \
+        else                                                                                                                \
+            hipLaunchKernelGGL((opm_classes_kernel<M, false>), grid, dim3(256), 0, s, logits, class_masks, max_masks, ws,     \
+                               per, classes, class_stride, set, new_min, new_max);                                          \
+    } while (0)
+    if (mode == ASR_OPM_ARGMAX) {
+        ASR_OPM_CLASSES_LAUNCH(ASR_OPM_ARGMAX, dim3(stream_grid(pixels)), pixels, nullptr);
+    } else if (mode == ASR_OPM_SLICE_MAX) {
+        ASR_OPM_CLASSES_LAUNCH(ASR_OPM_SLICE_MAX, dim3(stream_grid(pixels)), pixels, nullptr);
+    } else {
+        const int rc = asr_minmax_f32(logits, minmax_ws, pixels_per_copy * classes, copies, stream);
+        if (rc != ASR_OK) return rc;
+        ASR_OPM_CLASSES_LAUNCH(ASR_OPM_SLICE, dim3(stream_grid(pixels_per_copy), copies), pixels_per_copy, minmax_ws);
+    }
+#undef ASR_OPM_CLASSES_LAUNCH
+    ASR_LAUNCH_CHECK();
+    return ASR_OK;
+}
+
 extern "C" int asr_opm_argmax_f32(const float* logits, float* class_mask, int64_t pixels, int classes, int class_id,
                                   asr_stream_t stream) {
     ASR_REQUIRE(logits && class_mask, "asr_opm_argmax_f32: null pointer");
     ASR_REQUIRE(pixels > 0 && classes > 0 && class_id >= 0 && class_id < classes, "asr_opm_argmax_f32: bad shape/class");
-    if (classes <= kMaxStageClasses)
-        hipLaunchKernelGGL(opm_argmax_kernel, dim3(stream_grid(pixels)), dim3(256), 0, asr_stream(stream), logits, class_mask,
-                           pixels, classes, class_id);
-    else
-        hipLaunchKernelGGL(opm_argmax_direct_kernel, dim3(stream_grid(pixels)), dim3(256), 0, asr_stream(stream), logits,
-                           class_mask, pixels, classes, class_id);
-    ASR_LAUNCH_CHECK();
-    return ASR_OK;
+    return opm_launch(ASR_OPM_ARGMAX, logits, asr_one_class(class_id), class_mask, nullptr, nullptr, 1, pixels, classes, pixels, 0.0f,
+                      0.0f, stream);
 }
 
 extern "C" int asr_opm_slice_max_f32(const float* logits, float* class_mask, float* max_mask, int64_t pixels, int classes,
                                      int class_id, asr_stream_t stream) {
     ASR_REQUIRE(logits && class_mask && max_mask, "asr_opm_slice_max_f32: null pointer");
     ASR_REQUIRE(pixels > 0 && classes > 1 && class_id >= 0 && class_id < classes, "asr_opm_slice_max_f32: bad shape/class");
-    hipLaunchKernelGGL(opm_slice_max_kernel, dim3(stream_grid(pixels)), dim3(256), 0, asr_stream(stream), logits,
-                       class_mask, max_mask, pixels, classes, class_id);
-    ASR_LAUNCH_CHECK();
-    return ASR_OK;
+    return opm_launch(ASR_OPM_SLICE_MAX, logits, asr_one_class(class_id), class_mask, max_mask, nullptr, 1, pixels, classes, pixels,
+                      0.0f, 0.0f, stream);
 }
 
 extern "C" int asr_opm_slice_f32(const float* logits, float* class_mask, float* minmax_ws, int copies,
@@ -907,12 +888,8 @@ extern "C" int asr_opm_slice_f32(const float* logits, float* class_mask, float* 
     ASR_REQUIRE(logits && class_mask && minmax_ws, "asr_opm_slice_f32: null pointer");
     ASR_REQUIRE(copies > 0 && copies <= 65535 && pixels_per_copy > 0 && classes > 0 && class_id >= 0 && class_id < classes,
                 "asr_opm_slice_f32: bad shape/class");
-    int rc = asr_minmax_f32(logits, minmax_ws, pixels_per_copy * classes, copies, stream);
-    if (rc != ASR_OK) return rc;
-    hipLaunchKernelGGL(opm_slice_kernel, dim3(stream_grid(pixels_per_copy), copies), dim3(256), 0, asr_stream(stream),
-                       logits, class_mask, minmax_ws, pixels_per_copy, classes, class_id, new_min, new_max);
-    ASR_LAUNCH_CHECK();
-    return ASR_OK;
+    return opm_launch(ASR_OPM_SLICE, logits, asr_one_class(class_id), class_mask, nullptr, minmax_ws, copies, pixels_per_copy, classes,
+                      (int64_t)copies * pixels_per_copy, new_min, new_max, stream);
 }
 
 extern "C" int asr_threshold_f32(const float* image, const float* th_mask, float* minmax_ws, int32_t* out,
@@ -969,31 +946,11 @@ extern "C" int asr_opm_classes_f32(const float* logits, const int* ids, int K, i
     const int64_t pixels = (int64_t)copies * pixels_per_copy;
     ASR_REQUIRE(K == 1 || class_stride >= pixels, "asr_opm_classes_f32: class_stride %lld < %lld pixels (planes would overlap)",
                 (long long)class_stride, (long long)pixels);
-    hipStream_t s = asr_stream(stream);
-    const bool staged = classes <= kMaxStageClasses;
-#define ASR_OPM_CLASSES_LAUNCH(M, grid, per, ws)                                                                              \
-    do {                                                                                                                    \
-        if (staged)                                                                                                         \
-            hipLaunchKernelGGL((opm_classes_kernel<M, true>), grid, dim3(256), 0, s, logits, class_masks, max_masks, ws, per, \
-                               classes, class_stride, set, new_min, new_max);                                               \
-        else                                                                                                                \
-            hipLaunchKernelGGL((opm_classes_kernel<M, false>), grid, dim3(256), 0, s, logits, class_masks, max_masks, ws,     \
-                               per, classes, class_stride, set, new_min, new_max);                                          \
-    } while (0)
-    if (mode == ASR_OPM_ARGMAX) {
-        ASR_OPM_CLASSES_LAUNCH(ASR_OPM_ARGMAX, dim3(stream_grid(pixels)), pixels, nullptr);
-    } else if (mode == ASR_OPM_SLICE_MAX) {
-        ASR_REQUIRE(max_masks && classes > 1, "asr_opm_classes_f32: slice_max needs max_masks and classes > 1");
-        ASR_OPM_CLASSES_LAUNCH(ASR_OPM_SLICE_MAX, dim3(stream_grid(pixels)), pixels, nullptr);
-    } else {
-        ASR_REQUIRE(minmax_ws, "asr_opm_classes_f32: slice needs minmax_ws");
-        rc = asr_minmax_f32(logits, minmax_ws, pixels_per_copy * classes, copies, stream);     // once for all K classes
-        if (rc != ASR_OK) return rc;
-        ASR_OPM_CLASSES_LAUNCH(ASR_OPM_SLICE, dim3(stream_grid(pixels_per_copy), copies), pixels_per_copy, minmax_ws);
-    }
-#undef ASR_OPM_CLASSES_LAUNCH
-    ASR_LAUNCH_CHECK();
-    return ASR_OK;
+    ASR_REQUIRE(mode != ASR_OPM_SLICE_MAX || (max_masks && classes > 1),
+                "asr_opm_classes_f32: slice_max needs max_masks and classes > 1");
+    ASR_REQUIRE(mode != ASR_OPM_SLICE || minmax_ws, "asr_opm_classes_f32: slice needs minmax_ws");
+    return opm_launch(mode, logits, set, class_masks, max_masks, minmax_ws, copies, pixels_per_copy, classes, class_stride, new_min,
+                      new_max, stream);
 }
 
 extern "C" int asr_threshold_classes_f32(const float* image, const float* th_mask, float* minmax_ws, int32_t* out,

@@ -320,7 +320,10 @@ int asr_standard_mask_i32(const float* logits, int32_t* mask, int h_in, int w_in
 /* --- class sets: several classes of one image from one forward pass ----------------------------------------------
  * Each entry point below takes K distinct class ids `ids` (a HOST int array, read during the call; 1 <= K <=
  * ASR_MAX_CLASS_SET, every id in [0, classes)) and equals, bit for bit, K calls of its single-class counterpart, one per
- * id, while reading its input once.  A bad set (K out of range, an id twice, an id out of range) returns
+ * id, while reading its input once.  For the OPM and the standard mask the single-class entry points (asr_opm_argmax_f32,
+ * asr_opm_slice_f32, asr_opm_slice_max_f32, asr_standard_mask_i32) ARE the K = 1 case: they keep their own argument checks
+ * and messages and then run the class-set kernels on a set of one, so a one-id class-set call and the single-class call
+ * issue the same launches.  A bad set (K out of range, an id twice, an id out of range) returns
  * ASR_ERR_INVALID_ARG before any launch.  Each class keeps the reference's single-class meaning; the label-map entry
  * points further down fuse the classes into one label map. */
 #define ASR_MAX_CLASS_SET 32

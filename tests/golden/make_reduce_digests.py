@@ -1,10 +1,14 @@
 #!/usr/bin/env python3
 """What the single-class output-processing entry points return, as sha256 digests.
 
-    python tests/golden/make_reduce_digests.py [--out FILE]     # on the MI355X; writes tests/golden/reduce_single_class_digests.json
+    python tests/golden/make_reduce_digests.py --out FILE        # on the MI355X; compare FILE with the committed recording
 
-To be recorded while the single-class entry points have kernels of their own: once they run on the class-set kernels, "equals
-K single-class calls" no longer compares two implementations, and these digests hold the bytes the own kernels wrote.
+tests/golden/reduce_single_class_digests.json was recorded at commit 7c09926, the last one at which the single-class entry
+points had kernels of their own (opm_argmax_kernel, opm_argmax_direct_kernel, opm_slice_kernel, opm_slice_max_kernel,
+standard_mask_kernel).  They now run the K = 1 case of the class-set kernels, so "equals K single-class calls" no longer
+compares two implementations, and these digests hold the bytes the own kernels wrote.  NEVER regenerate the committed file
+from newer code: a difference is a finding.  (The tree before 8b4ff57, which gave argmax_kernel and class_activation_kernel
+their templated bodies, reproduces all 288 digests too.)
 Every case is one set of seeded logits (make_logits of tests/test_gpu_class_set_kernels.py: every id wins pixels and ties
 for the maximum, +-0.0 maxima, magnitudes to 1e4) and the
 digests of ops.argmax, ops.class_activation (softmax, sigmoid), and, for the first, a middle and the last class id,
@@ -12,7 +16,7 @@ ops.opm_argmax, ops.opm_slice, ops.opm_slice_max (both outputs) and ops.standard
 
 Class counts: 21 (rows staged through LDS), 32 (the last staged count: it fills the 32 KB tile), 33 (the first count read
 straight from global memory) and 40.  Copy shapes: (3, 37, 41) (several 256-row tiles and a tail), (1, 5, 7) (one partial tile)
-and (1, 16, 16) (exactly one tile).  A replay test imports run_case and compares; no recording is committed yet.
+and (1, 16, 16) (exactly one tile).  tests/test_gpu_reduce_digests.py imports run_case and compares.
 """
 import argparse
 import hashlib
@@ -79,7 +83,7 @@ def run_cases(dev):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=OUT)
+    ap.add_argument("--out", required=True, help="never the committed recording: compare this file with it")
     args = ap.parse_args()
     torch.cuda.set_device(0)
     out = run_cases(torch.device("cuda", 0))

@@ -1,5 +1,7 @@
 """Class sets on the GPU: each *_classes entry point equals, bit for bit, K calls of its single-class counterpart (and the
-OPM equals oracle.augment.opm per class).  Logits are built so that every class of the set really decides pixels: it is the
+OPM equals oracle.augment.opm per class).  The single-class OPM and standard-mask calls run the K = 1 case of the same
+kernels, so for them this checks plane placement and that a class's result does not depend on the rest of the set; the
+independent pin of the K = 1 bytes is tests/golden/reduce_single_class_digests.json (test_gpu_reduce_digests.py).  Logits are built so that every class of the set really decides pixels: it is the
 argmax of at least 1 % of them and ties for the maximum on some, with +-0.0 entries and magnitudes up to 1e4, on pixel
 counts that are not a multiple of 256."""
 import numpy as np

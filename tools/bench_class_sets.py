@@ -9,6 +9,8 @@ HotPath.run_image per class (what a per-class table costs without class sets); -
 Prints one JSON line: ms per image, and the SR-stage time per image (profile["_sr_stage_ms"], from a second, profiled pass).
 --what opm: the output-processing kernels alone, 20 calls each: argmax, slice and slice_max on one configs[1] forward batch of
 logits [16, 128, 128, 21], and the standard mask of its first map [128, 128, 21] at 512 x 512 (single: class 8; classes: K = 4).
+--impl single times the single-class entry points, which run the K = 1 case of the class-set kernels (opm_classes_kernel,
+standard_mask_classes_kernel); with --root on a checkout up to 7c09926 it times the kernels they had of their own.
 Run it under rocprofv3 --kernel-trace --stats for kernel times.
 --root: the tree whose asr_amd is imported (default: this one), so that an older checkout can be measured by the same code.
 """
