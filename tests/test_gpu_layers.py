@@ -172,7 +172,9 @@ def test_conv3x3_direct_same_padding_stride2(dev, f16x3):
 @pytest.mark.parametrize("b,h,w_", [(2, 64, 96), (1, 70, 90), (3, 32, 32)])
 def test_entry_stem_fused_matches_the_two_kernels(dev, b, h, w_):
     """conv1_1 + conv1_2 in one kernel (intermediate in LDS) against the stem kernel followed by the implicit-GEMM conv,
-    and against torch f32: ragged 16 x 16 tiles, map borders (conv1_2's zero padding around the conv1_1 map)."""
+    and against torch f32: ragged 16 x 16 tiles, map borders (conv1_2's zero padding around the conv1_1 map).  These shapes have
+    12, 9 and 3 tiles, one per workgroup; the persistent walk (several tiles per workgroup, the LDS image reused), maps below
+    one tile and ldx / ldy wider than the channels are in tests/test_gpu_layer_shapes.py."""
     from asr_amd import ops
     rng = np.random.default_rng(101)
     x = _rand(rng, b, h, w_, 3)
@@ -197,7 +199,9 @@ def test_entry_stem_fused_matches_the_two_kernels(dev, b, h, w_):
                                                    (128, 128, 1, 8, 14, True), (64, 128, 3, 33, 15, True)])
 def test_sepconv_fused_is_bit_identical_to_the_two_kernels(dev, c, n, b, h, w_, depth_act):
     """depthwise -> LDS (split f16) -> MFMA GEMM in one kernel against asr_dwconv3x3_nhwc_f32 + asr_pwconv_mfma_f16x3:
-    same depthwise arithmetic, same MFMA sequence per accumulator -> bitwise equal; ragged 8 x 14 tiles and image borders."""
+    same depthwise arithmetic, same MFMA sequence per accumulator -> bitwise equal; ragged 8 x 14 tiles and image borders.  These
+    shapes have at most 18 tiles, one per workgroup; runs of several tiles (the cross-tile prefetch, runs across tile-row and
+    image ends, idle workgroups) are in tests/test_gpu_layer_shapes.py."""
     from asr_amd import ops
     rng = np.random.default_rng(303)
     x = ops.to_device(_rand(rng, b, h, w_, c))
