@@ -38,6 +38,7 @@ MAX_CLASS_SET = 32               # ASR_MAX_CLASS_SET
 MAX_BAND_WIDTH, MAX_BAND_WIDTHS, MAX_BAND_PREDS = 64, 16, 8     # asr_band_class_counts_i32's limits
 MAX_CONFUSION_LABELS, MAX_CONFUSION_PREDS = 64, 8               # ASR_CONFUSION_MAX_LABELS / _MAX_PREDS
 CONFUSION_SPAN, CONFUSION_GRID = 1024, 64                        # ASR_CONFUSION_SPAN / _GRID: pixels of a workgroup's trip, row cap
+MAX_BINNED_BINS, MAX_BINNED_PREDS = 16, 8                        # asr_binned_class_counts_f32's limits
 OPM_MODES = {"argmax": 0, "slice": 1, "slice_max": 2}     # ASR_OPM_*
 
 OPT_ADAM, OPT_SGD, OPT_ADAGRAD, OPT_ADADELTA, OPT_ADAMAX = 0, 1, 2, 3, 4
@@ -77,6 +78,7 @@ SIGNATURES = {
     "asr_realign_select_max_copies": (_i, []),
     "asr_realign_select_f32": (_i, [_vp, _vp, _vp, _ip, _ip, _f, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "asr_realign_covered_f32": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _fl, _fl, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "asr_realign_moments_f32": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _fl, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "asr_minmax_f32": (_i, [_vp, _vp, _i64, _i, _vp]),
     "asr_class_activation_f32": (_i, [_vp, _vp, _i64, _i, _i, _vp]),
     "asr_argmax_i32": (_i, [_vp, _vp, _i64, _i, _vp]),
@@ -101,6 +103,7 @@ SIGNATURES = {
     "asr_class_counts_i32": (_i, [_vp, _vp, _vp, _i64, _i, _vp]),
     "asr_boundary_dist2_u16": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "asr_band_class_counts_i32": (_i, [_vp, _vp, _vp, _ip, _vp, _i64, _i, _i, _i, _i, _vp]),
+    "asr_binned_class_counts_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vp]),
     "asr_confusion_counts_i32": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp]),
     "asr_guided_state_bytes": (_sz, [_i, _i]),
     "asr_guided_workspace_bytes": (_sz, [_i, _i, _i]),

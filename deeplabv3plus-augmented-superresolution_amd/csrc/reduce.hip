@@ -721,6 +721,51 @@ __global__ __launch_bounds__(256) void band_finalize_kernel(long long* __restric
     }
 }
 
+// ---- binned counts: class_counts over the pixels whose value u lies at or below each of B edges (asr_binned_class_counts_f32) --
+// Bin j is {p : u[p] <= edges[j]} (one f32 compare: NaN on either side is in no bin), truth != ignore_label; the bins are
+// independent of each other, so the edges need no order and a pixel is added once per bin that holds it, as
+// class_counts_kernel would add it, into row j of a [B][3][256] workgroup histogram (label_hist_add).  The edges come from
+// device memory (a selection that never left the device) and are staged in LDS once per workgroup.  Grid row p scores
+// prediction p; the loop over the bins runs to num_bins for every lane, and a bin that holds no pixel of the wave is skipped
+// wave-uniformly.
+constexpr int kBinnedMaxBins = 16;
+constexpr int kBinnedMaxPreds = 8;
+
+__global__ __launch_bounds__(256) void binned_hist_kernel(const int32_t* __restrict__ truth, const int32_t* __restrict__ preds,
+                                                          const float* __restrict__ u, const float* __restrict__ edges,
+                                                          unsigned long long* __restrict__ counts, int64_t pixels,
+                                                          int ignore_label, int num_bins) {
+    extern __shared__ unsigned int binned_hist[];               // [B][3][256]
+    __shared__ float edge[kBinnedMaxBins];
+    const int bins = num_bins * 768;
+    for (int i = threadIdx.x; i < bins; i += 256) binned_hist[i] = 0u;
+    if (threadIdx.x < num_bins) edge[threadIdx.x] = edges[threadIdx.x];
+    __syncthreads();
+    const int32_t* q = preds + (int64_t)blockIdx.y * pixels;
+    const int lane = threadIdx.x & 63;
+    // the trip count is uniform over the workgroup, so every lane of a wave reaches the ballots and label_hist_add together
+    for (int64_t i0 = (int64_t)blockIdx.x * 256; i0 < pixels; i0 += (int64_t)gridDim.x * 256) {
+        const int64_t i = i0 + threadIdx.x;
+        const bool in = i < pixels;
+        const int tv = in ? truth[i] : -1, pv = in ? q[i] : -1;
+        const float uv = in ? u[i] : 0.0f;
+        const bool live = in && (ignore_label == -1 || tv != ignore_label);
+        const bool t_ok = tv >= 0 && tv < 256, p_ok = pv >= 0 && pv < 256;
+        for (int j = 0; j < num_bins; ++j) {
+            const bool held = live && uv <= edge[j];
+            if (__ballot(held) == 0ull) continue;              // wave-uniform
+            const int base = j * 768;                           // label_hist_add compares keys: the bin goes into the key
+            label_hist_add(binned_hist, (held && t_ok) ? base + tv : -1, lane);
+            label_hist_add(binned_hist, (held && p_ok) ? base + 256 + pv : -1, lane);
+            label_hist_add(binned_hist, (held && t_ok && tv == pv) ? base + 512 + tv : -1, lane);
+        }
+    }
+    __syncthreads();
+    unsigned long long* g = counts + (int64_t)blockIdx.y * bins;
+    for (int b = threadIdx.x; b < bins; b += 256)
+        if (binned_hist[b]) atomicAdd(g + b, (unsigned long long)binned_hist[b]);
+}
+
 // ---- confusion matrix: (truth label, predicted label) pair counts of label maps (asr_confusion_counts_i32) ----------------
 // bin(v) = v for 0 <= v < L, else L ("other").  A pixel is one key bin(t) * (L + 1) + bin(p), added with label_hist_add into a
 // workgroup histogram of (L + 1)^2 bins in LDS (most pixels of a wave are background on background: one popcount add); every
@@ -1185,6 +1230,29 @@ extern "C" int asr_band_class_counts_i32(const int32_t* truth, const int32_t* pr
     ASR_LAUNCH_CHECK();
     hipLaunchKernelGGL(band_finalize_kernel, dim3((unsigned)asr_cdiv((int64_t)num_preds * 768, 256)), dim3(256), 0, s,
                        reinterpret_cast<long long*>(counts), num_preds, set);
+    ASR_LAUNCH_CHECK();
+    return ASR_OK;
+}
+
+extern "C" int asr_binned_class_counts_f32(const int32_t* truth, const int32_t* preds, const float* u, const float* edges,
+                                           int64_t* counts, int64_t pixels, int num_preds, int num_bins, int ignore_label,
+                                           asr_stream_t stream) {
+    ASR_REQUIRE(truth && preds && u && edges && counts, "asr_binned_class_counts_f32: null pointer");
+    ASR_REQUIRE(pixels > 0 && pixels < ((int64_t)1 << 62), "asr_binned_class_counts_f32: bad shape (pixels=%lld)", (long long)pixels);
+    ASR_REQUIRE(num_preds >= 1 && num_preds <= kBinnedMaxPreds, "asr_binned_class_counts_f32: %d predictions (1..%d)", num_preds,
+                kBinnedMaxPreds);
+    ASR_REQUIRE(num_bins >= 1 && num_bins <= kBinnedMaxBins, "asr_binned_class_counts_f32: %d bins (1..%d)", num_bins,
+                kBinnedMaxBins);
+    // a workgroup's bins are 32-bit: with G workgroups in a grid row it sees fewer than pixels / G + 256 pixels, and
+    // G >= pixels / 2^31 keeps that below 2^32 (asr_confusion_counts_i32's argument)
+    int64_t grid = asr_cdiv(pixels, (int64_t)256);
+    grid = grid > 64 ? 64 : grid;
+    const int64_t need = asr_cdiv(pixels, (int64_t)1 << 31);
+    grid = grid < need ? need : grid;
+    hipStream_t s = asr_stream(stream);
+    ASR_HIP_CHECK(hipMemsetAsync(counts, 0, sizeof(int64_t) * 768 * (size_t)num_preds * (size_t)num_bins, s));
+    hipLaunchKernelGGL(binned_hist_kernel, dim3((unsigned)grid, num_preds), dim3(256), sizeof(unsigned int) * 768 * (size_t)num_bins, s,
+                       truth, preds, u, edges, reinterpret_cast<unsigned long long*>(counts), pixels, ignore_label, num_bins);
     ASR_LAUNCH_CHECK();
     return ASR_OK;
 }

@@ -1130,6 +1130,59 @@ __global__ __launch_bounds__(kSelPix) SR_NO_PK_F32 void sr_realign_covered_media
     out_median[o] = (nv > 0) ? r : 0.0f;
 }
 
+// ---- mean, population variance and valid count over the same copies (include/asr_hip.h: the rule) ----------------------
+// The shape of sr_realign_covered_kernel, registers only, for any n: the copies are walked twice, first for the sum and the
+// count of the valid ones (m = sum / nv), then for the squared deviations about that rounded m.  The second walk recomputes
+// every v_i with the same statements (the taps come from the caches), so nothing is parked and n has no cap.  HAS_W = false:
+// no weight plane, every copy is valid and the sum is sr_realign_kernel's own.  An invalid copy adds +0 to a sum that
+// starts at +0, which leaves its bits alone.
+template <bool HAS_W>
+__global__ __launch_bounds__(256) SR_NO_PK_F32 void sr_realign_moments_kernel(
+    const float* __restrict__ y, const float* __restrict__ wgt, float* __restrict__ out_mean, float* __restrict__ out_var,
+    float* __restrict__ out_nv, const float* __restrict__ trans_tf, const float* __restrict__ rot_tf, SrDims d, SrCover cv,
+    float scale_y, float scale_x) {
+    const int X = blockIdx.x * kTileX + threadIdx.x;
+    const int Y = blockIdx.y * kTileY + threadIdx.y;
+    const int b = blockIdx.z;
+    if (X >= d.W || Y >= d.H) return;
+    const int H = d.H, W = d.W, lh = d.h, lw = d.w;
+    const int64_t o = ((int64_t)b * H + Y) * W + X;
+    const int walks = out_var ? 2 : 1;
+    float m = 0.0f, fnv = 0.0f;
+    // ONE textual walk, run once or twice: with a second inlined copy of sr_realign_copy_value the kernel took 192 bytes of
+    // scratch per lane and 114 VGPRs (4 waves per SIMD, 6.8 x the time of one mean walk); this form has none and 64
+#pragma nounroll
+    for (int walk = 0; walk < walks; ++walk) {
+        float acc = 0.0f;
+        int cnt = 0;
+        for (int n = 0; n < d.n; ++n) {
+            const int bn = b * d.n + n;
+            float v;
+            bool valid = true;
+            if (HAS_W) {
+                const float* const src[2] = {y + (int64_t)bn * lh * lw, wgt + (int64_t)bn * cv.wgt_stride};
+                const SrPlanes<2> val = sr_realign_copy_value<2>(src, trans_tf, rot_tf, bn, X, Y, H, W, lh, lw, scale_y, scale_x);
+                v = val.v[0];
+                valid = val.v[1] >= cv.valid_min;
+            } else {
+                v = sr_realign_copy_value(y, trans_tf, rot_tf, bn, X, Y, H, W, lh, lw, scale_y, scale_x);
+            }
+            const float dv = v - m;                            // the first walk has m = +0: dv is v, bit for bit
+            const float term = walk ? dv * dv : dv;            // the product and the add round separately (-ffp-contract=off)
+            acc += valid ? term : 0.0f;
+            cnt += valid ? 1 : 0;
+        }
+        if (walk == 0) {
+            fnv = (float)cnt;
+            m = (cnt > 0) ? acc / fnv : 0.0f;
+            if (out_nv) out_nv[o] = fnv;
+            if (out_mean) out_mean[o] = m;
+        } else {
+            out_var[o] = (fnv > 0.0f) ? acc / fnv : 0.0f;
+        }
+    }
+}
+
 int check_dims(const char* fn, int batch, int n, int H, int W, int h, int w, SrDims* d) {
     ASR_REQUIRE(batch > 0 && n > 0 && H > 0 && W > 0 && h > 0 && w > 0, "%s: bad shape batch=%d n=%d %dx%d <- %dx%d",
                 fn, batch, n, H, W, h, w);
@@ -1503,6 +1556,30 @@ extern "C" int asr_realign_covered_f32(const float* y, const float* wgt, int wgt
         ASR_HIP_CHECK(asr_allow_dynamic_lds(once, reinterpret_cast<const void*>(sr_realign_covered_median_kernel), kSelLdsMax));
     hipLaunchKernelGGL(sr_realign_covered_median_kernel, dim3((unsigned)tiles, 1, (unsigned)batch), dim3(kSelX, kSelY), lds, s,
                        y, wgt, out_mean, out_median, out_cov, trans_tf, rot_tf, d, cv, (int)tiles_x, sy, sx);
+    ASR_LAUNCH_CHECK();
+    return ASR_OK;
+}
+
+extern "C" int asr_realign_moments_f32(const float* y, const float* wgt, int wgt_shared, float* out_mean, float* out_var,
+                                       float* out_nv, float valid_min, const float* trans_tf, const float* rot_tf, int batch,
+                                       int n, int H, int W, int h, int w, asr_stream_t stream) {
+    ASR_REQUIRE(y && trans_tf && rot_tf, "asr_realign_moments_f32: null pointer");
+    ASR_REQUIRE(out_mean || out_var || out_nv, "asr_realign_moments_f32: nothing to compute (out_mean, out_var and out_nv are NULL)");
+    ASR_REQUIRE(batch > 0 && batch <= 65535 && n > 0 && H > 0 && W > 0 && h > 0 && w > 0, "asr_realign_moments_f32: bad shape");
+    ASR_REQUIRE(!wgt || (valid_min > 0.0f && valid_min < __builtin_inff()),
+                "asr_realign_moments_f32: valid_min=%g must be finite and > 0", (double)valid_min);
+    SrDims d;
+    d.batch = batch; d.n = n; d.H = H; d.W = W; d.h = h; d.w = w; d.f = 0;
+    SrCover cv;
+    cv.cov_min = 0.0f; cv.valid_min = valid_min; cv.wgt_stride = wgt_shared ? 0 : (int64_t)h * w;
+    const float sy = (float)h / (float)H, sx = (float)w / (float)W;
+    hipStream_t s = asr_stream(stream);
+    if (wgt)
+        hipLaunchKernelGGL(sr_realign_moments_kernel<true>, hr_grid(d), kBlock, 0, s, y, wgt, out_mean, out_var, out_nv, trans_tf,
+                           rot_tf, d, cv, sy, sx);
+    else
+        hipLaunchKernelGGL(sr_realign_moments_kernel<false>, hr_grid(d), kBlock, 0, s, y, wgt, out_mean, out_var, out_nv, trans_tf,
+                           rot_tf, d, cv, sy, sx);
     ASR_LAUNCH_CHECK();
     return ASR_OK;
 }

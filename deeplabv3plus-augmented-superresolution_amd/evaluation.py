@@ -225,7 +225,8 @@ LABELMAP_CSV_COLUMNS = ("standard_iou", "aug_iou", "max_iou", "mean_iou")
 
 def gather_labelmap_records(local_indices, local_miou, local_counts, num_images, local_band_miou=None,
                             local_band_counts=None, num_widths=0, local_confusion=None, confusion_labels=0,
-                            local_sweep_miou=None, local_sweep_counts=None, num_factors=0):
+                            local_sweep_miou=None, local_sweep_counts=None, num_factors=0, local_cov_miou=None,
+                            local_cov_counts=None, num_coverages=0):
     """The one collective of evaluate_labelmaps.  local_miou: [n_local, 4] per-image Mean_IOU (LABELMAP_KEYS order);
     local_counts: [n_local, 4, 3, 256] integer counts.  Returns on every rank (rows [num_images, 4] float64, NaN rows where
     no rank reported; summed counts [4, 3, 256] int64).  The counts travel as float64 in the same all-gather as the rows:
@@ -240,8 +241,13 @@ def gather_labelmap_records(local_indices, local_miou, local_counts, num_images,
     num_factors = T > 0: the threshold-sweep records of the three SR label maps (LABELMAP_KEYS[1:]) ride in it as well --
     local_sweep_miou [n_local, 3, T], local_sweep_counts [n_local, 3, T, 3, 256] -- and the result ends in two more entries,
     sweep_rows [num_images, 3, T] and the summed sweep_counts [3, T, 3, 256] int64.  The order of the result is
-    (rows, counts[, band_rows, band_counts][, confusion][, sweep_rows, sweep_counts])."""
+    (rows, counts[, band_rows, band_counts][, confusion][, sweep_rows, sweep_counts][, cov_rows, cov_counts]).
+
+    num_coverages = C > 0: the risk-coverage records of the four label maps ride in it last -- local_cov_miou [n_local, 4, C],
+    local_cov_counts [n_local, 4, C, 3, 256] -- and the result ends in cov_rows [num_images, 4, C] and the summed cov_counts
+    [4, C, 3, 256] int64."""
     m = len(LABELMAP_KEYS)
+    c = int(num_coverages)
     b = int(num_widths)
     side = int(confusion_labels) + 1 if confusion_labels else 0
     t = int(num_factors)
@@ -250,7 +256,8 @@ def gather_labelmap_records(local_indices, local_miou, local_counts, num_images,
     base = m + m * 768
     conf = base + m * b + m * b * 768
     sweep = conf + m * side * side
-    width = sweep + ms * t + ms * t * 768
+    cov = sweep + ms * t + ms * t * 768
+    width = cov + m * c + m * c * 768
     rec = np.empty((n_local, width), dtype=np.float64)
     if n_local:
         rec[:, :m] = np.asarray(local_miou, dtype=np.float64).reshape(n_local, m)
@@ -262,7 +269,10 @@ def gather_labelmap_records(local_indices, local_miou, local_counts, num_images,
             rec[:, conf:sweep] = np.asarray(local_confusion, dtype=np.int64).reshape(n_local, m * side * side)
         if t:
             rec[:, sweep:sweep + ms * t] = np.asarray(local_sweep_miou, dtype=np.float64).reshape(n_local, ms * t)
-            rec[:, sweep + ms * t:] = np.asarray(local_sweep_counts, dtype=np.int64).reshape(n_local, ms * t * 768)
+            rec[:, sweep + ms * t:cov] = np.asarray(local_sweep_counts, dtype=np.int64).reshape(n_local, ms * t * 768)
+        if c:
+            rec[:, cov:cov + m * c] = np.asarray(local_cov_miou, dtype=np.float64).reshape(n_local, m * c)
+            rec[:, cov + m * c:] = np.asarray(local_cov_counts, dtype=np.int64).reshape(n_local, m * c * 768)
     table = D.all_gather_rows(local_indices, rec, num_images, width)
     counts = np.nan_to_num(table[:, m:base]).astype(np.int64).reshape(num_images, m, 3, 256)
     out = (table[:, :m], counts.sum(axis=0))
@@ -272,8 +282,11 @@ def gather_labelmap_records(local_indices, local_miou, local_counts, num_images,
     if side:
         out += (np.nan_to_num(table[:, conf:sweep]).astype(np.int64).reshape(num_images, m, side, side).sum(axis=0),)
     if t:
-        sweep_counts = np.nan_to_num(table[:, sweep + ms * t:]).astype(np.int64).reshape(num_images, ms, t, 3, 256)
+        sweep_counts = np.nan_to_num(table[:, sweep + ms * t:cov]).astype(np.int64).reshape(num_images, ms, t, 3, 256)
         out += (table[:, sweep:sweep + ms * t].reshape(num_images, ms, t), sweep_counts.sum(axis=0))
+    if c:
+        cov_counts = np.nan_to_num(table[:, cov + m * c:]).astype(np.int64).reshape(num_images, m, c, 3, 256)
+        out += (table[:, cov:cov + m * c].reshape(num_images, m, c), cov_counts.sum(axis=0))
     return out
 
 
@@ -293,7 +306,7 @@ def dataset_miou(counts):
 def evaluate_labelmaps(path, image_paths, gt_paths, class_ids=tuple(range(1, 21)), num_aug=100, angle_max=0.3, shift_max=30,
                        img_size=(512, 512), rank=0, world=1, seed=1234, sr_types=("aug", "max", "mean"), prune=True,
                        save_dir=None, band_widths=None, band_ignore_label=255, confusion_labels=None, th_factors=None,
-                       guide=None):
+                       guide=None, coverages=None, uncertainty_dir=None):
     """One fused label map per image and SR type (HotPath.run_image_labels) and its score.  Returns (rows, counts) on every
     rank: rows [images, 4] per-image Mean_IOU in LABELMAP_KEYS order (the reference's per-image-then-mean convention; NaN for
     an SR type that was not asked for), counts [4, 3, 256] int64 summed over the images (dataset_miou, label_ious).
@@ -322,7 +335,20 @@ def evaluate_labelmaps(path, image_paths, gt_paths, class_ids=tuple(range(1, 21)
     (rows, counts[, band_rows, band_counts][, confusion][, sweep_rows, sweep_counts]).
 
     guide ((radius, eps)): every SR score map is refined with the guided filter against its image before the fusion
-    (run_image_labels' guide; img_size must be the SR output size).  The return value keeps its form."""
+    (run_image_labels' guide; img_size must be the SR output size).  The return value keeps its form.
+
+    coverages (C whole percentages in [1, 100], 1..16): the same loop also collects each label map's counts over its p % most
+    certain pixels (run_image_labels' coverages: the variance of the class stacks over the copies, no further forward pass
+    or solve) and the return value ends in two more entries, after the sweep's: cov_rows [images, 4, C] per-image Mean_IOU
+    and cov_counts [4, C, 3, 256] int64 summed over the images, NaN / zero for a label map that was not asked for
+    (write_coverage_csv).  The quantiles are each image's own.  They travel in the same all-gather.  uncertainty_dir (with
+    coverages): sqrt of each image's uncertainty map, the standard deviation over the copies, as <stem>.npy (float32 [H, W])."""
+    if uncertainty_dir and coverages is None:
+        raise ValueError("uncertainty_dir needs coverages: the uncertainty map is only built for the risk-coverage curve")
+    if uncertainty_dir:
+        os.makedirs(uncertainty_dir, exist_ok=True)
+    covs = ops.check_coverages(coverages) if coverages is not None else None
+    n_c = len(covs) if covs else 0
     class_ids, params, mine = _class_set_run(class_ids, image_paths, gt_paths, rank, world, num_aug=num_aug,
                                              angle_max=angle_max, shift_max=shift_max, seed=seed)
     n_img = len(image_paths)
@@ -337,6 +363,7 @@ def evaluate_labelmaps(path, image_paths, gt_paths, class_ids=tuple(range(1, 21)
     if factors is not None and not 1 <= n_t <= ops.MAX_LABEL_SWEEP_FACTORS:
         raise ValueError(f"{n_t} threshold factors (1..{ops.MAX_LABEL_SWEEP_FACTORS})")
     mious, counts, band_mious, band_counts, confusion, sweep_mious, sweep_counts = [], [], [], [], [], [], []
+    cov_mious, cov_counts = [], []
     for g in mine:
         image, gt = _image_and_labels_on_device(image_paths[g], gt_paths[g], img_size)
         angles, shifts = params[g]
@@ -347,6 +374,10 @@ def evaluate_labelmaps(path, image_paths, gt_paths, class_ids=tuple(range(1, 21)
             extra["th_factors"] = factors
         if guide is not None:
             extra["guide"] = guide
+        if n_c:
+            extra["coverages"] = covs
+            if uncertainty_dir:
+                extra["keep_uncertainty"] = True
         res = path.run_image_labels(image, angles, shifts, class_ids, gt_dev=gt, sr_types=sr_types, prune=prune,
                                     adam_starts={c: int(starts[g, k]) for k, c in enumerate(class_ids)}, **extra)
         mious.append([res["Mean_IOU"].get(key, np.nan) for key in LABELMAP_KEYS])
@@ -359,6 +390,12 @@ def evaluate_labelmaps(path, image_paths, gt_paths, class_ids=tuple(range(1, 21)
         if n_t:
             sweep_mious.append([res["sweep_Mean_IOU"].get(key, np.full(n_t, np.nan)) for key in LABELMAP_KEYS[1:]])
             sweep_counts.append([res["sweep_counts"].get(key, np.zeros((n_t, 3, 256), np.int64)) for key in LABELMAP_KEYS[1:]])
+        if n_c:
+            cov_mious.append([res["coverage_Mean_IOU"].get(key, np.full(n_c, np.nan)) for key in LABELMAP_KEYS])
+            cov_counts.append([res["coverage_counts"].get(key, np.zeros((n_c, 3, 256), np.int64)) for key in LABELMAP_KEYS])
+        if n_c and uncertainty_dir:
+            np.save(os.path.join(uncertainty_dir, os.path.splitext(os.path.basename(image_paths[g]))[0] + ".npy"),
+                    torch.sqrt(res["uncertainty"]).cpu().numpy())
         if save_dir:
             from PIL import Image
             stem = os.path.splitext(os.path.basename(image_paths[g]))[0]
@@ -368,7 +405,8 @@ def evaluate_labelmaps(path, image_paths, gt_paths, class_ids=tuple(range(1, 21)
                         os.path.join(save_dir, f"{stem}_{key}.png"))
     return gather_labelmap_records(mine, mious, counts, n_img, band_mious if bands else None, band_counts if bands else None,
                                    n_b, confusion if n_conf else None, n_conf, sweep_mious if n_t else None,
-                                   sweep_counts if n_t else None, n_t)
+                                   sweep_counts if n_t else None, n_t, cov_mious if n_c else None,
+                                   cov_counts if n_c else None, n_c)
 
 
 def write_labelmap_csv(path, counts, rows):
@@ -474,6 +512,45 @@ def write_trimap_csv(path, widths, band_counts, band_rows, counts=None, ignore_l
             pixels = int(band_counts[:, b, 0].max(axis=0).sum())
             share = repr(pixels / total) if total else "nan"
             wr.writerow([f"w={width}"] + cells + [str(pixels), share, str(len(band_rows))])
+
+
+COVERAGE_CSV_COLUMNS = tuple(f"{key}_{kind}" for key in LABELMAP_KEYS
+                             for kind in ("dataset_mIoU", "mean_image_mIoU", "retained_share"))
+
+
+def write_coverage_csv(path, percents, cov_counts, cov_rows, counts=None, ignore_label=255):
+    """The risk-coverage curve of the label maps, one row per percentage ("coverage", in the caller's order).  For standard /
+    aug / max / mean: "<key>_dataset_mIoU" (dataset_miou of cov_counts [4, C, 3, 256], the counts over each image's p % most
+    certain pixels summed over the images), "<key>_mean_image_mIoU" (np.mean of the per-image Mean_IOU, cov_rows
+    [images, 4, C]; a NaN image propagates) and "<key>_retained_share": the ground-truth pixels the row retained (labels
+    0..255 of its counts) over the counted ground-truth pixels of the whole images -- from counts [4, 3, 256], the
+    whole-image counts write_labelmap_csv takes, with ignore_label's pixels (-1 or None: none) taken out; without counts,
+    over the pixels of the 100 % row when percents holds one, else nan.  The share is >= p / 100: pixels tied with the
+    quantile stay in.  The columns of a label map that was not produced (all-zero counts) are nan.  n = number of images."""
+    import csv
+    ps = ops.check_coverages(percents)
+    m = len(LABELMAP_KEYS)
+    cov_counts = np.asarray(cov_counts, dtype=np.int64).reshape(m, len(ps), 3, 256)
+    cov_rows = np.asarray(cov_rows, dtype=np.float64).reshape(-1, m, len(ps))
+    total = None
+    if counts is not None:
+        truth = np.asarray(counts, dtype=np.int64).reshape(m, 3, 256)[:, 0].max(axis=0).copy()
+        if ignore_label is not None and 0 <= int(ignore_label) <= 255:
+            truth[int(ignore_label)] = 0
+        total = int(truth.sum())
+    elif 100 in ps:
+        total = int(cov_counts[:, ps.index(100), 0].max(axis=0).sum())
+    with open(path, "w", newline="") as fh:
+        wr = csv.writer(fh, quoting=csv.QUOTE_ALL, lineterminator="\n")
+        wr.writerow(("coverage",) + COVERAGE_CSV_COLUMNS + ("n",))
+        for b, p in enumerate(ps):
+            cells = []
+            for j in range(m):
+                made = bool(cov_counts[j].any())            # a label map that was not asked for carries all-zero counts
+                cells.append(repr(dataset_miou(cov_counts[j, b])) if made else "nan")
+                cells.append(repr(float(np.mean(cov_rows[:, j, b]))) if made and len(cov_rows) else "nan")
+                cells.append(repr(int(cov_counts[j, b, 0].sum()) / total) if made and total else "nan")
+            wr.writerow([str(p)] + cells + [str(len(cov_rows))])
 
 
 CONFUSION_CSV_COLUMNS = ("key", "truth", "predicted", "pixels", "share_of_truth")

@@ -324,6 +324,55 @@ def confusion_counts(truth, preds, num_labels, out=None):
     return out.view(p, side, side)
 
 
+MAX_COVERAGE_BINS = 16
+
+
+def check_coverages(percents):
+    """The coverages of a risk-coverage curve as a list of ints: 1..16 of them, each a whole percentage in [1, 100]; any order,
+    repeats allowed.  Host only; ValueError otherwise."""
+    if isinstance(percents, (str, bytes)):
+        raise ValueError(f"coverages must be a sequence of integers, got {percents!r}")
+    try:
+        vals = list(percents)
+        if any(isinstance(v, (bool, str, bytes)) for v in vals):
+            raise TypeError
+        ps = [int(v) for v in vals]
+        same = all(float(v) == float(k) for v, k in zip(vals, ps))
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError(f"coverages must be a sequence of integers, got {percents!r}") from None
+    if not same:
+        raise ValueError(f"coverages must be integers, got {vals}")
+    if not 1 <= len(ps) <= MAX_COVERAGE_BINS:
+        raise ValueError(f"{len(ps)} coverages (1..{MAX_COVERAGE_BINS})")
+    bad = [v for v in ps if not 1 <= v <= 100]
+    if bad:
+        raise ValueError(f"coverages are percentages in [1, 100], got {bad}")
+    return ps
+
+
+def binned_class_counts(truth, preds, u, edges, ignore_label=255, out=None):
+    """One int32 truth and one f32 map u of the same size, P <= 8 int32 predictions [P, ...], B <= 16 f32 edges ON THE DEVICE
+    -> int64 [P, B, 3, 256]: class_counts restricted to the pixels with u <= edges[b] whose truth is not ignore_label (-1 or
+    None: none), in the caller's edge order (asr_binned_class_counts_f32).  A NaN is in no bin; +inf as an edge holds every
+    pixel.  out: a contiguous int64 tensor of that size to write into."""
+    per = truth.numel()
+    p = preds.numel() // per if per else 0
+    if per == 0 or p * per != preds.numel() or u.numel() != per:
+        raise AsrError("binned_class_counts: truth / preds / u size mismatch")
+    if not 1 <= p <= _lib.MAX_BINNED_PREDS:
+        raise AsrError(f"binned_class_counts: {p} predictions (1..{_lib.MAX_BINNED_PREDS})")
+    nb = edges.numel()
+    if edges.dim() != 1 or not 1 <= nb <= MAX_COVERAGE_BINS:
+        raise AsrError(f"binned_class_counts: edges must be a vector of 1..{MAX_COVERAGE_BINS} values, got {tuple(edges.shape)}")
+    if out is None:
+        out = torch.empty((p, nb, 3, 256), dtype=torch.int64, device=truth.device)
+    elif out.numel() != p * nb * 768:
+        raise AsrError("binned_class_counts: out size mismatch")
+    call("asr_binned_class_counts_f32", ptr(truth, torch.int32), ptr(preds, torch.int32), ptr(u), ptr(edges),
+         ptr(out, torch.int64), per, p, nb, -1 if ignore_label is None else int(ignore_label), stream_ptr())
+    return out.view(p, nb, 3, 256)
+
+
 def realign(y, trans_tf, rot_tf, out_hw, mode):
     """mode "max" | "mean" -> [B,H,W]; "both" -> (max, mean) from one pass over the copies."""
     if y.dim() != 4:
@@ -418,6 +467,46 @@ def realign_covered(y, wgt, trans_tf, rot_tf, out_hw, want=("mean",), cov_min=0.
     out = {k: torch.empty((b, H, W), dtype=f32, device=y.device) for k in want}
     call("asr_realign_covered_f32", ptr(y), ptr(wgt), shared, ptr(out.get("mean"), allow_none=True),
          ptr(out.get("median"), allow_none=True), ptr(out.get("cov"), allow_none=True), float(cov_min), float(valid_min),
+         ptr(trans_tf), ptr(rot_tf), b, n, H, W, h, w, stream_ptr())
+    return out
+
+
+MOMENT_OUTPUTS = ("mean", "var", "nv")
+
+
+def realign_moments(y, trans_tf, rot_tf, out_hw, want=("mean", "var"), wgt=None, valid_min=0.5):
+    """Mean, population variance and valid count over the realigned copies in one launch (asr_realign_moments_f32; the rule:
+    include/asr_hip.h).  y [B,N,h,w]; wgt None (every copy is valid), [B,N,h,w], or [h,w]: one plane shared by every copy;
+    a copy is valid at a pixel where its realigned weight is >= valid_min.  want: any of "mean" (over the valid copies, 0
+    where there is none; without wgt it is realign(..., "mean") bit for bit), "var" (the population variance about that
+    mean, 0 where nv is 0, exactly 0 where it is 1) and "nv" (the number of valid copies, as f32).  Returns a dict of [B,H,W]
+    tensors with the keys asked for."""
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or len(set(want)) != len(want) or any(k not in MOMENT_OUTPUTS for k in want):
+        raise AsrError(f"realign_moments: want must be a non-empty selection of {MOMENT_OUTPUTS} without repeats, got {want!r}")
+    if wgt is not None and not (np.isfinite(float(valid_min)) and float(valid_min) > 0.0):
+        raise AsrError(f"realign_moments: valid_min={valid_min} must be finite and > 0")
+    if y.dim() != 4:
+        raise AsrError("realign_moments: y must be [B,N,h,w]")
+    b, n, h, w = y.shape
+    shared = 0
+    if wgt is None:
+        pass
+    elif wgt.dim() == 2:
+        shared = 1
+        if tuple(wgt.shape) != (h, w):
+            raise AsrError(f"realign_moments: the shared wgt plane must be [{h},{w}], got {tuple(wgt.shape)}")
+    elif wgt.dim() == 4:
+        if tuple(wgt.shape) != (b, n, h, w):
+            raise AsrError(f"realign_moments: wgt must be [{b},{n},{h},{w}] like y, got {tuple(wgt.shape)}")
+    else:
+        raise AsrError(f"realign_moments: wgt must be None, [B,N,h,w] or [h,w], got {tuple(wgt.shape)}")
+    _check_tf(trans_tf, b, n, "trans_tf")
+    _check_tf(rot_tf, b, n, "rot_tf")
+    H, W = int(out_hw[0]), int(out_hw[1])
+    out = {k: torch.empty((b, H, W), dtype=f32, device=y.device) for k in want}
+    call("asr_realign_moments_f32", ptr(y), ptr(wgt, allow_none=True), shared, ptr(out.get("mean"), allow_none=True),
+         ptr(out.get("var"), allow_none=True), ptr(out.get("nv"), allow_none=True), float(valid_min) if wgt is not None else 0.0,
          ptr(trans_tf), ptr(rot_tf), b, n, H, W, h, w, stream_ptr())
     return out
 

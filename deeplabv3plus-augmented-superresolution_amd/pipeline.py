@@ -16,7 +16,8 @@ import torch
 
 from . import ops
 from .superresolution_scripts import augmentation_utils as au
-from .utils import iou_from_counts, mean_iou_from_counts
+from .utils import (coverage_edges, coverage_retained, iou_from_counts, mean_iou_from_counts, opm_scales,
+                    uncertainty_map)
 
 
 class HotPath:
@@ -291,7 +292,8 @@ class HotPath:
     # ---- label maps: the classes of an image fused into one label map per SR type, and its Mean_IOU -----------------------
     def run_image_labels(self, image_dev, angles, shifts, class_ids=range(1, 21), gt_dev=None, adam_starts=None,
                          sr_types=("aug", "max", "mean"), want_standard=True, prune=True, profile=None, keep_scores=False,
-                         band_widths=None, band_ignore_label=255, confusion_labels=None, th_factors=None, guide=None):
+                         band_widths=None, band_ignore_label=255, confusion_labels=None, th_factors=None, guide=None,
+                         coverages=None, keep_uncertainty=False):
         """One label map per SR type from one forward pass: stage 1 and the solves are run_image_classes's; stage 2 ends in the
         fusion kernel (ops.fuse_labels) instead of K thresholds.  class_ids: K <= 32 distinct ids, none 0 (the label of "no
         class").  At each pixel the label is the class whose single-class mask is set there and whose SR output is greatest
@@ -336,8 +338,26 @@ class HotPath:
         the image itself as the guide moves each score map's boundary onto the image's edges.  The guide-only pass
         (ops.guided_prepare) runs once per image inside the timed SR stage; each SR type's scores (and in slice_max its max
         maps' scores) are refined in place (ops.guided_apply) before the fusion, the sweep counts and keep_scores see them.
-        With guide=None nothing else is launched and every result is what it was."""
+        With guide=None nothing else is launched and every result is what it was.
+
+        coverages (with gt_dev; 1..16 whole percentages in [1, 100], any order): the risk-coverage curve of the label maps.
+        One ops.realign_moments call over the stacks of the solved classes (the stacks the solver read, frame coverage: one
+        shared all-ones plane, valid_min 0.5; in slice_max mode the class planes, not the max maps) gives each class's
+        variance over the copies; utils.uncertainty_map takes the maximum over the classes (+inf where a class rests on
+        fewer than two copies, and everywhere when no class was solved), utils.coverage_edges picks the p % quantiles among
+        the pixels that are not void (255) on the device, and one ops.binned_class_counts call scores every produced label
+        map, standard included, over its p % most certain pixels.  The result gains "coverage_counts" {key: int64 [B, 3, 256]
+        numpy}, "coverage_Mean_IOU" {key: float64 [B]} and "coverage_share" (float64 [B]: the share of the non-void pixels
+        each percentage retained, >= p / 100 as ties stay in), in the same single copy to the host as "counts"; with
+        keep_uncertainty also "uncertainty" (device float32 [H, W]) and "uncertainty_stacks" (the [K', N, h, w] tensor the
+        moments were taken of, None when no class was solved).  With coverages=None nothing else is launched and nothing
+        else returned."""
         ids = [int(c) for c in class_ids]
+        covs = ops.check_coverages(coverages) if coverages is not None else None
+        if covs is not None and gt_dev is None:
+            raise ValueError("coverages needs gt_dev: the risk-coverage curve scores the label maps against a ground truth")
+        if keep_uncertainty and covs is None:
+            raise ValueError("keep_uncertainty without coverages: the uncertainty map is only built for the risk-coverage curve")
         if guide is not None:
             try:
                 g_radius, g_eps = guide
@@ -386,7 +406,8 @@ class HotPath:
             tally = None
             if gt is not None:
                 tally = _LabelCounts(keys, len(bands) if bands else 0, image_dev.device, n_conf,
-                                     sr_types if factors is not None else (), len(factors) if factors is not None else 0)
+                                     sr_types if factors is not None else (), len(factors) if factors is not None else 0,
+                                     len(covs) if covs else 0)
             f_dev = ops.to_device(factors, device=image_dev.device) if factors is not None and kept and sr_types else None
             if tally is not None and want_standard:
                 tally.counts[0] = ops.class_counts(gt, maps[0])[0]
@@ -424,13 +445,33 @@ class HotPath:
                                       -1 if band_ignore_label is None else int(band_ignore_label), out=tally.band)
             if n_conf:
                 ops.confusion_counts(gt, maps, n_conf, out=tally.confusion)
+            u_map = None
+            if covs is not None:
+                u_map = self._uncertainty(y if kept else None, angles, self._sr_frame(image_dev, shifts), out_hw, image_dev.device)
+                edges = coverage_edges(u_map, gt, covs, ignore_label=255)
+                ops.binned_class_counts(gt, maps, u_map, edges, ignore_label=255, out=tally.coverage)
+                tally.retained[:] = coverage_retained(u_map, gt, edges, ignore_label=255)
         res = {key: maps[j] for j, key in enumerate(keys)}
         res["solved_ids"] = solved
         if tally is not None:
             res.update(tally.to_host())
         if keep_scores:
             res["scores"] = scores
+        if keep_uncertainty:
+            res["uncertainty"] = u_map
+            res["uncertainty_stacks"] = y if kept else None
         return res
+
+    def _uncertainty(self, y, angles, fshifts, out_hw, device):
+        """utils.uncertainty_map of the class stacks y [K', N, h, w] (None: no class): one moments launch under frame coverage."""
+        if y is None:
+            return torch.full(tuple(out_hw), float("inf"), dtype=torch.float32, device=device)
+        a = np.repeat(np.asarray(angles, dtype=np.float32)[None], y.shape[0], axis=0)
+        s = np.repeat(np.asarray(fshifts, dtype=np.float32)[None], y.shape[0], axis=0)
+        rot, tr = self.sr._transforms(a, s, y.device, negate=True)
+        ones = torch.ones(tuple(y.shape[2:]), dtype=torch.float32, device=y.device)
+        mom = ops.realign_moments(y, tr, rot, out_hw, want=("var", "nv"), wgt=ones, valid_min=0.5)
+        return uncertainty_map(mom["var"], mom["nv"], opm_scales(range(y.shape[0]), self.mode, normalised=True))
 
     def _check_th_factors(self, th_factors, gt_dev):
         """The factors of a label-map threshold sweep as a float32 array (1..ops.MAX_LABEL_SWEEP_FACTORS of them)."""
@@ -477,20 +518,25 @@ class _LabelCounts:
     """The counts of run_image_labels on the device, one int64 allocation so that they reach the host in one copy: per label
     map (in the order of keys) the [3, 256] whole-image counts, then, with B band widths, its [B, 3, 256] band counts, then,
     with L confusion labels, its [L+1, L+1] confusion matrix; last, with T threshold factors, the [T, 3, 256] sweep counts of
-    each SR type in sweep_keys."""
+    each SR type in sweep_keys; after those, with C coverages, each label map's [C, 3, 256] coverage counts and C + 1 pixel
+    totals (the counted pixels each coverage retained, then all of them)."""
 
-    def __init__(self, keys, n_bands, device, n_conf=0, sweep_keys=(), n_factors=0):
-        self.keys, self.n_bands, self.n_conf = keys, n_bands, n_conf
+    def __init__(self, keys, n_bands, device, n_conf=0, sweep_keys=(), n_factors=0, n_cov=0):
+        self.keys, self.n_bands, self.n_conf, self.n_cov = keys, n_bands, n_conf, n_cov
         self.sweep_keys, self.n_factors = list(sweep_keys), n_factors
         self._split = len(keys) * 768
         self._conf = self._split * (1 + n_bands)
         cells = (n_conf + 1) ** 2 if n_conf else 0
         self._sweep = self._conf + len(keys) * cells
-        self._buf = torch.empty(self._sweep + len(self.sweep_keys) * n_factors * 768, dtype=torch.int64, device=device)
+        self._cov = self._sweep + len(self.sweep_keys) * n_factors * 768
+        self._ret = self._cov + len(keys) * n_cov * 768
+        self._buf = torch.empty(self._ret + (n_cov + 1 if n_cov else 0), dtype=torch.int64, device=device)
         self.counts = self._buf[:self._split].view(len(keys), 3, 256)
         self.band = self._buf[self._split:self._conf]   # [len(keys), B, 3, 256], flat: ops.band_class_counts's out
         self.confusion = self._buf[self._conf:self._sweep]      # [len(keys), L+1, L+1], flat: ops.confusion_counts's out
-        self.sweep = self._buf[self._sweep:].view(len(self.sweep_keys), n_factors, 3, 256)      # row i: ops.fuse_labels_sweep_counts's out
+        self.sweep = self._buf[self._sweep:self._cov].view(len(self.sweep_keys), n_factors, 3, 256)      # row i: ops.fuse_labels_sweep_counts's out
+        self.coverage = self._buf[self._cov:self._ret]  # [len(keys), C, 3, 256], flat: ops.binned_class_counts's out
+        self.retained = self._buf[self._ret:]           # [C + 1]: utils.coverage_retained
 
     def to_host(self):
         """The "counts" / "Mean_IOU" (and "band_counts" / "band_Mean_IOU") entries of the result."""
@@ -507,10 +553,18 @@ class _LabelCounts:
             conf = host[self._conf:self._sweep].reshape(len(self.keys), self.n_conf + 1, self.n_conf + 1)
             res["confusion"] = {key: conf[j] for j, key in enumerate(self.keys)}
         if self.n_factors:
-            sweep = host[self._sweep:].reshape(len(self.sweep_keys), self.n_factors, 3, 256)
+            sweep = host[self._sweep:self._cov].reshape(len(self.sweep_keys), self.n_factors, 3, 256)
             res["sweep_counts"] = {t: sweep[i] for i, t in enumerate(self.sweep_keys)}
             res["sweep_Mean_IOU"] = {t: np.array([mean_iou_from_counts(c) for c in sweep[i]], dtype=np.float64)
                                      for i, t in enumerate(self.sweep_keys)}
+        if self.n_cov:
+            cov = host[self._cov:self._ret].reshape(len(self.keys), self.n_cov, 3, 256)
+            res["coverage_counts"] = {key: cov[j] for j, key in enumerate(self.keys)}
+            res["coverage_Mean_IOU"] = {key: np.array([mean_iou_from_counts(c) for c in cov[j]], dtype=np.float64)
+                                        for j, key in enumerate(self.keys)}
+            ret = host[self._ret:]
+            with np.errstate(divide="ignore", invalid="ignore"):
+                res["coverage_share"] = np.float64(ret[:-1]) / np.float64(ret[-1])
         return res
 
 

@@ -3,7 +3,8 @@
 -- plus batched variants that solve many images in one sequence of launches, and the robust one-pass fusions
 ``median_superresolution``, ``quantile_superresolution`` and ``trimmed_mean_superresolution`` (order statistics over the
 realigned copies, ``realign_select_batch``), and their coverage-normalised forms ``covered_mean_superresolution``,
-``covered_median_superresolution`` and ``coverage_map`` (``realign_covered_batch``).  All arithmetic
+``covered_median_superresolution`` and ``coverage_map`` (``realign_covered_batch``), and ``variance_superresolution``, how
+far the copies disagree at each pixel (``realign_moments_batch``).  All arithmetic
 runs in the fused HIP kernels of csrc/sr.hip; this class only prepares float32 parameters.
 
 ``use_BTV`` swaps the TV prior for the bilateral TV of superresolution.py:8-23 (inside the same
@@ -302,17 +303,21 @@ class Superresolution:
         of the realigned values over the sum of the realigned weights (0 below cov_min), the median runs over the copies
         whose realigned weight reaches valid_min, and "cov" is the sum of the realigned weights: on how many copies any
         fusion of them rests at each pixel.  One launch."""
-        b, n, h, w = copies.shape
-        if self.cover == "frame":
-            y, wgt = copies, torch.ones((h, w), dtype=torch.float32, device=copies.device)
-        else:
-            from .augmentation_utils import copy_validity
-            a, s = np.asarray(angles, dtype=np.float32), np.asarray(shifts, dtype=np.float32)
-            wgt = torch.stack([copy_validity(a[i], s[i], self.output_size, (h, w)) for i in range(b)]).contiguous()
-            y = (copies * wgt).contiguous()
+        wgt = self._cover_planes(copies, angles, shifts, self.cover)
+        y = copies if self.cover == "frame" else (copies * wgt).contiguous()
         rot, tr = self._transforms(angles, shifts, copies.device, negate=True)
         return ops.realign_covered(y, wgt, tr, rot, self.output_size, want=want, cov_min=self.cov_min,
                                    valid_min=self.valid_min)
+
+    def _cover_planes(self, copies, angles, shifts, cover):
+        """The weight planes of copies [B,N,h,w] under a cover mode: one shared all-ones [h,w] plane ("frame"), or each
+        copy's validity [B,N,h,w] ("validity")."""
+        b, n, h, w = copies.shape
+        if cover == "frame":
+            return torch.ones((h, w), dtype=torch.float32, device=copies.device)
+        from .augmentation_utils import copy_validity
+        a, s = np.asarray(angles, dtype=np.float32), np.asarray(shifts, dtype=np.float32)
+        return torch.stack([copy_validity(a[i], s[i], self.output_size, (h, w)) for i in range(b)]).contiguous()
 
     def _covered_single(self, augmented_copies, angles, shifts, key):
         dev = _lib.require_gpu()
@@ -328,3 +333,29 @@ class Superresolution:
 
     def coverage_map(self, augmented_copies, angles, shifts):
         return self._covered_single(augmented_copies, angles, shifts, "cov")
+
+    # -- how far the realigned copies disagree (not in the reference) ------------------------------------------------
+    _OBJECT_COVER = object()
+
+    def realign_moments_batch(self, copies, angles, shifts, want=("mean", "var"), cover=_OBJECT_COVER):
+        """copies [B,N,h,w] device, realigned as in realign_batch -> dict of device [B,H,W] with the keys of want, any of
+        "mean", "var", "nv" (ops.realign_moments): the mean over the copies that saw the pixel, the population variance of
+        those copies about it, and their number.  cover: the object's by default -- "frame" (a copy is valid where the realign
+        kept it inside the output frame) or "validity" (where it also came from inside the image), a copy counting where
+        its realigned weight reaches valid_min; the copies themselves are NOT multiplied by the weights -- or None: no
+        weight plane at all, every copy is valid everywhere, zero fill included ("mean" is then realign_batch's mean bit for
+        bit).  One launch."""
+        cover = self.cover if cover is self._OBJECT_COVER else cover
+        if cover is not None and cover not in COVER_MODES:
+            raise ValueError(f"cover must be None or one of {COVER_MODES}, got {cover!r}")
+        wgt = self._cover_planes(copies, angles, shifts, cover) if cover is not None else None
+        rot, tr = self._transforms(angles, shifts, copies.device, negate=True)
+        return ops.realign_moments(copies, tr, rot, self.output_size, want=want, wgt=wgt, valid_min=self.valid_min)
+
+    def variance_superresolution(self, augmented_copies, angles, shifts):
+        """([H, W, 1] float32 population variance of the realigned copies at each pixel, None): max_superresolution's
+        arguments and return shape, under the object's cover and valid_min."""
+        dev = _lib.require_gpu()
+        y = _stack_copies(augmented_copies, dev)[None]
+        a, s = self._batchify(angles, shifts)
+        return self.realign_moments_batch(y, a, s, ("var",))["var"][0].cpu().numpy()[..., None], None

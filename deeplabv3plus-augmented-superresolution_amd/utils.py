@@ -240,6 +240,103 @@ def metrics_from_confusion(M, other="ignore"):
                 if present.any() else nan}
 
 
+def opm_scales(class_ids, mode, normalised=True):
+    """s_k of uncertainty_map for the stacks of class_ids: what the stack holds where class k wins.  The argmax OPM writes the
+    class id there (asr_opm_classes_f32), so a RAW argmax stack has s_k = ids[k]; the min-max normalisation the solver's
+    stacks go through takes it to 1, and the slice and slice_max stacks are activations in [0, 1]: s_k = 1."""
+    ids = [int(c) for c in class_ids]
+    if mode == "argmax" and not normalised:
+        return [float(c) for c in ids]
+    return [1.0] * len(ids)
+
+
+def uncertainty_map(var_planes, nv_planes, scales):
+    """How far the realigned copies disagree at each pixel, over the classes: [H, W] float32 on the planes' device.
+    var_planes, nv_planes [K, H, W]: the "var" and "nv" of ops.realign_moments for the K classes' stacks; scales: K values
+    s_k, the value stack k holds where its class wins (opm_scales), so that var_k / s_k^2 is comparable between classes.
+    u = max over k of var_k / (s_k * s_k), in f32; a pixel where any of the planes rests on fewer than two copies (nv < 2:
+    a variance of nothing) gets +inf, so a risk-coverage curve retains it last.  Classes that were pruned take no part:
+    pass only the planes of the classes that were solved."""
+    if var_planes.dim() != 3 or tuple(nv_planes.shape) != tuple(var_planes.shape):
+        raise ValueError(f"var_planes and nv_planes must both be [K, H, W], got {tuple(var_planes.shape)} and "
+                         f"{tuple(nv_planes.shape)}")
+    s = np.asarray(list(scales), dtype=np.float32).reshape(-1)
+    if s.size != var_planes.shape[0] or s.size == 0:
+        raise ValueError(f"{s.size} scales for {var_planes.shape[0]} planes (at least one)")
+    if not (np.isfinite(s).all() and (s > 0).all()):
+        raise ValueError(f"scales must be finite and > 0, got {s.tolist()}")
+    s2 = torch.as_tensor(s * s).to(var_planes.device).view(-1, 1, 1)
+    u = (var_planes.to(torch.float32) / s2).amax(dim=0)
+    thin = (nv_planes < 2).any(dim=0)
+    return torch.where(thin, torch.full_like(u, float("inf")), u)
+
+
+def _flat_on(t, like, dtype):
+    if isinstance(t, torch.Tensor):
+        return t.to(device=like, dtype=dtype).contiguous().reshape(-1)
+    return torch.as_tensor(np.asarray(t).astype({torch.int32: np.int32, torch.float32: np.float32}[dtype]).reshape(-1)).to(like)
+
+
+def coverage_edges(u, truth, percents, ignore_label=255):
+    """The edges of a risk-coverage curve: float32 [B] on u's device, nothing read back.  u: an uncertainty map (tensor, any
+    shape; no NaN), truth: a label map of as many pixels, percents: ops.check_coverages.  M is the number of counted pixels
+    (truth != ignore_label; -1 or None: all of them); for percent p the edge is the k-th smallest u among them,
+    k = (p * M + 99) // 100 in int64 -- the least k with k / M >= p / 100 -- found by one sort with the ignored pixels sent
+    to +inf.  Keeping u <= edge retains every pixel tied with the k-th, so the retained share is >= p %, and an edge of +inf
+    (uncertainty_map's "nobody knows") retains everything.  M = 0 gives +inf edges."""
+    ps = ops.check_coverages(percents)
+    uu = u.to(torch.float32).contiguous().reshape(-1)
+    t = _flat_on(truth, uu.device, torch.int32)
+    if t.numel() != uu.numel() or uu.numel() == 0:
+        raise ValueError(f"expected {uu.numel()} ground-truth pixels (at least one), got {t.numel()}")
+    inf = torch.full_like(uu, float("inf"))
+    ignore = -1 if ignore_label is None else int(ignore_label)
+    counted = (t != ignore) if ignore != -1 else torch.ones_like(t, dtype=torch.bool)
+    m = counted.sum(dtype=torch.int64)
+    s = torch.sort(torch.where(counted, uu, inf)).values
+    p = torch.as_tensor(ps, dtype=torch.int64).to(uu.device)
+    k = (p * m + 99) // 100
+    e = s[torch.clamp(k - 1, 0, uu.numel() - 1)]
+    return torch.where(m > 0, e, torch.full_like(e, float("inf")))
+
+
+def coverage_retained(u, truth, edges, ignore_label=255):
+    """int64 [B + 1] on u's device: the counted pixels (truth != ignore_label) with u <= edges[b], then M, all of them."""
+    uu = u.to(torch.float32).contiguous().reshape(-1)
+    t = _flat_on(truth, uu.device, torch.int32)
+    ignore = -1 if ignore_label is None else int(ignore_label)
+    counted = (t != ignore) if ignore != -1 else torch.ones_like(t, dtype=torch.bool)
+    kept = (counted[None] & (uu[None] <= edges.view(-1, 1))).sum(dim=1, dtype=torch.int64)
+    return torch.cat([kept, counted.sum(dtype=torch.int64).view(1)])
+
+
+def risk_coverage_counts(y_true, y_pred, u, percents, ignore_label=255, return_share=False):
+    """The per-label counts of one prediction over its p % most certain pixels, for each p of percents: host int64
+    [B, 3, 256], row b what ops.class_counts counts over the pixels with u <= coverage_edges(...)[b] whose truth is not
+    ignore_label.  u: an uncertainty map of as many pixels (utils.uncertainty_map); numpy arrays or tensors.  With
+    return_share also float64 [B]: the share of the counted pixels each row retained (>= p / 100: ties stay in)."""
+    dev = _lib.require_gpu()
+    t = _as_label_tensor(y_true, dev)
+    p = _as_label_tensor(y_pred, dev)
+    uu = _flat_on(u, dev, torch.float32)
+    if p.numel() != t.numel() or uu.numel() != t.numel():
+        raise ValueError(f"expected {t.numel()} pixels, got {p.numel()} predicted and {uu.numel()} of u")
+    edges = coverage_edges(uu, t, percents, ignore_label=ignore_label)
+    counts = ops.binned_class_counts(t, p, uu, edges, ignore_label=ignore_label)[0].cpu().numpy()
+    if not return_share:
+        return counts
+    kept = coverage_retained(uu, t, edges, ignore_label=ignore_label).cpu().numpy()
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return counts, np.float64(kept[:-1]) / np.float64(kept[-1])
+
+
+def risk_coverage_mIoU(y_true, y_pred, u, percents, ignore_label=255):
+    """float64 [B]: Mean_IOU of the prediction over its p % most certain pixels (mean_iou_from_counts of
+    risk_coverage_counts).  A curve that rises as p falls says u knows where the prediction is wrong."""
+    counts = risk_coverage_counts(y_true, y_pred, u, percents, ignore_label=ignore_label)
+    return np.array([mean_iou_from_counts(c) for c in counts], dtype=np.float64)
+
+
 def compute_IoU(true_image, image, img_size=(512, 512), class_id=None, include_bg=False):
     """IoU of two label maps (utils.py:207-230): single class (optionally with background) when class_id is given,
     otherwise the multi-class Mean_IOU.  Void (255) pixels are NOT excluded from the single-class form, exactly

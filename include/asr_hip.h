@@ -246,6 +246,31 @@ int asr_realign_covered_f32(const float* y, const float* wgt, int wgt_shared, fl
                             float* out_cov, float cov_min, float valid_min, const float* trans_tf, const float* rot_tf,
                             int batch, int n, int H, int W, int h, int w, asr_stream_t stream);
 
+/* Moments over the realigned copies: the mean, the population variance about it and the number of copies that saw the pixel,
+ * in ONE launch -- how far the copies disagree at a pixel, the second product of test-time augmentation next to the fused
+ * value.  y, trans_tf, rot_tf, batch, n, H, W, h, w are exactly those of asr_realign_max_f32.  wgt may be NULL; when given
+ * it is as in asr_realign_covered_f32: [batch, n, h, w] when wgt_shared == 0, ONE [h, w] plane when wgt_shared != 0.
+ * out_mean, out_var, out_nv are [batch, H, W]; each is optional (NULL), at least one must be given.
+ *
+ * The rule.  For output pixel (b, Y, X) and copy i, v_i is the value sr_realign_kernel folds for plane (b, i) of y, zero
+ * fill included.
+ *  - wgt == NULL: every copy is valid, nv = n, and valid_min is ignored.
+ *  - wgt given: c_i is the value the SAME statements give for the copy's weight plane; copy i is valid when
+ *    c_i >= valid_min, and nv is the number of valid copies.  valid_min must be finite and > 0.
+ *  - out_nv is (float)nv.
+ *  - out_mean is m = S / (float)nv, S the sum of the valid v_i in copy order, in f32, no contraction, then one IEEE f32
+ *    division; 0 when nv == 0.  With wgt == NULL it is asr_realign_mean_f32 bit for bit.
+ *  - out_var is the population variance about that ROUNDED m: s = s + d * d with d = v_i - m over the valid copies in copy
+ *    order (the subtraction, the product and the add each round once, no contraction), then one IEEE f32 division by
+ *    (float)nv.  It is 0 when nv == 0 and exactly 0 when nv == 1 (m is v_i itself there).
+ *  - Results for NaN inputs are unspecified.
+ * Null y / transforms, all three outputs NULL, a bad shape, and with wgt a valid_min that is not finite and > 0 return
+ * ASR_ERR_INVALID_ARG before any launch.  Any n is accepted and no LDS is used: a thread owns one output pixel and walks
+ * the copies twice, recomputing each v_i for the deviations instead of parking it. */
+int asr_realign_moments_f32(const float* y, const float* wgt, int wgt_shared, float* out_mean, float* out_var, float* out_nv,
+                            float valid_min, const float* trans_tf, const float* rot_tf, int batch, int n, int H, int W,
+                            int h, int w, asr_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * Output processing, thresholding, IoU
  * ------------------------------------------------------------------------------------------ */
@@ -437,6 +462,25 @@ int asr_boundary_dist2_u16(const int32_t* truth, uint16_t* dist2, int segments, 
 int asr_band_class_counts_i32(const int32_t* truth, const int32_t* preds, const uint16_t* dist2, const int* widths,
                               int64_t* counts, int64_t pixels, int num_preds, int num_widths, int r_max, int ignore_label,
                               asr_stream_t stream);
+
+/* --- binned counts: label maps scored over the pixels whose value u lies at or below each of B edges ------------------------
+ * (the risk-coverage curve: u an uncertainty map, the edges its quantiles, so that bin j keeps the most certain pixels)
+ *  - bin j is {p : u[p] <= edges[j]}, one f32 compare: -0 <= +0 holds, a NaN (in u or as an edge) is in no bin, and an edge of
+ *    +inf holds every pixel whose u is not NaN.  Bins are defined independently: the edges need not be sorted or distinct;
+ *  - ignore_label (-1 = none): pixels whose truth equals it are in no bin;
+ *  - the counts of a prediction P against T in bin j are counts[0][l], [1][l], [2][l] exactly as asr_class_counts_i32
+ *    defines them, over the pixels of the bin.  Labels outside 0..255 are not counted (and index nothing).
+ * Hence with every edge +inf, no NaN in u and ignore_label = -1, each bin is asr_class_counts_i32's counts bit for bit.
+ *
+ * asr_binned_class_counts_f32: num_preds (1..8) predictions [num_preds, pixels] against ONE truth [pixels] and ONE u [pixels]
+ * f32 (shared as asr_band_class_counts_i32 shares truth and dist2), for num_bins = B (1..16) edges: edges is a DEVICE array of
+ * B floats (they come from a selection on the device; nothing is read back).  counts [num_preds, B, 3, 256] int64, zeroed by
+ * the call, in the caller's edge order.  A bad argument returns ASR_ERR_INVALID_ARG before any launch.  One launch: each
+ * prediction is a grid row of at most 64 workgroups (or as many as keep a workgroup below 2^32 pixels) that re-reads truth and
+ * u (cache-fed); a pixel is added once per bin that holds it.  3 KiB of LDS per bin in a workgroup (48 KiB at 16). */
+int asr_binned_class_counts_f32(const int32_t* truth, const int32_t* preds, const float* u, const float* edges,
+                                int64_t* counts, int64_t pixels, int num_preds, int num_bins, int ignore_label,
+                                asr_stream_t stream);
 
 /* --- confusion matrix: where the pixels of each ground-truth label go in a label map --------------------------------------
  * Definitions (everything is integer):

@@ -30,7 +30,15 @@ these flags nothing else is computed or written.
 --guide_radius R [--guide_eps E]: every SR score map is refined with the guided filter (include/asr_hip.h, "guided filter";
 window radius R in 0..32, regulariser E, default 1e-3) against its own image before the label fusion, which moves the maps'
 boundaries onto the image's edges; compare the --band_widths curve with and without it.  Off when omitted: every CSV keeps its
-columns either way."""
+columns either way.
+
+--coverages 50,60,70,80,90,100 [--coverage_out FILE] [--uncertainty_dir DIR]: the risk-coverage curve as well -- the variance of
+the class stacks over the realigned copies (include/asr_hip.h at asr_realign_moments_f32; utils.uncertainty_map) says where the
+copies disagreed, and every label map is scored on each image's p % most certain non-void pixels (asr_binned_class_counts_f32),
+with no further forward pass or solve.  One CSV row per percentage (evaluation.write_coverage_csv: dataset mIoU, mean per-image
+mIoU and the share actually retained, which is >= p % because ties stay in); a curve that rises as p falls says the map knows
+where the labels are wrong.  DIR: sqrt(u), the standard deviation over the copies, per image as <image stem>.npy (+inf where
+fewer than two copies saw the pixel).  Without these flags nothing else is computed or written."""
 import argparse
 import os
 import sys
@@ -75,6 +83,10 @@ parser.add_argument("--th_sweep_out", default=None, help="CSV file for the thres
 parser.add_argument("--guide_radius", type=int, default=None,
                     help="refine the SR score maps with the guided filter of this window radius (0..32) against the image")
 parser.add_argument("--guide_eps", type=float, default=None, help="the guided filter's regulariser (default 1e-3)")
+parser.add_argument("--coverages", default=None,
+                    help="comma-separated whole percentages (1..100, at most 16), e.g. 50,60,70,80,90,100: the risk-coverage curve too")
+parser.add_argument("--coverage_out", default=None, help="CSV file for the risk-coverage curve (default: <--out stem>_coverage.csv)")
+parser.add_argument("--uncertainty_dir", default=None, help="folder for sqrt(u) per image as .npy (needs --coverages)")
 parser.add_argument("--no_prune", action="store_true", help="solve every class, also those that win no pixel (same results)")
 
 
@@ -84,7 +96,8 @@ def main():
     from asr_amd import distributed as D
     from asr_amd.evaluation import (LABELMAP_KEYS, best_threshold_factors, dataset_miou, evaluate_labelmaps,
                                     write_confusion_csv, write_confusion_metrics_csv, write_labelmap_csv,
-                                    write_labelmap_threshold_csv, write_trimap_csv)
+                                    write_coverage_csv, write_labelmap_threshold_csv, write_trimap_csv)
+    from asr_amd.ops import check_coverages
     from asr_amd.model import DeeplabV3Plus
     from asr_amd.pipeline import HotPath
     from asr_amd.superresolution_scripts.optimizer import Optimizer
@@ -119,6 +132,14 @@ def main():
         guide = (args.guide_radius, 1e-3 if args.guide_eps is None else args.guide_eps)
         if not 0.0 < guide[1] < float("inf"):
             parser.error("--guide_eps must be finite and > 0")
+    if (args.coverage_out or args.uncertainty_dir) and not args.coverages:
+        parser.error("--coverage_out and --uncertainty_dir need --coverages")
+    covs = None
+    if args.coverages:
+        try:
+            covs = check_coverages([int(v) for v in args.coverages.split(",")])
+        except ValueError as e:
+            parser.error(f"--coverages: {e}")
     names = None
     if args.class_names:
         with open(args.class_names) as fh:
@@ -144,9 +165,11 @@ def main():
                              prune=not args.no_prune, save_dir=args.save_dir, band_widths=bands,
                              confusion_labels=args.confusion_labels if args.confusion_out else None,
                              **(dict(th_factors=factors) if factors is not None else {}),
-                             **(dict(guide=guide) if guide is not None else {}))
+                             **(dict(guide=guide) if guide is not None else {}),
+                             **(dict(coverages=covs, uncertainty_dir=args.uncertainty_dir) if covs is not None else {}))
     rows, counts = out[:2]
     confusion = out[4 if bands else 2] if args.confusion_out else None
+    sweep_rows, sweep_counts = out[-4:-2] if covs is not None else out[-2:]
     if rank == 0:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         write_labelmap_csv(args.out, counts, rows)
@@ -167,10 +190,20 @@ def main():
         if factors is not None:
             curve = args.th_sweep_out or os.path.splitext(os.path.abspath(args.out))[0] + "_thresholds.csv"
             os.makedirs(os.path.dirname(os.path.abspath(curve)), exist_ok=True)
-            write_labelmap_threshold_csv(curve, factors, out[-1], out[-2], counts, rows)
-            for key, (f, miou) in best_threshold_factors(factors, out[-1]).items():
+            write_labelmap_threshold_csv(curve, factors, sweep_counts, sweep_rows, counts, rows)
+            for key, (f, miou) in best_threshold_factors(factors, sweep_counts).items():
                 print(f"{key}: best th_factor {f!r} by dataset mIoU ({miou:.4f})")
             print(f"Wrote {curve}")
+        if covs is not None:
+            cov_csv = args.coverage_out or os.path.splitext(os.path.abspath(args.out))[0] + "_coverage.csv"
+            os.makedirs(os.path.dirname(os.path.abspath(cov_csv)), exist_ok=True)
+            write_coverage_csv(cov_csv, covs, out[-1], out[-2], counts=counts)
+            lo, hi = covs.index(min(covs)), covs.index(max(covs))
+            for j, key in enumerate(LABELMAP_KEYS):
+                if out[-1][j].any():
+                    print(f"{key}: dataset mIoU {dataset_miou(out[-1][j, lo]):.4f} on the {covs[lo]} % most certain pixels, "
+                          f"{dataset_miou(out[-1][j, hi]):.4f} at {covs[hi]} %")
+            print(f"Wrote {cov_csv}")
     if world > 1:
         torch.distributed.barrier()
         torch.distributed.destroy_process_group()
