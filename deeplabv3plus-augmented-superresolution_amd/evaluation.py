@@ -9,6 +9,7 @@ import numpy as np
 import torch
 
 from . import distributed as D, ops
+from .label_record import counts_name, label_fields, label_layout
 from .superresolution_scripts.augmentation_utils import _image_to_device
 from .superresolution_scripts.superres_utils import DATA_EXTS, EXTRA_SR_TYPES, compute_SR, load_SR_data, probe_SR_data
 from .utils import compute_IoU, load_image
@@ -223,71 +224,48 @@ LABELMAP_KEYS = ("standard", "aug", "max", "mean")
 LABELMAP_CSV_COLUMNS = ("standard_iou", "aug_iou", "max_iou", "mean_iou")
 
 
-def gather_labelmap_records(local_indices, local_miou, local_counts, num_images, local_band_miou=None,
-                            local_band_counts=None, num_widths=0, local_confusion=None, confusion_labels=0,
-                            local_sweep_miou=None, local_sweep_counts=None, num_factors=0, local_cov_miou=None,
-                            local_cov_counts=None, num_coverages=0):
-    """The one collective of evaluate_labelmaps.  local_miou: [n_local, 4] per-image Mean_IOU (LABELMAP_KEYS order);
-    local_counts: [n_local, 4, 3, 256] integer counts.  Returns on every rank (rows [num_images, 4] float64, NaN rows where
-    no rank reported; summed counts [4, 3, 256] int64).  The counts travel as float64 in the same all-gather as the rows:
-    exact below 2^53 pixels per bin.
+# the attribute names of LabelmapScores by field prefix: (per-image Mean_IOU rows, summed counts), or the counts alone
+_SCORE_ATTRS = {"": ("rows", "counts"), "band_": ("band_rows", "band_counts"), "confusion": ("confusion",),
+                "sweep_": ("sweep_rows", "sweep_counts"), "coverage_": ("cov_rows", "cov_counts")}
 
-    num_widths = B > 0: the trimap records ride in the same all-gather -- local_band_miou [n_local, 4, B], local_band_counts
-    [n_local, 4, B, 3, 256] -- and the result is (rows, counts, band_rows [num_images, 4, B], band_counts [4, B, 3, 256]).
 
-    confusion_labels = L > 0: the confusion matrices ride in it too, as the counts do -- local_confusion [n_local, 4, L+1, L+1]
-    -- and the result gains one more entry, the summed matrices [4, L+1, L+1] int64.
+class LabelmapScores(tuple):
+    """What gather_labelmap_records and evaluate_labelmaps return: the tuple
+    (rows, counts[, band_rows, band_counts][, confusion][, sweep_rows, sweep_counts][, cov_rows, cov_counts]), one or two
+    entries per field of label_record.label_fields that is on.  Every entry is also an attribute of that name, None when its
+    field is off."""
 
-    num_factors = T > 0: the threshold-sweep records of the three SR label maps (LABELMAP_KEYS[1:]) ride in it as well --
-    local_sweep_miou [n_local, 3, T], local_sweep_counts [n_local, 3, T, 3, 256] -- and the result ends in two more entries,
-    sweep_rows [num_images, 3, T] and the summed sweep_counts [3, T, 3, 256] int64.  The order of the result is
-    (rows, counts[, band_rows, band_counts][, confusion][, sweep_rows, sweep_counts][, cov_rows, cov_counts]).
+    def __new__(cls, items=(), names=()):
+        self = super().__new__(cls, items)
+        vars(self).update(dict.fromkeys(sum(_SCORE_ATTRS.values(), ()), None))
+        vars(self).update(zip(names, self))
+        return self
 
-    num_coverages = C > 0: the risk-coverage records of the four label maps ride in it last -- local_cov_miou [n_local, 4, C],
-    local_cov_counts [n_local, 4, C, 3, 256] -- and the result ends in cov_rows [num_images, 4, C] and the summed cov_counts
-    [4, C, 3, 256] int64."""
-    m = len(LABELMAP_KEYS)
-    c = int(num_coverages)
-    b = int(num_widths)
-    side = int(confusion_labels) + 1 if confusion_labels else 0
-    t = int(num_factors)
-    ms = m - 1                                      # the SR label maps: the standard map does not depend on the factor
+
+def gather_labelmap_records(local_indices, fields, local, num_images):
+    """The one collective of evaluate_labelmaps.  fields: label_record.label_fields(LABELMAP_KEYS, ...); local: {field:
+    (local_miou | None, local_counts)}, for each field the per-image Mean_IOU [n_local, len(keys), *shape[:-2]] (scored
+    fields only) and the integer counts [n_local, len(keys), *shape] of this rank's images.  Returns on every rank a
+    LabelmapScores: per scored field the rows [num_images, len(keys), *shape[:-2]] float64, NaN where no rank reported, and
+    per field the counts [len(keys), *shape] int64 summed over the images.  The counts travel as float64 in the same
+    all-gather as the rows, laid out by label_record.label_layout: exact below 2^53 pixels per bin."""
+    spans, width = label_layout(fields, with_miou=True)
     n_local = len(local_indices)
-    base = m + m * 768
-    conf = base + m * b + m * b * 768
-    sweep = conf + m * side * side
-    cov = sweep + ms * t + ms * t * 768
-    width = cov + m * c + m * c * 768
     rec = np.empty((n_local, width), dtype=np.float64)
     if n_local:
-        rec[:, :m] = np.asarray(local_miou, dtype=np.float64).reshape(n_local, m)
-        rec[:, m:base] = np.asarray(local_counts, dtype=np.int64).reshape(n_local, m * 768)
-        if b:
-            rec[:, base:base + m * b] = np.asarray(local_band_miou, dtype=np.float64).reshape(n_local, m * b)
-            rec[:, base + m * b:conf] = np.asarray(local_band_counts, dtype=np.int64).reshape(n_local, m * b * 768)
-        if side:
-            rec[:, conf:sweep] = np.asarray(local_confusion, dtype=np.int64).reshape(n_local, m * side * side)
-        if t:
-            rec[:, sweep:sweep + ms * t] = np.asarray(local_sweep_miou, dtype=np.float64).reshape(n_local, ms * t)
-            rec[:, sweep + ms * t:cov] = np.asarray(local_sweep_counts, dtype=np.int64).reshape(n_local, ms * t * 768)
-        if c:
-            rec[:, cov:cov + m * c] = np.asarray(local_cov_miou, dtype=np.float64).reshape(n_local, m * c)
-            rec[:, cov + m * c:] = np.asarray(local_cov_counts, dtype=np.int64).reshape(n_local, m * c * 768)
+        for f, (rows, cells) in zip(fields, spans):
+            miou, counts = local[f]
+            if rows is not None:
+                rec[:, rows] = np.asarray(miou, dtype=np.float64).reshape(n_local, -1)
+            rec[:, cells] = np.asarray(counts, dtype=np.int64).reshape(n_local, -1)
     table = D.all_gather_rows(local_indices, rec, num_images, width)
-    counts = np.nan_to_num(table[:, m:base]).astype(np.int64).reshape(num_images, m, 3, 256)
-    out = (table[:, :m], counts.sum(axis=0))
-    if b:
-        band_counts = np.nan_to_num(table[:, base + m * b:conf]).astype(np.int64).reshape(num_images, m, b, 3, 256)
-        out += (table[:, base:base + m * b].reshape(num_images, m, b), band_counts.sum(axis=0))
-    if side:
-        out += (np.nan_to_num(table[:, conf:sweep]).astype(np.int64).reshape(num_images, m, side, side).sum(axis=0),)
-    if t:
-        sweep_counts = np.nan_to_num(table[:, sweep + ms * t:cov]).astype(np.int64).reshape(num_images, ms, t, 3, 256)
-        out += (table[:, sweep:sweep + ms * t].reshape(num_images, ms, t), sweep_counts.sum(axis=0))
-    if c:
-        cov_counts = np.nan_to_num(table[:, cov + m * c:]).astype(np.int64).reshape(num_images, m, c, 3, 256)
-        out += (table[:, cov:cov + m * c].reshape(num_images, m, c), cov_counts.sum(axis=0))
-    return out
+    out, names = [], ()
+    for f, (rows, cells) in zip(fields, spans):
+        if rows is not None:
+            out.append(table[:, rows].reshape((num_images, len(f.keys)) + f.shape[:-2]))
+        out.append(np.nan_to_num(table[:, cells]).astype(np.int64).reshape((num_images, len(f.keys)) + f.shape).sum(axis=0))
+        names += _SCORE_ATTRS[f.prefix]
+    return LabelmapScores(out, names)
 
 
 def label_ious(counts):
@@ -307,9 +285,10 @@ def evaluate_labelmaps(path, image_paths, gt_paths, class_ids=tuple(range(1, 21)
                        img_size=(512, 512), rank=0, world=1, seed=1234, sr_types=("aug", "max", "mean"), prune=True,
                        save_dir=None, band_widths=None, band_ignore_label=255, confusion_labels=None, th_factors=None,
                        guide=None, coverages=None, uncertainty_dir=None):
-    """One fused label map per image and SR type (HotPath.run_image_labels) and its score.  Returns (rows, counts) on every
-    rank: rows [images, 4] per-image Mean_IOU in LABELMAP_KEYS order (the reference's per-image-then-mean convention; NaN for
-    an SR type that was not asked for), counts [4, 3, 256] int64 summed over the images (dataset_miou, label_ious).
+    """One fused label map per image and SR type (HotPath.run_image_labels) and its score.  Returns on every rank a
+    LabelmapScores, the tuple (rows, counts) plus what the options below append, every entry also an attribute by the name
+    given here: rows [images, 4] per-image Mean_IOU in LABELMAP_KEYS order (the reference's per-image-then-mean convention;
+    NaN for an SR type that was not asked for), counts [4, 3, 256] int64 summed over the images (dataset_miou, label_ious).
 
     The class set is the SAME for every image and is never read from the ground truth, so a class that is not in an image
     can be predicted there and costs IoU.  Draws: image g gets draw g of distributed.replay_augmentation_stream over the
@@ -323,16 +302,15 @@ def evaluate_labelmaps(path, image_paths, gt_paths, class_ids=tuple(range(1, 21)
     map that was not asked for.  They travel in the same all-gather.
 
     confusion_labels (an integer L in [1, 64]): the same loop also collects each label map's confusion matrix against the
-    ground truth (run_image_labels' confusion_labels) and the return value gains one more entry: the matrices [4, L+1, L+1]
-    int64 in LABELMAP_KEYS order, summed over the images (utils.metrics_from_confusion, write_confusion_csv), all zero for a
-    label map that was not asked for.  They travel in the same all-gather as well.
+    ground truth (run_image_labels' confusion_labels) and the return value gains one more entry, confusion: the matrices
+    [4, L+1, L+1] int64 in LABELMAP_KEYS order, summed over the images (utils.metrics_from_confusion, write_confusion_csv), all
+    zero for a label map that was not asked for.  They travel in the same all-gather as well.
 
     th_factors (T threshold factors, 1..64; not in slice_max mode): the same loop also collects the counts of every SR label
     map under every factor (run_image_labels' th_factors: one more pass over the SR outputs it already holds, no further
     forward pass or solve) and the return value ends in two more entries: sweep_rows [images, 3, T] per-image Mean_IOU and
     sweep_counts [3, T, 3, 256] int64 summed over the images, both in the order aug / max / mean and NaN / zero for an SR
-    type that was not asked for (write_labelmap_threshold_csv).  They travel in the same all-gather.  The whole return value is
-    (rows, counts[, band_rows, band_counts][, confusion][, sweep_rows, sweep_counts]).
+    type that was not asked for (write_labelmap_threshold_csv).  They travel in the same all-gather.
 
     guide ((radius, eps)): every SR score map is refined with the guided filter against its image before the fusion
     (run_image_labels' guide; img_size must be the SR output size).  The return value keeps its form.
@@ -345,55 +323,31 @@ def evaluate_labelmaps(path, image_paths, gt_paths, class_ids=tuple(range(1, 21)
     coverages): sqrt of each image's uncertainty map, the standard deviation over the copies, as <stem>.npy (float32 [H, W])."""
     if uncertainty_dir and coverages is None:
         raise ValueError("uncertainty_dir needs coverages: the uncertainty map is only built for the risk-coverage curve")
+    opts = path.label_options(tuple(img_size) + (3,), True, band_widths, band_ignore_label, confusion_labels, th_factors,
+                              guide, coverages, bool(uncertainty_dir))
     if uncertainty_dir:
         os.makedirs(uncertainty_dir, exist_ok=True)
-    covs = ops.check_coverages(coverages) if coverages is not None else None
-    n_c = len(covs) if covs else 0
     class_ids, params, mine = _class_set_run(class_ids, image_paths, gt_paths, rank, world, num_aug=num_aug,
                                              angle_max=angle_max, shift_max=shift_max, seed=seed)
     n_img = len(image_paths)
     starts = D.adam_class_starts(np.ones((n_img, len(class_ids)), dtype=bool), path.sr.num_iter, path.mode)
     if save_dir:
         os.makedirs(save_dir, exist_ok=True)
-    bands = ops.check_band_widths(band_widths) if band_widths is not None else None
-    n_b = len(bands) if bands else 0
-    n_conf = ops.check_confusion_labels(confusion_labels) if confusion_labels is not None else 0
-    factors = None if th_factors is None else [float(f) for f in np.asarray(th_factors, dtype=np.float64).reshape(-1)]
-    n_t = len(factors) if factors is not None else 0
-    if factors is not None and not 1 <= n_t <= ops.MAX_LABEL_SWEEP_FACTORS:
-        raise ValueError(f"{n_t} threshold factors (1..{ops.MAX_LABEL_SWEEP_FACTORS})")
-    mious, counts, band_mious, band_counts, confusion, sweep_mious, sweep_counts = [], [], [], [], [], [], []
-    cov_mious, cov_counts = [], []
+    fields = label_fields(LABELMAP_KEYS, *opts.sizes)
+    local = {f: ([], []) for f in fields}
     for g in mine:
         image, gt = _image_and_labels_on_device(image_paths[g], gt_paths[g], img_size)
         angles, shifts = params[g]
-        extra = dict(band_widths=bands, band_ignore_label=band_ignore_label) if bands else {}
-        if n_conf:
-            extra["confusion_labels"] = n_conf
-        if n_t:
-            extra["th_factors"] = factors
-        if guide is not None:
-            extra["guide"] = guide
-        if n_c:
-            extra["coverages"] = covs
-            if uncertainty_dir:
-                extra["keep_uncertainty"] = True
         res = path.run_image_labels(image, angles, shifts, class_ids, gt_dev=gt, sr_types=sr_types, prune=prune,
-                                    adam_starts={c: int(starts[g, k]) for k, c in enumerate(class_ids)}, **extra)
-        mious.append([res["Mean_IOU"].get(key, np.nan) for key in LABELMAP_KEYS])
-        counts.append([res["counts"].get(key, np.zeros((3, 256), np.int64)) for key in LABELMAP_KEYS])
-        if bands:
-            band_mious.append([res["band_Mean_IOU"].get(key, np.full(n_b, np.nan)) for key in LABELMAP_KEYS])
-            band_counts.append([res["band_counts"].get(key, np.zeros((n_b, 3, 256), np.int64)) for key in LABELMAP_KEYS])
-        if n_conf:
-            confusion.append([res["confusion"].get(key, np.zeros((n_conf + 1, n_conf + 1), np.int64)) for key in LABELMAP_KEYS])
-        if n_t:
-            sweep_mious.append([res["sweep_Mean_IOU"].get(key, np.full(n_t, np.nan)) for key in LABELMAP_KEYS[1:]])
-            sweep_counts.append([res["sweep_counts"].get(key, np.zeros((n_t, 3, 256), np.int64)) for key in LABELMAP_KEYS[1:]])
-        if n_c:
-            cov_mious.append([res["coverage_Mean_IOU"].get(key, np.full(n_c, np.nan)) for key in LABELMAP_KEYS])
-            cov_counts.append([res["coverage_counts"].get(key, np.zeros((n_c, 3, 256), np.int64)) for key in LABELMAP_KEYS])
-        if n_c and uncertainty_dir:
+                                    adam_starts={c: int(starts[g, k]) for k, c in enumerate(class_ids)},
+                                    band_widths=opts.bands, band_ignore_label=band_ignore_label,
+                                    confusion_labels=opts.n_conf or None, th_factors=opts.factors, guide=opts.guide,
+                                    coverages=opts.covs, keep_uncertainty=bool(uncertainty_dir))
+        for f, (mious, counts) in local.items():        # a label map that was not produced: NaN Mean_IOU, zero counts
+            if f.scored:
+                mious.append([res[f.prefix + "Mean_IOU"].get(key, np.full(f.shape[:-2], np.nan)) for key in f.keys])
+            counts.append([res[counts_name(f)].get(key, np.zeros(f.shape, np.int64)) for key in f.keys])
+        if uncertainty_dir:
             np.save(os.path.join(uncertainty_dir, os.path.splitext(os.path.basename(image_paths[g]))[0] + ".npy"),
                     torch.sqrt(res["uncertainty"]).cpu().numpy())
         if save_dir:
@@ -403,10 +357,24 @@ def evaluate_labelmaps(path, image_paths, gt_paths, class_ids=tuple(range(1, 21)
                 if key in res:
                     Image.fromarray(res[key].cpu().numpy().astype(np.uint8), mode="L").save(
                         os.path.join(save_dir, f"{stem}_{key}.png"))
-    return gather_labelmap_records(mine, mious, counts, n_img, band_mious if bands else None, band_counts if bands else None,
-                                   n_b, confusion if n_conf else None, n_conf, sweep_mious if n_t else None,
-                                   sweep_counts if n_t else None, n_t, cov_mious if n_c else None,
-                                   cov_counts if n_c else None, n_c)
+    return gather_labelmap_records(mine, fields, local, n_img)
+
+
+def _miou_cells(made, counts, image_mious):
+    """The two CSV cells of one label map: the dataset mIoU of its counts [3, 256] summed over the images, and np.mean of its
+    per-image Mean_IOU [images] (a NaN image propagates; "nan" without images).  made False -- the label map was not
+    produced, its counts are all zero -- both are "nan"."""
+    if not made:
+        return ["nan", "nan"]
+    return [repr(dataset_miou(counts)), repr(float(np.mean(image_mious))) if len(image_mious) else "nan"]
+
+
+def _counted_truth_pixels(counts, ignore_label):
+    """The ground-truth pixels that the whole-image counts [4, 3, 256] counted, ignore_label's (-1 or None: none) taken out."""
+    truth = np.asarray(counts, dtype=np.int64).reshape(len(LABELMAP_KEYS), 3, 256)[:, 0].max(axis=0).copy()
+    if ignore_label is not None and 0 <= int(ignore_label) <= 255:
+        truth[int(ignore_label)] = 0
+    return int(truth.sum())
 
 
 def write_labelmap_csv(path, counts, rows):
@@ -447,18 +415,14 @@ def write_labelmap_threshold_csv(path, factors, sweep_counts, sweep_rows, counts
     sweep_rows = np.asarray(sweep_rows, dtype=np.float64).reshape(-1, ms, len(fs))
     counts = np.asarray(counts, dtype=np.int64).reshape(len(LABELMAP_KEYS), 3, 256)
     rows = np.asarray(rows, dtype=np.float64).reshape(-1, len(LABELMAP_KEYS))
-    standard = ["nan", "nan"]
-    if counts[0].any():
-        standard = [repr(dataset_miou(counts[0])), repr(float(np.mean(rows[:, 0]))) if len(rows) else "nan"]
+    standard = _miou_cells(counts[0].any(), counts[0], rows[:, 0])
     with open(path, "w", newline="") as fh:
         wr = csv.writer(fh, quoting=csv.QUOTE_ALL, lineterminator="\n")
         wr.writerow(THRESHOLD_CSV_COLUMNS)
         for j, f in enumerate(fs):
             cells = []
-            for i in range(ms):
-                made = bool(sweep_counts[i].any())          # an SR type that was not asked for carries all-zero counts
-                cells.append(repr(dataset_miou(sweep_counts[i, j])) if made else "nan")
-                cells.append(repr(float(np.mean(sweep_rows[:, i, j]))) if made and len(sweep_rows) else "nan")
+            for i in range(ms):                             # an SR type that was not asked for carries all-zero counts
+                cells += _miou_cells(sweep_counts[i].any(), sweep_counts[i, j], sweep_rows[:, i, j])
             wr.writerow([repr(f)] + cells + standard)
 
 
@@ -494,21 +458,14 @@ def write_trimap_csv(path, widths, band_counts, band_rows, counts=None, ignore_l
     m = len(LABELMAP_KEYS)
     band_counts = np.asarray(band_counts, dtype=np.int64).reshape(m, len(ws), 3, 256)
     band_rows = np.asarray(band_rows, dtype=np.float64).reshape(-1, m, len(ws))
-    total = None
-    if counts is not None:
-        truth = np.asarray(counts, dtype=np.int64).reshape(m, 3, 256)[:, 0].max(axis=0).copy()
-        if ignore_label is not None and 0 <= int(ignore_label) <= 255:
-            truth[int(ignore_label)] = 0
-        total = int(truth.sum())
+    total = _counted_truth_pixels(counts, ignore_label) if counts is not None else None
     with open(path, "w", newline="") as fh:
         wr = csv.writer(fh, quoting=csv.QUOTE_ALL, lineterminator="\n")
         wr.writerow(("Name",) + TRIMAP_CSV_COLUMNS + ("band_pixels", "band_share", "n"))
         for b, width in enumerate(ws):
             cells = []
-            for j in range(m):
-                made = bool(band_counts[j].any())           # a label map that was not asked for carries all-zero counts
-                cells.append(repr(dataset_miou(band_counts[j, b])) if made else "nan")
-                cells.append(repr(float(np.mean(band_rows[:, j, b]))) if made and len(band_rows) else "nan")
+            for j in range(m):                              # a label map that was not asked for carries all-zero counts
+                cells += _miou_cells(band_counts[j].any(), band_counts[j, b], band_rows[:, j, b])
             pixels = int(band_counts[:, b, 0].max(axis=0).sum())
             share = repr(pixels / total) if total else "nan"
             wr.writerow([f"w={width}"] + cells + [str(pixels), share, str(len(band_rows))])
@@ -534,10 +491,7 @@ def write_coverage_csv(path, percents, cov_counts, cov_rows, counts=None, ignore
     cov_rows = np.asarray(cov_rows, dtype=np.float64).reshape(-1, m, len(ps))
     total = None
     if counts is not None:
-        truth = np.asarray(counts, dtype=np.int64).reshape(m, 3, 256)[:, 0].max(axis=0).copy()
-        if ignore_label is not None and 0 <= int(ignore_label) <= 255:
-            truth[int(ignore_label)] = 0
-        total = int(truth.sum())
+        total = _counted_truth_pixels(counts, ignore_label)
     elif 100 in ps:
         total = int(cov_counts[:, ps.index(100), 0].max(axis=0).sum())
     with open(path, "w", newline="") as fh:
@@ -547,8 +501,7 @@ def write_coverage_csv(path, percents, cov_counts, cov_rows, counts=None, ignore
             cells = []
             for j in range(m):
                 made = bool(cov_counts[j].any())            # a label map that was not asked for carries all-zero counts
-                cells.append(repr(dataset_miou(cov_counts[j, b])) if made else "nan")
-                cells.append(repr(float(np.mean(cov_rows[:, j, b]))) if made and len(cov_rows) else "nan")
+                cells += _miou_cells(made, cov_counts[j, b], cov_rows[:, j, b])
                 cells.append(repr(int(cov_counts[j, b, 0].sum()) / total) if made and total else "nan")
             wr.writerow([str(p)] + cells + [str(len(cov_rows))])
 

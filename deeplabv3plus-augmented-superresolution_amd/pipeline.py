@@ -10,11 +10,13 @@ Used by bench.py, the scripts and the smoke test.
 from __future__ import annotations
 
 import contextlib
+from collections import namedtuple
 
 import numpy as np
 import torch
 
 from . import ops
+from .label_record import counts_name, label_fields, label_layout
 from .superresolution_scripts import augmentation_utils as au
 from .utils import (coverage_edges, coverage_retained, iou_from_counts, mean_iou_from_counts, opm_scales,
                     uncertainty_map)
@@ -353,25 +355,8 @@ class HotPath:
         moments were taken of, None when no class was solved).  With coverages=None nothing else is launched and nothing
         else returned."""
         ids = [int(c) for c in class_ids]
-        covs = ops.check_coverages(coverages) if coverages is not None else None
-        if covs is not None and gt_dev is None:
-            raise ValueError("coverages needs gt_dev: the risk-coverage curve scores the label maps against a ground truth")
-        if keep_uncertainty and covs is None:
-            raise ValueError("keep_uncertainty without coverages: the uncertainty map is only built for the risk-coverage curve")
-        if guide is not None:
-            try:
-                g_radius, g_eps = guide
-            except (TypeError, ValueError):
-                raise ValueError(f"guide must be (radius, eps), got {guide!r}") from None
-            g_radius, g_eps = ops.check_guided(g_radius, g_eps)
-            if image_dev.dim() != 3 or tuple(image_dev.shape) != tuple(self.sr.output_size) + (3,):
-                raise ValueError(f"guide needs the image as [H, W, 3] at the SR output size {tuple(self.sr.output_size)}, got "
-                                 f"{tuple(image_dev.shape)}")
-        factors = self._check_th_factors(th_factors, gt_dev) if th_factors is not None else None
-        bands = ops.check_band_widths(band_widths) if band_widths is not None else None
-        n_conf = ops.check_confusion_labels(confusion_labels) if confusion_labels is not None else 0
-        if n_conf and gt_dev is None:
-            raise ValueError("confusion_labels needs gt_dev: a confusion matrix is counted against a ground truth")
+        opts = self.label_options(None if image_dev is None else tuple(image_dev.shape), gt_dev is not None, band_widths,
+                                  band_ignore_label, confusion_labels, th_factors, guide, coverages, keep_uncertainty)
         if any(c == 0 for c in ids):
             raise ValueError(f"class id 0 is the fallback label, never a candidate: {ids}")
         unknown = [t for t in sr_types if t not in ("aug", "max", "mean")]
@@ -401,23 +386,19 @@ class HotPath:
         if kept:
             y, ymax = self._normalise(y, ymax)
         scores = {}
+        fshifts = self._sr_frame(image_dev, shifts)
         with self._sr_stage_timed(profile):
             gt = self._gt_int32(gt_dev) if gt_dev is not None else None
-            tally = None
-            if gt is not None:
-                tally = _LabelCounts(keys, len(bands) if bands else 0, image_dev.device, n_conf,
-                                     sr_types if factors is not None else (), len(factors) if factors is not None else 0,
-                                     len(covs) if covs else 0)
-            f_dev = ops.to_device(factors, device=image_dev.device) if factors is not None and kept and sr_types else None
+            tally = _LabelCounts(label_fields(keys, *opts.sizes), image_dev.device) if gt is not None else None
+            f_dev = ops.to_device(opts.factors, device=image_dev.device) if opts.factors is not None and kept and sr_types else None
             if tally is not None and want_standard:
                 tally.counts[0] = ops.class_counts(gt, maps[0])[0]
             g_state = None
-            if guide is not None and kept and sr_types:
+            if opts.guide is not None and kept and sr_types:
                 g_image = image_dev.to(torch.float32).contiguous()
-                g_state = ops.guided_prepare(g_image, g_radius, g_eps)
+                g_state = ops.guided_prepare(g_image, *opts.guide)
             if kept:
-                for t, tgt, tmax in self._classes_scores(y, ymax, angles, self._sr_frame(image_dev, shifts),
-                                                         [starts[k] for k in kept], sr_types):
+                for t, tgt, tmax in self._classes_scores(y, ymax, angles, fshifts, [starts[k] for k in kept], sr_types):
                     j = keys.index(t)
                     if g_state is not None:
                         ops.guided_apply(g_state, g_image, tgt, out=tgt)
@@ -436,21 +417,10 @@ class HotPath:
                 maps[first:].zero_()
                 if gt is not None:
                     tally.counts[first:] = ops.class_counts(gt, maps[first])[0]          # one count serves every (equal) zero map
-                    if factors is not None:
+                    if opts.factors is not None:
                         tally.sweep[:] = tally.counts[first]                             # ... under every factor
             self._advance_past(starts, adam_starts, sr_types)
-            if bands is not None and gt is not None:
-                r_max = max(bands)
-                ops.band_class_counts(gt, maps, ops.boundary_dist2(gt.view(out_hw[0], out_hw[1]), r_max), bands, r_max,
-                                      -1 if band_ignore_label is None else int(band_ignore_label), out=tally.band)
-            if n_conf:
-                ops.confusion_counts(gt, maps, n_conf, out=tally.confusion)
-            u_map = None
-            if covs is not None:
-                u_map = self._uncertainty(y if kept else None, angles, self._sr_frame(image_dev, shifts), out_hw, image_dev.device)
-                edges = coverage_edges(u_map, gt, covs, ignore_label=255)
-                ops.binned_class_counts(gt, maps, u_map, edges, ignore_label=255, out=tally.coverage)
-                tally.retained[:] = coverage_retained(u_map, gt, edges, ignore_label=255)
+            u_map = self._score_label_maps(tally, gt, maps, opts, y if kept else None, angles, fshifts)
         res = {key: maps[j] for j, key in enumerate(keys)}
         res["solved_ids"] = solved
         if tally is not None:
@@ -462,6 +432,62 @@ class HotPath:
             res["uncertainty_stacks"] = y if kept else None
         return res
 
+    def label_options(self, image_shape, has_gt, band_widths=None, band_ignore_label=255, confusion_labels=None,
+                      th_factors=None, guide=None, coverages=None, keep_uncertainty=False):
+        """The scoring options of run_image_labels, checked and normalised into one LabelOptions; ValueError as its docstring
+        says.  Host only, and nothing of self is read that the options given do not need (mode: th_factors; sr: guide).
+        image_shape: the image's shape or None; has_gt: a ground truth comes with it."""
+        covs = ops.check_coverages(coverages) if coverages is not None else None
+        if covs is not None and not has_gt:
+            raise ValueError("coverages needs gt_dev: the risk-coverage curve scores the label maps against a ground truth")
+        if keep_uncertainty and covs is None:
+            raise ValueError("keep_uncertainty without coverages: the uncertainty map is only built for the risk-coverage curve")
+        if guide is not None:
+            try:
+                g_radius, g_eps = guide
+            except (TypeError, ValueError):
+                raise ValueError(f"guide must be (radius, eps), got {guide!r}") from None
+            guide = ops.check_guided(g_radius, g_eps)
+            if image_shape != tuple(self.sr.output_size) + (3,):
+                raise ValueError(f"guide needs the image as [H, W, 3] at the SR output size {tuple(self.sr.output_size)}, got "
+                                 f"{image_shape}")
+        factors = None
+        if th_factors is not None:
+            if not has_gt:
+                raise ValueError("th_factors needs gt_dev: the sweep counts every factor's label map against a ground truth")
+            if self.mode == "slice_max":
+                raise ValueError("th_factors in slice_max mode: a class passes against its max map there, the threshold plays no "
+                                 "part, so there is nothing to sweep")
+            factors = np.asarray(th_factors, dtype=np.float32).reshape(-1)
+            if not 1 <= factors.size <= ops.MAX_LABEL_SWEEP_FACTORS:
+                raise ValueError(f"{factors.size} threshold factors (1..{ops.MAX_LABEL_SWEEP_FACTORS})")
+        bands = ops.check_band_widths(band_widths) if band_widths is not None else None
+        n_conf = ops.check_confusion_labels(confusion_labels) if confusion_labels is not None else 0
+        if n_conf and not has_gt:
+            raise ValueError("confusion_labels needs gt_dev: a confusion matrix is counted against a ground truth")
+        band_ignore = -1 if bands is None or band_ignore_label is None else int(band_ignore_label)
+        sizes = (len(bands or ()), n_conf, 0 if factors is None else factors.size, len(covs or ()))
+        return LabelOptions(bands, band_ignore, n_conf, factors, guide, covs, sizes)
+
+    def _score_label_maps(self, tally, gt, maps, opts, stacks, angles, fshifts):
+        """The scores of the finished label maps [M, H, W] against gt, into tally: trimap bands, confusion matrices, risk-coverage
+        (stacks: the [K', N, h, w] class stacks the solver read, None when no class was solved).  Returns the uncertainty map,
+        None without coverages."""
+        out_hw = tuple(maps.shape[1:])
+        if opts.bands is not None and gt is not None:
+            r_max = max(opts.bands)
+            ops.band_class_counts(gt, maps, ops.boundary_dist2(gt.view(out_hw), r_max), opts.bands, r_max, opts.band_ignore,
+                                  out=tally.band)
+        if opts.n_conf:
+            ops.confusion_counts(gt, maps, opts.n_conf, out=tally.confusion)
+        if opts.covs is None:
+            return None
+        u_map = self._uncertainty(stacks, angles, fshifts, out_hw, maps.device)
+        edges = coverage_edges(u_map, gt, opts.covs, ignore_label=255)
+        ops.binned_class_counts(gt, maps, u_map, edges, ignore_label=255, out=tally.coverage)
+        tally.retained[:] = coverage_retained(u_map, gt, edges, ignore_label=255)
+        return u_map
+
     def _uncertainty(self, y, angles, fshifts, out_hw, device):
         """utils.uncertainty_map of the class stacks y [K', N, h, w] (None: no class): one moments launch under frame coverage."""
         if y is None:
@@ -472,18 +498,6 @@ class HotPath:
         ones = torch.ones(tuple(y.shape[2:]), dtype=torch.float32, device=y.device)
         mom = ops.realign_moments(y, tr, rot, out_hw, want=("var", "nv"), wgt=ones, valid_min=0.5)
         return uncertainty_map(mom["var"], mom["nv"], opm_scales(range(y.shape[0]), self.mode, normalised=True))
-
-    def _check_th_factors(self, th_factors, gt_dev):
-        """The factors of a label-map threshold sweep as a float32 array (1..ops.MAX_LABEL_SWEEP_FACTORS of them)."""
-        if gt_dev is None:
-            raise ValueError("th_factors needs gt_dev: the sweep counts every factor's label map against a ground truth")
-        if self.mode == "slice_max":
-            raise ValueError("th_factors in slice_max mode: a class passes against its max map there, the threshold plays no "
-                             "part, so there is nothing to sweep")
-        f = np.asarray(th_factors, dtype=np.float32).reshape(-1)
-        if not 1 <= f.size <= ops.MAX_LABEL_SWEEP_FACTORS:
-            raise ValueError(f"{f.size} threshold factors (1..{ops.MAX_LABEL_SWEEP_FACTORS})")
-        return f
 
     def _finish(self, res):
         res.pop("_masks", None)          # the rows stay alive through the per-key views
@@ -514,55 +528,39 @@ class HotPath:
                          iou("max", False), iou("mean", False)], dtype=np.float64)
 
 
-class _LabelCounts:
-    """The counts of run_image_labels on the device, one int64 allocation so that they reach the host in one copy: per label
-    map (in the order of keys) the [3, 256] whole-image counts, then, with B band widths, its [B, 3, 256] band counts, then,
-    with L confusion labels, its [L+1, L+1] confusion matrix; last, with T threshold factors, the [T, 3, 256] sweep counts of
-    each SR type in sweep_keys; after those, with C coverages, each label map's [C, 3, 256] coverage counts and C + 1 pixel
-    totals (the counted pixels each coverage retained, then all of them)."""
+# HotPath.label_options' value: band widths | None and the label left out of the bands (-1: none), confusion labels (0: off),
+# float32 threshold factors | None, the guide's (radius, eps) | None, coverages | None; sizes: (B, L, T, C), 0 where off
+LabelOptions = namedtuple("LabelOptions", "bands band_ignore n_conf factors guide covs sizes")
 
-    def __init__(self, keys, n_bands, device, n_conf=0, sweep_keys=(), n_factors=0, n_cov=0):
-        self.keys, self.n_bands, self.n_conf, self.n_cov = keys, n_bands, n_conf, n_cov
-        self.sweep_keys, self.n_factors = list(sweep_keys), n_factors
-        self._split = len(keys) * 768
-        self._conf = self._split * (1 + n_bands)
-        cells = (n_conf + 1) ** 2 if n_conf else 0
-        self._sweep = self._conf + len(keys) * cells
-        self._cov = self._sweep + len(self.sweep_keys) * n_factors * 768
-        self._ret = self._cov + len(keys) * n_cov * 768
-        self._buf = torch.empty(self._ret + (n_cov + 1 if n_cov else 0), dtype=torch.int64, device=device)
-        self.counts = self._buf[:self._split].view(len(keys), 3, 256)
-        self.band = self._buf[self._split:self._conf]   # [len(keys), B, 3, 256], flat: ops.band_class_counts's out
-        self.confusion = self._buf[self._conf:self._sweep]      # [len(keys), L+1, L+1], flat: ops.confusion_counts's out
-        self.sweep = self._buf[self._sweep:self._cov].view(len(self.sweep_keys), n_factors, 3, 256)      # row i: ops.fuse_labels_sweep_counts's out
-        self.coverage = self._buf[self._cov:self._ret]  # [len(keys), C, 3, 256], flat: ops.binned_class_counts's out
-        self.retained = self._buf[self._ret:]           # [C + 1]: utils.coverage_retained
+
+class _LabelCounts:
+    """The counts of run_image_labels on the device, one int64 allocation so that they reach the host in one copy: the fields
+    of label_record.label_layout one after another; after them, with C coverages, C + 1 pixel totals (the counted pixels each
+    coverage retained, then all of them).  Each field that is on is the attribute of its prefix's name -- counts, band,
+    confusion, sweep, coverage -- as [len(keys), *shape]: what the ops.*_counts(out=...) call of that score writes into."""
+
+    def __init__(self, fields, device):
+        spans, end = label_layout(fields, with_miou=False)
+        self._fields = [(f, at) for f, (_, at) in zip(fields, spans)]
+        n_cov = next((f.shape[0] for f in fields if f.prefix == "coverage_"), 0)
+        self._buf = torch.empty(end + (n_cov + 1 if n_cov else 0), dtype=torch.int64, device=device)
+        for f, at in self._fields:
+            setattr(self, f.prefix.rstrip("_") or "counts", self._buf[at].view((len(f.keys),) + f.shape))
+        self.retained = self._buf[end:]                         # [C + 1]: utils.coverage_retained
 
     def to_host(self):
-        """The "counts" / "Mean_IOU" (and "band_counts" / "band_Mean_IOU") entries of the result."""
+        """The count and Mean_IOU entries of the result, by field, and with coverages "coverage_share"."""
         host = self._buf.cpu().numpy()
-        counts = host[:self._split].reshape(len(self.keys), 3, 256)
-        res = {"counts": {key: counts[j] for j, key in enumerate(self.keys)},
-               "Mean_IOU": {key: mean_iou_from_counts(counts[j]) for j, key in enumerate(self.keys)}}
-        if self.n_bands:
-            band = host[self._split:self._conf].reshape(len(self.keys), self.n_bands, 3, 256)
-            res["band_counts"] = {key: band[j] for j, key in enumerate(self.keys)}
-            res["band_Mean_IOU"] = {key: np.array([mean_iou_from_counts(c) for c in band[j]], dtype=np.float64)
-                                    for j, key in enumerate(self.keys)}
-        if self.n_conf:
-            conf = host[self._conf:self._sweep].reshape(len(self.keys), self.n_conf + 1, self.n_conf + 1)
-            res["confusion"] = {key: conf[j] for j, key in enumerate(self.keys)}
-        if self.n_factors:
-            sweep = host[self._sweep:self._cov].reshape(len(self.sweep_keys), self.n_factors, 3, 256)
-            res["sweep_counts"] = {t: sweep[i] for i, t in enumerate(self.sweep_keys)}
-            res["sweep_Mean_IOU"] = {t: np.array([mean_iou_from_counts(c) for c in sweep[i]], dtype=np.float64)
-                                     for i, t in enumerate(self.sweep_keys)}
-        if self.n_cov:
-            cov = host[self._cov:self._ret].reshape(len(self.keys), self.n_cov, 3, 256)
-            res["coverage_counts"] = {key: cov[j] for j, key in enumerate(self.keys)}
-            res["coverage_Mean_IOU"] = {key: np.array([mean_iou_from_counts(c) for c in cov[j]], dtype=np.float64)
-                                        for j, key in enumerate(self.keys)}
-            ret = host[self._ret:]
+        res = {}
+        for f, at in self._fields:
+            counts = host[at].reshape((len(f.keys),) + f.shape)
+            res[counts_name(f)] = {key: counts[j] for j, key in enumerate(f.keys)}
+            if f.scored:
+                miou = np.array([mean_iou_from_counts(c) for c in counts.reshape(-1, 3, 256)], dtype=np.float64)
+                miou = miou.reshape((len(f.keys),) + f.shape[:-2])
+                res[f.prefix + "Mean_IOU"] = {key: miou[j] if miou[j].ndim else float(miou[j]) for j, key in enumerate(f.keys)}
+        if self.retained.numel():
+            ret = host[-self.retained.numel():]
             with np.errstate(divide="ignore", invalid="ignore"):
                 res["coverage_share"] = np.float64(ret[:-1]) / np.float64(ret[-1])
         return res

@@ -119,10 +119,11 @@ def main():
         factors = [float(v) for v in TH_FACTORS]
     if args.th_sweep_out and factors is None:
         parser.error("--th_sweep_out needs --th_factors or --th_sweep")
-    if factors is not None and not 1 <= len(factors) <= 64:
-        parser.error("--th_factors holds 1..64 factors")
-    if factors is not None and args.mode == "slice_max":
-        parser.error("--th_factors / --th_sweep: in slice_max mode the threshold plays no part, there is nothing to sweep")
+    if factors is not None:
+        try:                # their number, and no sweep in slice_max mode: the library's own check, ahead of the model
+            HotPath(None, None, mode=args.mode).label_options(None, True, th_factors=factors)
+        except ValueError as e:
+            parser.error(f"--th_factors / --th_sweep: {e}")
     if args.guide_eps is not None and args.guide_radius is None:
         parser.error("--guide_eps needs --guide_radius")
     guide = None
@@ -167,9 +168,7 @@ def main():
                              **(dict(th_factors=factors) if factors is not None else {}),
                              **(dict(guide=guide) if guide is not None else {}),
                              **(dict(coverages=covs, uncertainty_dir=args.uncertainty_dir) if covs is not None else {}))
-    rows, counts = out[:2]
-    confusion = out[4 if bands else 2] if args.confusion_out else None
-    sweep_rows, sweep_counts = out[-4:-2] if covs is not None else out[-2:]
+    rows, counts = out.rows, out.counts
     if rank == 0:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         write_labelmap_csv(args.out, counts, rows)
@@ -179,30 +178,30 @@ def main():
         if bands:
             trimap = args.trimap_out or os.path.splitext(os.path.abspath(args.out))[0] + "_trimap.csv"
             os.makedirs(os.path.dirname(os.path.abspath(trimap)), exist_ok=True)
-            write_trimap_csv(trimap, bands, out[3], out[2], counts=counts)
+            write_trimap_csv(trimap, bands, out.band_counts, out.band_rows, counts=counts)
             print(f"Wrote {trimap}")
         if args.confusion_out:
             metrics = os.path.splitext(os.path.abspath(args.confusion_out))[0] + "_metrics.csv"
             os.makedirs(os.path.dirname(os.path.abspath(args.confusion_out)), exist_ok=True)
-            write_confusion_csv(args.confusion_out, confusion, names)
-            write_confusion_metrics_csv(metrics, confusion, names)
+            write_confusion_csv(args.confusion_out, out.confusion, names)
+            write_confusion_metrics_csv(metrics, out.confusion, names)
             print(f"Wrote {args.confusion_out} and {metrics}")
         if factors is not None:
             curve = args.th_sweep_out or os.path.splitext(os.path.abspath(args.out))[0] + "_thresholds.csv"
             os.makedirs(os.path.dirname(os.path.abspath(curve)), exist_ok=True)
-            write_labelmap_threshold_csv(curve, factors, sweep_counts, sweep_rows, counts, rows)
-            for key, (f, miou) in best_threshold_factors(factors, sweep_counts).items():
+            write_labelmap_threshold_csv(curve, factors, out.sweep_counts, out.sweep_rows, counts, rows)
+            for key, (f, miou) in best_threshold_factors(factors, out.sweep_counts).items():
                 print(f"{key}: best th_factor {f!r} by dataset mIoU ({miou:.4f})")
             print(f"Wrote {curve}")
         if covs is not None:
             cov_csv = args.coverage_out or os.path.splitext(os.path.abspath(args.out))[0] + "_coverage.csv"
             os.makedirs(os.path.dirname(os.path.abspath(cov_csv)), exist_ok=True)
-            write_coverage_csv(cov_csv, covs, out[-1], out[-2], counts=counts)
+            write_coverage_csv(cov_csv, covs, out.cov_counts, out.cov_rows, counts=counts)
             lo, hi = covs.index(min(covs)), covs.index(max(covs))
             for j, key in enumerate(LABELMAP_KEYS):
-                if out[-1][j].any():
-                    print(f"{key}: dataset mIoU {dataset_miou(out[-1][j, lo]):.4f} on the {covs[lo]} % most certain pixels, "
-                          f"{dataset_miou(out[-1][j, hi]):.4f} at {covs[hi]} %")
+                if out.cov_counts[j].any():
+                    print(f"{key}: dataset mIoU {dataset_miou(out.cov_counts[j, lo]):.4f} on the {covs[lo]} % most certain pixels, "
+                          f"{dataset_miou(out.cov_counts[j, hi]):.4f} at {covs[hi]} %")
             print(f"Wrote {cov_csv}")
     if world > 1:
         torch.distributed.barrier()

@@ -140,9 +140,10 @@ def test_gather_appends_the_coverage_records_last():
     counts = rng.integers(0, 100, (n, 4, 3, 256))
     sweep_m, sweep_c = rng.uniform(size=(n, 3, T)), rng.integers(0, 100, (n, 3, T, 3, 256))
     cov_m, cov_c = rng.uniform(size=(n, 4, C)), rng.integers(0, 100, (n, 4, C, 3, 256))
-    plain = E.gather_labelmap_records(list(range(n)), miou, counts, n, local_sweep_miou=sweep_m, local_sweep_counts=sweep_c, num_factors=T)
-    out = E.gather_labelmap_records(list(range(n)), miou, counts, n, local_sweep_miou=sweep_m, local_sweep_counts=sweep_c, num_factors=T,
-                                    local_cov_miou=cov_m, local_cov_counts=cov_c, num_coverages=C)
+    local = {"": (miou, counts), "sweep_": (sweep_m, sweep_c), "coverage_": (cov_m, cov_c)}
+    gather = lambda fields: E.gather_labelmap_records(list(range(n)), fields, {f: local[f.prefix] for f in fields}, n)
+    plain = gather(E.label_fields(E.LABELMAP_KEYS, n_factors=T))
+    out = gather(E.label_fields(E.LABELMAP_KEYS, n_factors=T, n_cov=C))
     assert len(plain) == 4 and len(out) == 6
     for a, b in zip(plain, out[:4]):
         assert np.array_equal(a, b)

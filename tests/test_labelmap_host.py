@@ -256,7 +256,8 @@ def _worker(rank, world, port, num_images, q):
         D.init_from_env(backend="gloo")
     mine = D.shard_indices(num_images, rank, world)
     recs = [_record(g) for g in mine]
-    rows, total = E.gather_labelmap_records(mine, [r[0] for r in recs], [r[1] for r in recs], num_images)
+    fields = E.label_fields(E.LABELMAP_KEYS)
+    rows, total = E.gather_labelmap_records(mine, fields, {fields[0]: ([r[0] for r in recs], [r[1] for r in recs])}, num_images)
     q.put((rank, rows, total))
     if torch.distributed.is_initialized():
         torch.distributed.destroy_process_group()

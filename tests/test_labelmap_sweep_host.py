@@ -163,10 +163,10 @@ def _record(g):
 
 def _gather(E, mine, recs, num_images, everything):
     col = lambda key: [r[key] for r in recs]
-    extra = dict(local_band_miou=col("band_miou"), local_band_counts=col("band_counts"), num_widths=B,
-                 local_confusion=col("confusion"), confusion_labels=L) if everything else {}
-    return E.gather_labelmap_records(mine, col("miou"), col("counts"), num_images, local_sweep_miou=col("sweep_miou"),
-                                     local_sweep_counts=col("sweep_counts"), num_factors=T, **extra)
+    fields = E.label_fields(E.LABELMAP_KEYS, n_bands=B if everything else 0, n_conf=L if everything else 0, n_factors=T)
+    local = {"": (col("miou"), col("counts")), "band_": (col("band_miou"), col("band_counts")),
+             "confusion": (None, col("confusion")), "sweep_": (col("sweep_miou"), col("sweep_counts"))}
+    return E.gather_labelmap_records(mine, fields, {f: local[f.prefix] for f in fields}, num_images)
 
 
 def _worker(rank, world, port, num_images, q):

@@ -304,8 +304,9 @@ def _band_worker(rank, world, port, num_images, q):
         D.init_from_env(backend="gloo")
     mine = D.shard_indices(num_images, rank, world)
     recs = [_band_record(g) for g in mine]
-    out = E.gather_labelmap_records(mine, [r[0] for r in recs], [r[1] for r in recs], num_images, [r[2] for r in recs],
-                                    [r[3] for r in recs], 3)
+    whole, band = fields = E.label_fields(E.LABELMAP_KEYS, n_bands=3)
+    out = E.gather_labelmap_records(mine, fields, {whole: ([r[0] for r in recs], [r[1] for r in recs]),
+                                                   band: ([r[2] for r in recs], [r[3] for r in recs])}, num_images)
     q.put((rank,) + tuple(out))
     if torch.distributed.is_initialized():
         torch.distributed.destroy_process_group()
