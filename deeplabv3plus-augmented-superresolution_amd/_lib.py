@@ -39,6 +39,7 @@ MAX_BAND_WIDTH, MAX_BAND_WIDTHS, MAX_BAND_PREDS = 64, 16, 8     # asr_band_class
 MAX_CONFUSION_LABELS, MAX_CONFUSION_PREDS = 64, 8               # ASR_CONFUSION_MAX_LABELS / _MAX_PREDS
 CONFUSION_SPAN, CONFUSION_GRID = 1024, 64                        # ASR_CONFUSION_SPAN / _GRID: pixels of a workgroup's trip, row cap
 MAX_BINNED_BINS, MAX_BINNED_PREDS = 16, 8                        # asr_binned_class_counts_f32's limits
+REGIONS_TILE_W, REGIONS_TILE_H = 32, 32                          # ASR_REGIONS_TILE_W / _TILE_H: a workgroup's tile in asr_label_regions_i32
 OPM_MODES = {"argmax": 0, "slice": 1, "slice_max": 2}     # ASR_OPM_*
 
 OPT_ADAM, OPT_SGD, OPT_ADAGRAD, OPT_ADADELTA, OPT_ADAMAX = 0, 1, 2, 3, 4
@@ -109,6 +110,10 @@ SIGNATURES = {
     "asr_guided_workspace_bytes": (_sz, [_i, _i, _i]),
     "asr_guided_prepare_f32": (_i, [_vp, _vp, _i, _i, _i, _fl, _vp]),
     "asr_guided_apply_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "asr_label_regions_workspace_bytes": (_sz, [_i, _i, _i]),
+    "asr_label_regions_i32": (_i, [_vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _vp]),
+    "asr_clean_labels_workspace_bytes": (_sz, [_i, _i, _i]),
+    "asr_clean_labels_i32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _vp]),
     "asr_pwconv_packed_floats": (_sz, [_i, _i]),
     "asr_pwconv_pack_weights_f32": (_i, [_vp, _vp, _i, _i, _vp]),
     "asr_pwconv_mfma_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),

@@ -226,13 +226,14 @@ LABELMAP_CSV_COLUMNS = ("standard_iou", "aug_iou", "max_iou", "mean_iou")
 
 # the attribute names of LabelmapScores by field prefix: (per-image Mean_IOU rows, summed counts), or the counts alone
 _SCORE_ATTRS = {"": ("rows", "counts"), "band_": ("band_rows", "band_counts"), "confusion": ("confusion",),
-                "sweep_": ("sweep_rows", "sweep_counts"), "coverage_": ("cov_rows", "cov_counts")}
+                "sweep_": ("sweep_rows", "sweep_counts"), "coverage_": ("cov_rows", "cov_counts"),
+                "raw_": ("raw_rows", "raw_counts"), "regions": ("regions",)}
 
 
 class LabelmapScores(tuple):
     """What gather_labelmap_records and evaluate_labelmaps return: the tuple
-    (rows, counts[, band_rows, band_counts][, confusion][, sweep_rows, sweep_counts][, cov_rows, cov_counts]), one or two
-    entries per field of label_record.label_fields that is on.  Every entry is also an attribute of that name, None when its
+    (rows, counts[, band_rows, band_counts][, confusion][, sweep_rows, sweep_counts][, cov_rows, cov_counts][, raw_rows,
+    raw_counts, regions]), one or two entries per field of label_record.label_fields that is on.  Every entry is also an attribute of that name, None when its
     field is off."""
 
     def __new__(cls, items=(), names=()):
@@ -284,7 +285,7 @@ def dataset_miou(counts):
 def evaluate_labelmaps(path, image_paths, gt_paths, class_ids=tuple(range(1, 21)), num_aug=100, angle_max=0.3, shift_max=30,
                        img_size=(512, 512), rank=0, world=1, seed=1234, sr_types=("aug", "max", "mean"), prune=True,
                        save_dir=None, band_widths=None, band_ignore_label=255, confusion_labels=None, th_factors=None,
-                       guide=None, coverages=None, uncertainty_dir=None):
+                       guide=None, min_region=None, coverages=None, uncertainty_dir=None):
     """One fused label map per image and SR type (HotPath.run_image_labels) and its score.  Returns on every rank a
     LabelmapScores, the tuple (rows, counts) plus what the options below append, every entry also an attribute by the name
     given here: rows [images, 4] per-image Mean_IOU in LABELMAP_KEYS order (the reference's per-image-then-mean convention;
@@ -320,11 +321,17 @@ def evaluate_labelmaps(path, image_paths, gt_paths, class_ids=tuple(range(1, 21)
     or solve) and the return value ends in two more entries, after the sweep's: cov_rows [images, 4, C] per-image Mean_IOU
     and cov_counts [4, C, 3, 256] int64 summed over the images, NaN / zero for a label map that was not asked for
     (write_coverage_csv).  The quantiles are each image's own.  They travel in the same all-gather.  uncertainty_dir (with
-    coverages): sqrt of each image's uncertainty map, the standard deviation over the copies, as <stem>.npy (float32 [H, W])."""
+    coverages): sqrt of each image's uncertainty map, the standard deviation over the copies, as <stem>.npy (float32 [H, W]).
+
+    min_region (an integer A or (A, connectivity); not together with th_factors): every label map is cleaned of its regions of
+    fewer than A pixels before it is scored and saved (run_image_labels' min_region), so every entry above is the cleaned
+    maps', and the return value ends in three more entries: raw_rows [images, 4] and raw_counts [4, 3, 256], what rows and
+    counts are without the option, and regions [4, 4] int64, per label map the regions, small regions, pixels in small
+    regions and pixels changed, summed over the images (write_regions_csv).  They travel in the same all-gather."""
     if uncertainty_dir and coverages is None:
         raise ValueError("uncertainty_dir needs coverages: the uncertainty map is only built for the risk-coverage curve")
     opts = path.label_options(tuple(img_size) + (3,), True, band_widths, band_ignore_label, confusion_labels, th_factors,
-                              guide, coverages, bool(uncertainty_dir))
+                              guide, coverages, bool(uncertainty_dir), min_region)
     if uncertainty_dir:
         os.makedirs(uncertainty_dir, exist_ok=True)
     class_ids, params, mine = _class_set_run(class_ids, image_paths, gt_paths, rank, world, num_aug=num_aug,
@@ -342,7 +349,7 @@ def evaluate_labelmaps(path, image_paths, gt_paths, class_ids=tuple(range(1, 21)
                                     adam_starts={c: int(starts[g, k]) for k, c in enumerate(class_ids)},
                                     band_widths=opts.bands, band_ignore_label=band_ignore_label,
                                     confusion_labels=opts.n_conf or None, th_factors=opts.factors, guide=opts.guide,
-                                    coverages=opts.covs, keep_uncertainty=bool(uncertainty_dir))
+                                    coverages=opts.covs, keep_uncertainty=bool(uncertainty_dir), min_region=opts.min_region)
         for f, (mious, counts) in local.items():        # a label map that was not produced: NaN Mean_IOU, zero counts
             if f.scored:
                 mious.append([res[f.prefix + "Mean_IOU"].get(key, np.full(f.shape[:-2], np.nan)) for key in f.keys])
@@ -395,6 +402,29 @@ def write_labelmap_csv(path, counts, rows):
         wr.writerow(["dataset_mIoU"] + [repr(dataset_miou(counts[j])) for j in range(len(LABELMAP_KEYS))] + [str(len(rows))])
         wr.writerow(["mean_image_mIoU"] + [repr(float(np.mean(rows[:, j]))) if len(rows) else "nan"
                                            for j in range(len(LABELMAP_KEYS))] + [str(len(rows))])
+
+
+REGIONS_CSV_COLUMNS = ("key", "regions", "small_regions", "small_region_pixels", "pixels_changed", "raw_dataset_mIoU",
+                       "raw_mean_image_mIoU", "dataset_mIoU", "mean_image_mIoU")
+
+
+def write_regions_csv(path, regions, raw_counts, raw_rows, counts, rows):
+    """What removing the small regions did, one row per label map (standard / aug / max / mean): the regions, the small regions,
+    the pixels in small regions and the pixels changed, regions [4, 4] summed over the images, then the dataset mIoU and the
+    mean image mIoU before the clean-up (raw_counts [4, 3, 256], raw_rows [images, 4]) and after it (counts, rows): what
+    write_labelmap_csv's last two rows hold.  The cells of a label map that was not produced (all-zero counts) are nan."""
+    import csv
+    regions = np.asarray(regions, dtype=np.int64).reshape(len(LABELMAP_KEYS), 4)
+    raw_counts, counts = np.asarray(raw_counts, dtype=np.int64), np.asarray(counts, dtype=np.int64)
+    raw_rows = np.asarray(raw_rows, dtype=np.float64).reshape(-1, len(LABELMAP_KEYS))
+    rows = np.asarray(rows, dtype=np.float64).reshape(-1, len(LABELMAP_KEYS))
+    with open(path, "w", newline="") as fh:
+        wr = csv.writer(fh, quoting=csv.QUOTE_ALL, lineterminator="\n")
+        wr.writerow(REGIONS_CSV_COLUMNS)
+        for j, key in enumerate(LABELMAP_KEYS):
+            made = bool(counts[j].any() or raw_counts[j].any())
+            wr.writerow([key] + ([str(int(v)) for v in regions[j]] if made else ["nan"] * 4)
+                        + _miou_cells(made, raw_counts[j], raw_rows[:, j]) + _miou_cells(made, counts[j], rows[:, j]))
 
 
 THRESHOLD_CSV_COLUMNS = ("th_factor",) + tuple(f"{key}_{kind}" for key in LABELMAP_KEYS[1:] + LABELMAP_KEYS[:1]

@@ -12,10 +12,11 @@ import numpy as np
 Field = namedtuple("Field", "prefix keys shape scored")
 
 
-def label_fields(keys, n_bands=0, n_conf=0, n_factors=0, n_cov=0):
+def label_fields(keys, n_bands=0, n_conf=0, n_factors=0, n_cov=0, n_regions=0):
     """The fields that are switched on, in the order they are stored: whole-image counts, then with B band widths the trimap,
     with L labels the confusion matrix, with T threshold factors the sweep (SR label maps only: the standard map does not
-    depend on the factor), with C coverages the risk-coverage curve."""
+    depend on the factor), with C coverages the risk-coverage curve, with n_regions set (small regions removed from the label
+    maps) the whole-image counts of the maps before the clean-up and the four region statistics of include/asr_hip.h."""
     keys = tuple(keys)
     fields = [Field("", keys, (3, 256), True)]
     if n_bands:
@@ -26,6 +27,9 @@ def label_fields(keys, n_bands=0, n_conf=0, n_factors=0, n_cov=0):
         fields.append(Field("sweep_", tuple(k for k in keys if k != "standard"), (n_factors, 3, 256), True))
     if n_cov:
         fields.append(Field("coverage_", keys, (n_cov, 3, 256), True))
+    if n_regions:
+        fields.append(Field("raw_", keys, (3, 256), True))
+        fields.append(Field("regions", keys, (4,), False))
     return tuple(fields)
 
 

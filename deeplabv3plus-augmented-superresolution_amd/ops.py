@@ -884,6 +884,88 @@ def guided_filter(guide, p, radius=8, eps=1e-3, out=None):
     return guided_apply(guided_prepare(guide, radius, eps), guide, p, out=out)
 
 
+# ---------------------------------------------------------------------------------------------
+def _region_int(v, name):
+    try:
+        if isinstance(v, (bool, str, bytes)):
+            raise TypeError
+        n = int(v)
+        same = float(v) == float(n)
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError(f"min_region: {name} must be an integer, got {v!r}") from None
+    if not same:
+        raise ValueError(f"min_region: {name} must be an integer, got {v!r}")
+    return n
+
+
+def check_min_region(min_region):
+    """min_region of a label-map clean-up as (min_area, connectivity): an int (connectivity 4) or a pair (min_area,
+    connectivity); min_area >= 1, connectivity 4 or 8.  Host only; ValueError otherwise."""
+    if isinstance(min_region, (tuple, list)):
+        if len(min_region) != 2:
+            raise ValueError(f"min_region must be an integer or (min_area, connectivity), got {min_region!r}")
+        area, conn = _region_int(min_region[0], "min_area"), _region_int(min_region[1], "connectivity")
+    else:
+        area, conn = _region_int(min_region, "min_area"), 4
+    if area < 1:
+        raise ValueError(f"min_region: min_area {area} below 1")
+    if area > 2 ** 31 - 1:
+        raise ValueError(f"min_region: min_area {area} above 2^31 - 1")
+    if conn not in (4, 8):
+        raise ValueError(f"min_region: connectivity {conn} (4 or 8)")
+    return area, conn
+
+
+def _region_maps(labels, name):
+    if not isinstance(labels, torch.Tensor):
+        raise AsrError(f"{name}: expected a torch.Tensor, got {type(labels)}")
+    if labels.dim() not in (2, 3) or min(labels.shape) < 1:
+        raise AsrError(f"{name}: labels must be [H, W] or [M, H, W], got {tuple(labels.shape)}")
+    maps = 1 if labels.dim() == 2 else int(labels.shape[0])
+    return maps, int(labels.shape[-2]), int(labels.shape[-1])
+
+
+def label_regions(labels, connectivity=4):
+    """int32 label maps [H, W] or [M, H, W] -> (root, area), int32 of the same shape: the smallest linear index (within the
+    pixel's own map) and the pixel count of each pixel's connected region of equal value (asr_label_regions_i32; connectivity
+    4 or 8).  The workspace (4 bytes per pixel) comes from torch's caching allocator."""
+    maps, h, w = _region_maps(labels, "label_regions")
+    lib = _lib.load()
+    root, area = torch.empty_like(labels), torch.empty_like(labels)
+    nbytes = lib.asr_label_regions_workspace_bytes(maps, h, w)
+    ws = torch.empty(max(nbytes // 4, 1), dtype=torch.int32, device=labels.device)
+    call("asr_label_regions_i32", ptr(labels, torch.int32), ptr(root, torch.int32), ptr(area, torch.int32),
+         ptr(ws, torch.int32), nbytes, maps, h, w, int(connectivity), stream_ptr())
+    return root, area
+
+
+def clean_labels(labels, min_area, connectivity=4, regions=None, out=None, want_stats=False):
+    """int32 label maps [H, W] or [M, H, W] -> the maps with every region of fewer than min_area pixels replaced by the one
+    value of its non-small surround, or by 0 when that surround is empty or mixed (asr_clean_labels_i32).  regions: the
+    (root, area) of label_regions(labels, connectivity), to reuse them; out: may be labels itself (in place).
+    want_stats: also the int64 [M, 4] (or [4]) tensor of regions, small regions, pixels in small regions, pixels changed."""
+    maps, h, w = _region_maps(labels, "clean_labels")
+    min_area, connectivity = check_min_region((min_area, connectivity))
+    root, area = label_regions(labels, connectivity) if regions is None else regions
+    for t, nm in ((root, "root"), (area, "area")):
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != tuple(labels.shape):
+            raise AsrError(f"clean_labels: {nm} must have the shape of labels, {tuple(labels.shape)}")
+    if out is None:
+        out = torch.empty_like(labels)
+    elif tuple(out.shape) != tuple(labels.shape):
+        raise AsrError(f"clean_labels: out must be {tuple(labels.shape)}, got {tuple(out.shape)}")
+    lib = _lib.load()
+    stats = torch.empty((maps, 4), dtype=torch.int64, device=labels.device) if want_stats else None
+    nbytes = lib.asr_clean_labels_workspace_bytes(maps, h, w)
+    ws = torch.empty(max(nbytes // 4, 1), dtype=torch.int32, device=labels.device)
+    call("asr_clean_labels_i32", ptr(labels, torch.int32), ptr(root, torch.int32), ptr(area, torch.int32),
+         ptr(out, torch.int32), ptr(stats, torch.int64, allow_none=True), ptr(ws, torch.int32), nbytes, maps, h, w,
+         int(connectivity), int(min_area), stream_ptr())
+    if want_stats:
+        return out, (stats[0] if labels.dim() == 2 else stats)
+    return out
+
+
 MAX_SWEEP_FACTORS = 256
 
 

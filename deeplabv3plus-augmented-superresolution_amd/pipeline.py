@@ -295,7 +295,7 @@ class HotPath:
     def run_image_labels(self, image_dev, angles, shifts, class_ids=range(1, 21), gt_dev=None, adam_starts=None,
                          sr_types=("aug", "max", "mean"), want_standard=True, prune=True, profile=None, keep_scores=False,
                          band_widths=None, band_ignore_label=255, confusion_labels=None, th_factors=None, guide=None,
-                         coverages=None, keep_uncertainty=False):
+                         coverages=None, keep_uncertainty=False, min_region=None):
         """One label map per SR type from one forward pass: stage 1 and the solves are run_image_classes's; stage 2 ends in the
         fusion kernel (ops.fuse_labels) instead of K thresholds.  class_ids: K <= 32 distinct ids, none 0 (the label of "no
         class").  At each pixel the label is the class whose single-class mask is set there and whose SR output is greatest
@@ -353,10 +353,22 @@ class HotPath:
         each percentage retained, >= p / 100 as ties stay in), in the same single copy to the host as "counts"; with
         keep_uncertainty also "uncertainty" (device float32 [H, W]) and "uncertainty_stacks" (the [K', N, h, w] tensor the
         moments were taken of, None when no class was solved).  With coverages=None nothing else is launched and nothing
-        else returned."""
+        else returned.
+
+        min_region (an integer A or (A, connectivity), connectivity 4 or 8, default 4; not together with th_factors, whose label
+        maps are counted and never written): the clean-up of include/asr_hip.h, "regions".  After the last fusion, inside the
+        timed SR stage, one ops.label_regions and one ops.clean_labels call run over all produced label maps at once, the
+        standard map included, in place: every region of fewer than A pixels takes the one value of its non-small surround, or
+        0.  Everything downstream sees the cleaned maps: the returned maps, "counts" and "Mean_IOU" (recounted with
+        ops.class_counts, since the fusion's in-pass counts belong to the raw maps), the trimap, the confusion matrix and the
+        risk-coverage counts.  The result gains "regions" {key: int64 [4] numpy: regions, small regions, pixels in small
+        regions, pixels changed} and, with gt_dev, "raw_counts" and "raw_Mean_IOU", the scores before the clean-up.  With no
+        class left after pruning the zero maps are one region each and the calls still run.  With min_region=None nothing
+        else is launched and nothing else returned."""
         ids = [int(c) for c in class_ids]
         opts = self.label_options(None if image_dev is None else tuple(image_dev.shape), gt_dev is not None, band_widths,
-                                  band_ignore_label, confusion_labels, th_factors, guide, coverages, keep_uncertainty)
+                                  band_ignore_label, confusion_labels, th_factors, guide, coverages, keep_uncertainty,
+                                  min_region)
         if any(c == 0 for c in ids):
             raise ValueError(f"class id 0 is the fallback label, never a candidate: {ids}")
         unknown = [t for t in sr_types if t not in ("aug", "max", "mean")]
@@ -420,11 +432,15 @@ class HotPath:
                     if opts.factors is not None:
                         tally.sweep[:] = tally.counts[first]                             # ... under every factor
             self._advance_past(starts, adam_starts, sr_types)
+            region_stats = self._clean_label_maps(tally, gt, maps, opts.min_region) if opts.min_region is not None else None
             u_map = self._score_label_maps(tally, gt, maps, opts, y if kept else None, angles, fshifts)
         res = {key: maps[j] for j, key in enumerate(keys)}
         res["solved_ids"] = solved
         if tally is not None:
             res.update(tally.to_host())
+        elif region_stats is not None:
+            host = region_stats.cpu().numpy()
+            res["regions"] = {key: host[j] for j, key in enumerate(keys)}
         if keep_scores:
             res["scores"] = scores
         if keep_uncertainty:
@@ -433,7 +449,7 @@ class HotPath:
         return res
 
     def label_options(self, image_shape, has_gt, band_widths=None, band_ignore_label=255, confusion_labels=None,
-                      th_factors=None, guide=None, coverages=None, keep_uncertainty=False):
+                      th_factors=None, guide=None, coverages=None, keep_uncertainty=False, min_region=None):
         """The scoring options of run_image_labels, checked and normalised into one LabelOptions; ValueError as its docstring
         says.  Host only, and nothing of self is read that the options given do not need (mode: th_factors; sr: guide).
         image_shape: the image's shape or None; has_gt: a ground truth comes with it."""
@@ -451,6 +467,11 @@ class HotPath:
             if image_shape != tuple(self.sr.output_size) + (3,):
                 raise ValueError(f"guide needs the image as [H, W, 3] at the SR output size {tuple(self.sr.output_size)}, got "
                                  f"{image_shape}")
+        if min_region is not None:
+            min_region = ops.check_min_region(min_region)
+            if th_factors is not None:
+                raise ValueError("th_factors with min_region: the sweep counts label maps that are never written, so there is "
+                                 "nothing to clean")
         factors = None
         if th_factors is not None:
             if not has_gt:
@@ -466,8 +487,23 @@ class HotPath:
         if n_conf and not has_gt:
             raise ValueError("confusion_labels needs gt_dev: a confusion matrix is counted against a ground truth")
         band_ignore = -1 if bands is None or band_ignore_label is None else int(band_ignore_label)
-        sizes = (len(bands or ()), n_conf, 0 if factors is None else factors.size, len(covs or ()))
-        return LabelOptions(bands, band_ignore, n_conf, factors, guide, covs, sizes)
+        sizes = (len(bands or ()), n_conf, 0 if factors is None else factors.size, len(covs or ()), int(min_region is not None))
+        return LabelOptions(bands, band_ignore, n_conf, factors, guide, covs, sizes, min_region)
+
+    @staticmethod
+    def _clean_label_maps(tally, gt, maps, min_region):
+        """The small regions of the finished label maps [M, H, W] removed in place (one labelling and one clean-up call over
+        all of them); with a tally the raw counts kept, the counts taken again on the cleaned maps and the region statistics
+        stored.  Returns the statistics, device int64 [M, 4]."""
+        min_area, connectivity = min_region
+        _, stats = ops.clean_labels(maps, min_area, connectivity, regions=ops.label_regions(maps, connectivity), out=maps,
+                                    want_stats=True)
+        if tally is not None:
+            tally.raw[:] = tally.counts
+            for j in range(maps.shape[0]):
+                tally.counts[j] = ops.class_counts(gt, maps[j])[0]
+            tally.regions[:] = stats
+        return stats
 
     def _score_label_maps(self, tally, gt, maps, opts, stacks, angles, fshifts):
         """The scores of the finished label maps [M, H, W] against gt, into tally: trimap bands, confusion matrices, risk-coverage
@@ -529,15 +565,16 @@ class HotPath:
 
 
 # HotPath.label_options' value: band widths | None and the label left out of the bands (-1: none), confusion labels (0: off),
-# float32 threshold factors | None, the guide's (radius, eps) | None, coverages | None; sizes: (B, L, T, C), 0 where off
-LabelOptions = namedtuple("LabelOptions", "bands band_ignore n_conf factors guide covs sizes")
+# float32 threshold factors | None, the guide's (radius, eps) | None, coverages | None; sizes: (B, L, T, C, R), 0 where off (R: 1
+# with min_region); min_region: (min_area, connectivity) | None
+LabelOptions = namedtuple("LabelOptions", "bands band_ignore n_conf factors guide covs sizes min_region")
 
 
 class _LabelCounts:
     """The counts of run_image_labels on the device, one int64 allocation so that they reach the host in one copy: the fields
     of label_record.label_layout one after another; after them, with C coverages, C + 1 pixel totals (the counted pixels each
     coverage retained, then all of them).  Each field that is on is the attribute of its prefix's name -- counts, band,
-    confusion, sweep, coverage -- as [len(keys), *shape]: what the ops.*_counts(out=...) call of that score writes into."""
+    confusion, sweep, coverage, raw, regions -- as [len(keys), *shape]: what the ops.*_counts(out=...) call of that score writes into."""
 
     def __init__(self, fields, device):
         spans, end = label_layout(fields, with_miou=False)

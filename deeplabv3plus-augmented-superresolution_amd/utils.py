@@ -194,6 +194,30 @@ def confusion_matrix(y_true, y_pred, num_labels):
     return ops.confusion_counts(t, p, n)[0].cpu().numpy()
 
 
+def _clean_on_device(label_map, min_area, connectivity):
+    min_area, connectivity = ops.check_min_region((min_area, connectivity))
+    shape = tuple(label_map.shape) if hasattr(label_map, "shape") else np.asarray(label_map).shape
+    if len(shape) == 3 and shape[-1] == 1:
+        shape = shape[:2]
+    if len(shape) not in (2, 3):
+        raise ValueError(f"a label map of shape {shape}: regions are two-dimensional, [H, W] or [M, H, W]")
+    t = _as_label_tensor(label_map, _lib.require_gpu()).view(shape)
+    return ops.clean_labels(t, min_area, connectivity, want_stats=True)
+
+
+def remove_small_regions(label_map, min_area, connectivity=4):
+    """The label map cleaned of its regions of fewer than min_area pixels (include/asr_hip.h, "regions"): each takes the one
+    value of its non-small surround, or 0 when that is empty or mixed.  connectivity 4 or 8.  A numpy array or tensor, on the
+    host or the device, [H, W] / [H, W, 1] or [M, H, W]; returns a host int32 array of shape [H, W] or [M, H, W]."""
+    return _clean_on_device(label_map, min_area, connectivity)[0].cpu().numpy()
+
+
+def region_stats(label_map, min_area, connectivity=4):
+    """Host int64 [4] (or [M, 4]): the number of regions, of small regions (fewer than min_area pixels), of pixels in small
+    regions, and of pixels whose value remove_small_regions changes."""
+    return _clean_on_device(label_map, min_area, connectivity)[1].cpu().numpy()
+
+
 def metrics_from_confusion(M, other="ignore"):
     """The usual result table of a segmentation from one confusion matrix M [L+1, L+1] (truth in the rows, the last row and
     column the "other" bin).  Pure numpy, float64.  With row_l, col_l the sums of row and column l and d_l = M[l, l]:

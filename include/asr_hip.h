@@ -543,6 +543,50 @@ int asr_guided_prepare_f32(const float* guide, void* state, int H, int W, int r,
 int asr_guided_apply_f32(const void* state, const float* guide, const float* p, float* q, void* workspace, int planes, int H,
                          int W, int r, asr_stream_t stream);
 
+/* --- regions: connected components of a label map, and the label map cleaned of its small ones -----------------------------
+ * (what is elsewhere called remove_small_objects / remove_small_holes, or an area opening, for every value at once)
+ * Definitions (everything is integer; nothing is ever rounded):
+ *  - a label map is int32 [h, w], linear index y * w + x; the connectivity c is 4 or 8;
+ *  - a REGION is a maximal set of pixels of equal value that is connected by c-neighbour steps inside the image.  Every value
+ *    makes regions: 0, 255, negative values and ids alike.  The image border connects nothing;
+ *  - root[p] is the smallest linear index of p's region and area[p] that region's pixel count: functions of the input alone,
+ *    independent of dispatch order and bit-identical from call to call;
+ *  - for a threshold min_area >= 1 a region is SMALL when area < min_area;
+ *  - the SURROUND V(R) of a small region R is the set of values of the pixels q outside R that are c-adjacent to a pixel of R,
+ *    lie inside the image, and whose own region is not small: small regions never vote;
+ *  - the CLEANED MAP: out[p] = labels[p] when p's region is not small; else the single element of V(R) when |V(R)| = 1; else
+ *    0 ("no class").  One pass over the regions of the INPUT; it is not iterated.
+ * Hence: min_area = 1 returns the input bit for bit; min_area > h * w returns all zeros; a small island inside one large
+ * region takes that region's value (a pin-hole of 0 inside a class is filled, a speck of a class inside background goes to
+ * 0); a small island that touches two large regions of different values goes to 0; two adjacent small regions inside a large
+ * 0 region both go to 0; a small region nested in another small region goes to 0, not to the outer small region's value; a
+ * small 0-region with a mixed surround stays 0.
+ *  - stats [maps, 4] int64, zeroed by the call, per map: the number of regions, the number of small regions, the number of
+ *    pixels in small regions, the number of pixels whose value changed.
+ *
+ * asr_label_regions_i32: labels [maps, h, w] -> root, area [maps, h, w] int32; root holds indices within the pixel's own map.
+ * asr_clean_labels_i32: labels with the root and area of the same connectivity -> out [maps, h, w] (out may alias labels) and
+ * stats (may be NULL).  Both need a workspace of at least their *_workspace_bytes(maps, h, w) bytes, 4-byte aligned, fully
+ * rewritten by each call (host arithmetic, 0 for a size below 1); a short one returns ASR_ERR_WORKSPACE.  Null pointers, a
+ * connectivity other than 4 or 8, min_area < 1, h or w < 1, h * w > 2^31 - 1 and maps outside 1..65535 (a map is a grid
+ * layer) return ASR_ERR_INVALID_ARG.  Refusals happen before any launch and nothing is written.
+ * How: a workgroup of 256 threads labels one ASR_REGIONS_TILE_W x ASR_REGIONS_TILE_H tile by union-find in LDS (links made
+ * by atomic min, so parent[i] <= i always); a second launch joins the neighbour pairs that straddle a tile border with the
+ * same routine on global memory; a third flattens and adds each tile-local pixel count once to its region's root; a fourth
+ * spreads the areas.  The clean-up keeps, per small region, the minimum and maximum of the non-small neighbours' values
+ * (|V| = 1 exactly when they are equal).  Phases are separate launches on the caller's stream: no workgroup ever waits for
+ * another, and every walk is a counted loop (a root of -1 would report an overrun, which parent[i] <= i excludes).  An
+ * address receives one atomic per tile, wave or workgroup, never one per pixel. */
+#define ASR_REGIONS_TILE_W 32
+#define ASR_REGIONS_TILE_H 32
+size_t asr_label_regions_workspace_bytes(int maps, int h, int w);
+int asr_label_regions_i32(const int32_t* labels, int32_t* root, int32_t* area, void* workspace, size_t workspace_bytes,
+                          int maps, int h, int w, int connectivity, asr_stream_t stream);
+size_t asr_clean_labels_workspace_bytes(int maps, int h, int w);
+int asr_clean_labels_i32(const int32_t* labels, const int32_t* root, const int32_t* area, int32_t* out, int64_t* stats,
+                         void* workspace, size_t workspace_bytes, int maps, int h, int w, int connectivity, int min_area,
+                         asr_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * DeepLabV3+ (Xception-65, OS16) layers -- model.py.  BatchNorm is folded by the caller.
  * ------------------------------------------------------------------------------------------ */

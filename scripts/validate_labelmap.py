@@ -38,7 +38,13 @@ copies disagreed, and every label map is scored on each image's p % most certain
 with no further forward pass or solve.  One CSV row per percentage (evaluation.write_coverage_csv: dataset mIoU, mean per-image
 mIoU and the share actually retained, which is >= p % because ties stay in); a curve that rises as p falls says the map knows
 where the labels are wrong.  DIR: sqrt(u), the standard deviation over the copies, per image as <image stem>.npy (+inf where
-fewer than two copies saw the pixel).  Without these flags nothing else is computed or written."""
+fewer than two copies saw the pixel).  Without these flags nothing else is computed or written.
+
+--min_region A [--region_connectivity {4,8}] [--regions_out FILE]: every label map is cleaned of its connected regions of fewer than
+A pixels before it is scored and saved (include/asr_hip.h, "regions": a small region takes the one value of its non-small
+surround, or 0), so every CSV above is the cleaned maps'; FILE (evaluation.write_regions_csv) holds, per label map, how many
+regions there were, how many were small, how many pixels changed, and both mIoUs before and after.  Not together with
+--th_sweep / --th_factors, whose label maps are never written.  Without --min_region nothing else is computed or written."""
 import argparse
 import os
 import sys
@@ -87,6 +93,10 @@ parser.add_argument("--coverages", default=None,
                     help="comma-separated whole percentages (1..100, at most 16), e.g. 50,60,70,80,90,100: the risk-coverage curve too")
 parser.add_argument("--coverage_out", default=None, help="CSV file for the risk-coverage curve (default: <--out stem>_coverage.csv)")
 parser.add_argument("--uncertainty_dir", default=None, help="folder for sqrt(u) per image as .npy (needs --coverages)")
+parser.add_argument("--min_region", type=int, default=None,
+                    help="remove connected regions of fewer than this many pixels from every label map before scoring it")
+parser.add_argument("--region_connectivity", type=int, choices=[4, 8], default=4, help="the regions' connectivity (default 4)")
+parser.add_argument("--regions_out", default=None, help="CSV file for the region statistics (default: <--out stem>_regions.csv)")
 parser.add_argument("--no_prune", action="store_true", help="solve every class, also those that win no pixel (same results)")
 
 
@@ -96,8 +106,8 @@ def main():
     from asr_amd import distributed as D
     from asr_amd.evaluation import (LABELMAP_KEYS, best_threshold_factors, dataset_miou, evaluate_labelmaps,
                                     write_confusion_csv, write_confusion_metrics_csv, write_labelmap_csv,
-                                    write_coverage_csv, write_labelmap_threshold_csv, write_trimap_csv)
-    from asr_amd.ops import check_coverages
+                                    write_coverage_csv, write_labelmap_threshold_csv, write_regions_csv, write_trimap_csv)
+    from asr_amd.ops import check_coverages, check_min_region
     from asr_amd.model import DeeplabV3Plus
     from asr_amd.pipeline import HotPath
     from asr_amd.superresolution_scripts.optimizer import Optimizer
@@ -124,6 +134,17 @@ def main():
             HotPath(None, None, mode=args.mode).label_options(None, True, th_factors=factors)
         except ValueError as e:
             parser.error(f"--th_factors / --th_sweep: {e}")
+    if args.regions_out and args.min_region is None:
+        parser.error("--regions_out needs --min_region")
+    min_region = None
+    if args.min_region is not None:
+        if factors is not None:
+            parser.error("--min_region with --th_sweep / --th_factors: the sweep counts label maps that are never written, so "
+                         "there is nothing to clean")
+        try:
+            min_region = check_min_region((args.min_region, args.region_connectivity))
+        except ValueError as e:
+            parser.error(f"--min_region: {e}")
     if args.guide_eps is not None and args.guide_radius is None:
         parser.error("--guide_eps needs --guide_radius")
     guide = None
@@ -167,7 +188,8 @@ def main():
                              confusion_labels=args.confusion_labels if args.confusion_out else None,
                              **(dict(th_factors=factors) if factors is not None else {}),
                              **(dict(guide=guide) if guide is not None else {}),
-                             **(dict(coverages=covs, uncertainty_dir=args.uncertainty_dir) if covs is not None else {}))
+                             **(dict(coverages=covs, uncertainty_dir=args.uncertainty_dir) if covs is not None else {}),
+                             **(dict(min_region=min_region) if min_region is not None else {}))
     rows, counts = out.rows, out.counts
     if rank == 0:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
@@ -203,6 +225,16 @@ def main():
                     print(f"{key}: dataset mIoU {dataset_miou(out.cov_counts[j, lo]):.4f} on the {covs[lo]} % most certain pixels, "
                           f"{dataset_miou(out.cov_counts[j, hi]):.4f} at {covs[hi]} %")
             print(f"Wrote {cov_csv}")
+        if min_region is not None:
+            reg_csv = args.regions_out or os.path.splitext(os.path.abspath(args.out))[0] + "_regions.csv"
+            os.makedirs(os.path.dirname(os.path.abspath(reg_csv)), exist_ok=True)
+            write_regions_csv(reg_csv, out.regions, out.raw_counts, out.raw_rows, counts, rows)
+            for j, key in enumerate(LABELMAP_KEYS):
+                if out.raw_counts[j].any():
+                    print(f"{key}: {int(out.regions[j, 1])} of {int(out.regions[j, 0])} regions below {min_region[0]} pixels, "
+                          f"{int(out.regions[j, 3])} pixels changed, dataset mIoU {dataset_miou(out.raw_counts[j]):.4f} -> "
+                          f"{dataset_miou(counts[j]):.4f}")
+            print(f"Wrote {reg_csv}")
     if world > 1:
         torch.distributed.barrier()
         torch.distributed.destroy_process_group()
