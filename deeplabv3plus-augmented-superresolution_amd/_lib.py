@@ -40,6 +40,7 @@ MAX_CONFUSION_LABELS, MAX_CONFUSION_PREDS = 64, 8               # ASR_CONFUSION_
 CONFUSION_SPAN, CONFUSION_GRID = 1024, 64                        # ASR_CONFUSION_SPAN / _GRID: pixels of a workgroup's trip, row cap
 MAX_BINNED_BINS, MAX_BINNED_PREDS = 16, 8                        # asr_binned_class_counts_f32's limits
 REGIONS_TILE_W, REGIONS_TILE_H = 32, 32                          # ASR_REGIONS_TILE_W / _TILE_H: a workgroup's tile in asr_label_regions_i32
+MAX_SEGMENT_LABELS, SEGMENTS_IOU_ONE = 64, 1 << 30               # ASR_SEGMENTS_MAX_LABELS / _IOU_ONE
 OPM_MODES = {"argmax": 0, "slice": 1, "slice_max": 2}     # ASR_OPM_*
 
 OPT_ADAM, OPT_SGD, OPT_ADAGRAD, OPT_ADADELTA, OPT_ADAMAX = 0, 1, 2, 3, 4
@@ -114,6 +115,8 @@ SIGNATURES = {
     "asr_label_regions_i32": (_i, [_vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _vp]),
     "asr_clean_labels_workspace_bytes": (_sz, [_i, _i, _i]),
     "asr_clean_labels_i32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _vp]),
+    "asr_segment_match_workspace_bytes": (_sz, [_i, _i, _i]),
+    "asr_segment_match_i32": (_i, [_vp] * 9 + [_sz, _i, _i, _i, _i, _i, _vp]),
     "asr_pwconv_packed_floats": (_sz, [_i, _i]),
     "asr_pwconv_pack_weights_f32": (_i, [_vp, _vp, _i, _i, _vp]),
     "asr_pwconv_mfma_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),

@@ -227,13 +227,14 @@ LABELMAP_CSV_COLUMNS = ("standard_iou", "aug_iou", "max_iou", "mean_iou")
 # the attribute names of LabelmapScores by field prefix: (per-image Mean_IOU rows, summed counts), or the counts alone
 _SCORE_ATTRS = {"": ("rows", "counts"), "band_": ("band_rows", "band_counts"), "confusion": ("confusion",),
                 "sweep_": ("sweep_rows", "sweep_counts"), "coverage_": ("cov_rows", "cov_counts"),
-                "raw_": ("raw_rows", "raw_counts"), "regions": ("regions",)}
+                "raw_": ("raw_rows", "raw_counts"), "regions": ("regions",), "segments": ("segments",),
+                "raw_segments": ("raw_segments",)}
 
 
 class LabelmapScores(tuple):
     """What gather_labelmap_records and evaluate_labelmaps return: the tuple
     (rows, counts[, band_rows, band_counts][, confusion][, sweep_rows, sweep_counts][, cov_rows, cov_counts][, raw_rows,
-    raw_counts, regions]), one or two entries per field of label_record.label_fields that is on.  Every entry is also an attribute of that name, None when its
+    raw_counts, regions][, segments][, raw_segments]), one or two entries per field of label_record.label_fields that is on.  Every entry is also an attribute of that name, None when its
     field is off."""
 
     def __new__(cls, items=(), names=()):
@@ -285,7 +286,7 @@ def dataset_miou(counts):
 def evaluate_labelmaps(path, image_paths, gt_paths, class_ids=tuple(range(1, 21)), num_aug=100, angle_max=0.3, shift_max=30,
                        img_size=(512, 512), rank=0, world=1, seed=1234, sr_types=("aug", "max", "mean"), prune=True,
                        save_dir=None, band_widths=None, band_ignore_label=255, confusion_labels=None, th_factors=None,
-                       guide=None, min_region=None, coverages=None, uncertainty_dir=None):
+                       guide=None, min_region=None, segments=None, coverages=None, uncertainty_dir=None):
     """One fused label map per image and SR type (HotPath.run_image_labels) and its score.  Returns on every rank a
     LabelmapScores, the tuple (rows, counts) plus what the options below append, every entry also an attribute by the name
     given here: rows [images, 4] per-image Mean_IOU in LABELMAP_KEYS order (the reference's per-image-then-mean convention;
@@ -327,11 +328,19 @@ def evaluate_labelmaps(path, image_paths, gt_paths, class_ids=tuple(range(1, 21)
     fewer than A pixels before it is scored and saved (run_image_labels' min_region), so every entry above is the cleaned
     maps', and the return value ends in three more entries: raw_rows [images, 4] and raw_counts [4, 3, 256], what rows and
     counts are without the option, and regions [4, 4] int64, per label map the regions, small regions, pixels in small
-    regions and pixels changed, summed over the images (write_regions_csv).  They travel in the same all-gather."""
+    regions and pixels changed, summed over the images (write_regions_csv).  They travel in the same all-gather.
+
+    segments (an integer L, (L, connectivity) or (L, connectivity, include_zero); not together with th_factors): the same loop
+    also matches each label map's segments against the ground truth's (run_image_labels' segments) and the return value ends
+    in one more entry, segments [4, L, 4] int64, per label map and label TP, FP, FN and Q summed over the images
+    (utils.metrics_from_segments, write_segments_csv), all zero for a label map that was not asked for; with min_region
+    another follows, raw_segments, the same of the maps before the clean-up.  They travel in the same float64 all-gather:
+    exact while a Q sum stays below 2^53, that is 2^23 (about 8 million) matched segments per label map and label, each
+    adding at most 2^30."""
     if uncertainty_dir and coverages is None:
         raise ValueError("uncertainty_dir needs coverages: the uncertainty map is only built for the risk-coverage curve")
     opts = path.label_options(tuple(img_size) + (3,), True, band_widths, band_ignore_label, confusion_labels, th_factors,
-                              guide, coverages, bool(uncertainty_dir), min_region)
+                              guide, coverages, bool(uncertainty_dir), min_region, segments)
     if uncertainty_dir:
         os.makedirs(uncertainty_dir, exist_ok=True)
     class_ids, params, mine = _class_set_run(class_ids, image_paths, gt_paths, rank, world, num_aug=num_aug,
@@ -340,7 +349,7 @@ def evaluate_labelmaps(path, image_paths, gt_paths, class_ids=tuple(range(1, 21)
     starts = D.adam_class_starts(np.ones((n_img, len(class_ids)), dtype=bool), path.sr.num_iter, path.mode)
     if save_dir:
         os.makedirs(save_dir, exist_ok=True)
-    fields = label_fields(LABELMAP_KEYS, *opts.sizes)
+    fields = label_fields(LABELMAP_KEYS, *opts.sizes, n_segments=opts.segments[0] if opts.segments else 0)
     local = {f: ([], []) for f in fields}
     for g in mine:
         image, gt = _image_and_labels_on_device(image_paths[g], gt_paths[g], img_size)
@@ -349,7 +358,8 @@ def evaluate_labelmaps(path, image_paths, gt_paths, class_ids=tuple(range(1, 21)
                                     adam_starts={c: int(starts[g, k]) for k, c in enumerate(class_ids)},
                                     band_widths=opts.bands, band_ignore_label=band_ignore_label,
                                     confusion_labels=opts.n_conf or None, th_factors=opts.factors, guide=opts.guide,
-                                    coverages=opts.covs, keep_uncertainty=bool(uncertainty_dir), min_region=opts.min_region)
+                                    coverages=opts.covs, keep_uncertainty=bool(uncertainty_dir), min_region=opts.min_region,
+                                    segments=opts.segments)
         for f, (mious, counts) in local.items():        # a label map that was not produced: NaN Mean_IOU, zero counts
             if f.scored:
                 mious.append([res[f.prefix + "Mean_IOU"].get(key, np.full(f.shape[:-2], np.nan)) for key in f.keys])
@@ -425,6 +435,36 @@ def write_regions_csv(path, regions, raw_counts, raw_rows, counts, rows):
             made = bool(counts[j].any() or raw_counts[j].any())
             wr.writerow([key] + ([str(int(v)) for v in regions[j]] if made else ["nan"] * 4)
                         + _miou_cells(made, raw_counts[j], raw_rows[:, j]) + _miou_cells(made, counts[j], rows[:, j]))
+
+
+SEGMENTS_CSV_COLUMNS = ("key", "stage", "label", "TP", "FP", "FN", "precision", "recall", "SQ", "RQ", "PQ")
+
+
+def write_segments_csv(path, segments, raw_segments=None, class_names=None):
+    """The region-by-region scores in long form, one row per (label map, stage, label): segments [4, L, 4] int64 (TP, FP, FN, Q
+    summed over the images, LABELMAP_KEYS order) is the stage "final"; raw_segments, the same before the clean-up, when given
+    the stage "raw", written ahead of it.  Each row holds TP, FP, FN and utils.metrics_from_segments' precision, recall, SQ, RQ
+    and PQ, for the labels with TP + FP + FN > 0 (named as in write_confusion_csv: class_names or the number); a row "mean" per (key,
+    stage) follows them with the summed TP, FP, FN, empty precision and recall, and the mean SQ, RQ and PQ over those labels.
+    A label map without any segment (not produced, or nothing to match) has its "mean" row alone, nan."""
+    import csv
+    from .utils import metrics_from_segments
+    stages = [("final", np.asarray(segments, dtype=np.int64))]
+    if raw_segments is not None:
+        stages.insert(0, ("raw", np.asarray(raw_segments, dtype=np.int64)))
+    with open(path, "w", newline="") as fh:
+        wr = csv.writer(fh, quoting=csv.QUOTE_ALL, lineterminator="\n")
+        wr.writerow(SEGMENTS_CSV_COLUMNS)
+        for j, key in enumerate(LABELMAP_KEYS):
+            for stage, counts in stages:
+                c = counts.reshape(len(LABELMAP_KEYS), -1, 4)[j]
+                m = metrics_from_segments(c)
+                names = confusion_label_names(c.shape[0], class_names)
+                for l in np.nonzero(c[:, :3].sum(axis=1) > 0)[0].tolist():
+                    wr.writerow([key, stage, names[l]] + [str(int(v)) for v in c[l, :3]]
+                                + [repr(float(m[k][l])) for k in ("precision", "recall", "SQ", "RQ", "PQ")])
+                wr.writerow([key, stage, "mean"] + [str(int(v)) for v in c[:, :3].sum(axis=0)] + ["", ""]
+                            + [repr(m[k]) for k in ("mean_SQ", "mean_RQ", "mean_PQ")])
 
 
 THRESHOLD_CSV_COLUMNS = ("th_factor",) + tuple(f"{key}_{kind}" for key in LABELMAP_KEYS[1:] + LABELMAP_KEYS[:1]

@@ -12,11 +12,13 @@ import numpy as np
 Field = namedtuple("Field", "prefix keys shape scored")
 
 
-def label_fields(keys, n_bands=0, n_conf=0, n_factors=0, n_cov=0, n_regions=0):
+def label_fields(keys, n_bands=0, n_conf=0, n_factors=0, n_cov=0, n_regions=0, n_segments=0):
     """The fields that are switched on, in the order they are stored: whole-image counts, then with B band widths the trimap,
     with L labels the confusion matrix, with T threshold factors the sweep (SR label maps only: the standard map does not
     depend on the factor), with C coverages the risk-coverage curve, with n_regions set (small regions removed from the label
-    maps) the whole-image counts of the maps before the clean-up and the four region statistics of include/asr_hip.h."""
+    maps) the whole-image counts of the maps before the clean-up and the four region statistics of include/asr_hip.h, with
+    n_segments = L labels the segment counts (TP, FP, FN, Q per label; include/asr_hip.h, "segments") of the finished maps
+    and, when n_regions is on as well, of the maps before the clean-up."""
     keys = tuple(keys)
     fields = [Field("", keys, (3, 256), True)]
     if n_bands:
@@ -30,6 +32,10 @@ def label_fields(keys, n_bands=0, n_conf=0, n_factors=0, n_cov=0, n_regions=0):
     if n_regions:
         fields.append(Field("raw_", keys, (3, 256), True))
         fields.append(Field("regions", keys, (4,), False))
+    if n_segments:
+        fields.append(Field("segments", keys, (n_segments, 4), False))
+        if n_regions:
+            fields.append(Field("raw_segments", keys, (n_segments, 4), False))
     return tuple(fields)
 
 

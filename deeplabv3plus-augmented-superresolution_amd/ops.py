@@ -885,16 +885,16 @@ def guided_filter(guide, p, radius=8, eps=1e-3, out=None):
 
 
 # ---------------------------------------------------------------------------------------------
-def _region_int(v, name):
+def _region_int(v, name, what="min_region"):
     try:
         if isinstance(v, (bool, str, bytes)):
             raise TypeError
         n = int(v)
         same = float(v) == float(n)
     except (TypeError, ValueError, OverflowError):
-        raise ValueError(f"min_region: {name} must be an integer, got {v!r}") from None
+        raise ValueError(f"{what}: {name} must be an integer, got {v!r}") from None
     if not same:
-        raise ValueError(f"min_region: {name} must be an integer, got {v!r}")
+        raise ValueError(f"{what}: {name} must be an integer, got {v!r}")
     return n
 
 
@@ -964,6 +964,64 @@ def clean_labels(labels, min_area, connectivity=4, regions=None, out=None, want_
     if want_stats:
         return out, (stats[0] if labels.dim() == 2 else stats)
     return out
+
+
+def check_segments(segments):
+    """segments of a region-by-region score as (num_labels, connectivity, include_zero): an int L, a pair (L, connectivity) or
+    a triple (L, connectivity, include_zero); 1 <= L <= 64, connectivity 4 or 8 (default 8), include_zero a bool or 0 / 1
+    (default False).  Host only; ValueError otherwise."""
+    conn, zero = 8, False
+    if isinstance(segments, (tuple, list)):
+        if not 1 <= len(segments) <= 3:
+            raise ValueError(f"segments must be L, (L, connectivity) or (L, connectivity, include_zero), got {segments!r}")
+        labels = _region_int(segments[0], "num_labels", "segments")
+        if len(segments) > 1:
+            conn = _region_int(segments[1], "connectivity", "segments")
+        if len(segments) > 2:
+            zero = segments[2]
+            if not isinstance(zero, (bool, np.bool_)) and not (isinstance(zero, (int, np.integer)) and zero in (0, 1)):
+                raise ValueError(f"segments: include_zero must be a bool, got {zero!r}")
+            zero = bool(zero)
+    else:
+        labels = _region_int(segments, "num_labels", "segments")
+    if not 1 <= labels <= _lib.MAX_SEGMENT_LABELS:
+        raise ValueError(f"segments: {labels} labels (1..{_lib.MAX_SEGMENT_LABELS})")
+    if conn not in (4, 8):
+        raise ValueError(f"segments: connectivity {conn} (4 or 8)")
+    return labels, conn, zero
+
+
+def segment_match(truth, preds, num_labels=21, connectivity=8, include_zero=False, truth_regions=None, pred_regions=None,
+                  want_planes=False, out=None):
+    """The segments of int32 prediction maps [H, W] or [M, H, W] matched against those of ONE truth [H, W] (include/asr_hip.h,
+    "segments"; asr_segment_match_i32) -> device int64 counts [M, L, 4] (TP, FP, FN, Q per label; [L, 4] for an [H, W]
+    prediction), written into out when given.  truth_regions / pred_regions: the (root, area) of label_regions(truth | preds,
+    connectivity), to reuse them; what is not given is labelled here.  want_planes: also (pred_match, truth_match), int32 of
+    preds' shape.  The workspace comes from torch's caching allocator."""
+    num_labels, connectivity, include_zero = check_segments((num_labels, connectivity, include_zero))
+    maps, h, w = _region_maps(preds, "segment_match")
+    if not isinstance(truth, torch.Tensor) or tuple(truth.shape) != (h, w):
+        shape = tuple(truth.shape) if isinstance(truth, torch.Tensor) else type(truth)
+        raise AsrError(f"segment_match: truth must be [{h}, {w}], the shape of one prediction, got {shape}")
+    t_root, t_area = label_regions(truth, connectivity) if truth_regions is None else truth_regions
+    p_root = label_regions(preds, connectivity)[0] if pred_regions is None else pred_regions[0]
+    for t, nm, like in ((t_root, "truth root", truth), (t_area, "truth area", truth), (p_root, "predicted root", preds)):
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != tuple(like.shape):
+            raise AsrError(f"segment_match: the {nm} must have the shape {tuple(like.shape)}")
+    shape = (maps, num_labels, 4) if preds.dim() == 3 else (num_labels, 4)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.int64, device=preds.device)
+    elif tuple(out.shape) != shape:
+        raise AsrError(f"segment_match: out must be {shape}, got {tuple(out.shape)}")
+    lib = _lib.load()
+    planes = (torch.empty_like(preds), torch.empty_like(preds)) if want_planes else (None, None)
+    nbytes = lib.asr_segment_match_workspace_bytes(maps, h, w)
+    ws = torch.empty(max(nbytes // 8, 1), dtype=torch.int64, device=preds.device)
+    call("asr_segment_match_i32", ptr(truth, torch.int32), ptr(t_root, torch.int32), ptr(t_area, torch.int32),
+         ptr(preds, torch.int32), ptr(p_root, torch.int32), ptr(out, torch.int64), ptr(planes[0], torch.int32, allow_none=True),
+         ptr(planes[1], torch.int32, allow_none=True), ptr(ws, torch.int64), nbytes, maps, h, w, num_labels,
+         int(include_zero), stream_ptr())
+    return (out,) + planes if want_planes else out
 
 
 MAX_SWEEP_FACTORS = 256

@@ -295,7 +295,7 @@ class HotPath:
     def run_image_labels(self, image_dev, angles, shifts, class_ids=range(1, 21), gt_dev=None, adam_starts=None,
                          sr_types=("aug", "max", "mean"), want_standard=True, prune=True, profile=None, keep_scores=False,
                          band_widths=None, band_ignore_label=255, confusion_labels=None, th_factors=None, guide=None,
-                         coverages=None, keep_uncertainty=False, min_region=None):
+                         coverages=None, keep_uncertainty=False, min_region=None, segments=None):
         """One label map per SR type from one forward pass: stage 1 and the solves are run_image_classes's; stage 2 ends in the
         fusion kernel (ops.fuse_labels) instead of K thresholds.  class_ids: K <= 32 distinct ids, none 0 (the label of "no
         class").  At each pixel the label is the class whose single-class mask is set there and whose SR output is greatest
@@ -364,11 +364,21 @@ class HotPath:
         risk-coverage counts.  The result gains "regions" {key: int64 [4] numpy: regions, small regions, pixels in small
         regions, pixels changed} and, with gt_dev, "raw_counts" and "raw_Mean_IOU", the scores before the clean-up.  With no
         class left after pruning the zero maps are one region each and the calls still run.  With min_region=None nothing
-        else is launched and nothing else returned."""
+        else is launched and nothing else returned.
+
+        segments (with gt_dev; an integer L, (L, connectivity) or (L, connectivity, include_zero), ops.check_segments; not together
+        with th_factors, whose label maps are counted and never written): the region-by-region score of include/asr_hip.h,
+        "segments".  After the last fusion (and after the clean-up when min_region is on), inside the timed SR stage, three calls
+        run: one ops.label_regions of the truth, one over all produced label maps, the standard map included, and one
+        ops.segment_match.  The result gains "segments" {key: int64 [L, 4] numpy: TP, FP, FN and Q per label, what
+        utils.segment_counts gives for that label map; utils.metrics_from_segments} in the same single copy to the host as
+        "counts".  With min_region on, the maps before the clean-up are matched too, "raw_segments" {key: int64 [L, 4]}, against
+        the same labelling of the truth; the clean-up's labelling of the maps is reused when the two connectivities agree.  With
+        segments=None nothing else is launched and nothing else returned."""
         ids = [int(c) for c in class_ids]
         opts = self.label_options(None if image_dev is None else tuple(image_dev.shape), gt_dev is not None, band_widths,
                                   band_ignore_label, confusion_labels, th_factors, guide, coverages, keep_uncertainty,
-                                  min_region)
+                                  min_region, segments)
         if any(c == 0 for c in ids):
             raise ValueError(f"class id 0 is the fallback label, never a candidate: {ids}")
         unknown = [t for t in sr_types if t not in ("aug", "max", "mean")]
@@ -401,7 +411,8 @@ class HotPath:
         fshifts = self._sr_frame(image_dev, shifts)
         with self._sr_stage_timed(profile):
             gt = self._gt_int32(gt_dev) if gt_dev is not None else None
-            tally = _LabelCounts(label_fields(keys, *opts.sizes), image_dev.device) if gt is not None else None
+            tally = (_LabelCounts(label_fields(keys, *opts.sizes, n_segments=opts.segments[0] if opts.segments else 0),
+                                  image_dev.device) if gt is not None else None)
             f_dev = ops.to_device(opts.factors, device=image_dev.device) if opts.factors is not None and kept and sr_types else None
             if tally is not None and want_standard:
                 tally.counts[0] = ops.class_counts(gt, maps[0])[0]
@@ -432,7 +443,11 @@ class HotPath:
                     if opts.factors is not None:
                         tally.sweep[:] = tally.counts[first]                             # ... under every factor
             self._advance_past(starts, adam_starts, sr_types)
-            region_stats = self._clean_label_maps(tally, gt, maps, opts.min_region) if opts.min_region is not None else None
+            t_regions = ops.label_regions(gt.view(maps.shape[1:]), opts.segments[1]) if opts.segments is not None else None
+            region_stats = (self._clean_label_maps(tally, gt, maps, opts.min_region, opts.segments, t_regions)
+                            if opts.min_region is not None else None)
+            if opts.segments is not None:
+                self._match_segments(gt, maps, opts.segments, t_regions, None, tally.segments)
             u_map = self._score_label_maps(tally, gt, maps, opts, y if kept else None, angles, fshifts)
         res = {key: maps[j] for j, key in enumerate(keys)}
         res["solved_ids"] = solved
@@ -449,7 +464,7 @@ class HotPath:
         return res
 
     def label_options(self, image_shape, has_gt, band_widths=None, band_ignore_label=255, confusion_labels=None,
-                      th_factors=None, guide=None, coverages=None, keep_uncertainty=False, min_region=None):
+                      th_factors=None, guide=None, coverages=None, keep_uncertainty=False, min_region=None, segments=None):
         """The scoring options of run_image_labels, checked and normalised into one LabelOptions; ValueError as its docstring
         says.  Host only, and nothing of self is read that the options given do not need (mode: th_factors; sr: guide).
         image_shape: the image's shape or None; has_gt: a ground truth comes with it."""
@@ -472,6 +487,13 @@ class HotPath:
             if th_factors is not None:
                 raise ValueError("th_factors with min_region: the sweep counts label maps that are never written, so there is "
                                  "nothing to clean")
+        if segments is not None:
+            segments = ops.check_segments(segments)
+            if not has_gt:
+                raise ValueError("segments needs gt_dev: the segments of a label map are matched against those of a ground truth")
+            if th_factors is not None:
+                raise ValueError("th_factors with segments: the sweep counts label maps that are never written, so there are no "
+                                 "segments to match")
         factors = None
         if th_factors is not None:
             if not has_gt:
@@ -488,16 +510,27 @@ class HotPath:
             raise ValueError("confusion_labels needs gt_dev: a confusion matrix is counted against a ground truth")
         band_ignore = -1 if bands is None or band_ignore_label is None else int(band_ignore_label)
         sizes = (len(bands or ()), n_conf, 0 if factors is None else factors.size, len(covs or ()), int(min_region is not None))
-        return LabelOptions(bands, band_ignore, n_conf, factors, guide, covs, sizes, min_region)
+        return LabelOptions(bands, band_ignore, n_conf, factors, guide, covs, sizes, min_region, segments)
 
     @staticmethod
-    def _clean_label_maps(tally, gt, maps, min_region):
+    def _match_segments(gt, maps, segments, truth_regions, pred_regions, out):
+        """ops.segment_match of the label maps [M, H, W] against gt into out [M, L, 4]; pred_regions None: labelled here."""
+        num_labels, connectivity, include_zero = segments
+        ops.segment_match(gt.view(maps.shape[1:]), maps, num_labels, connectivity, include_zero, truth_regions=truth_regions,
+                          pred_regions=pred_regions, out=out)
+
+    @staticmethod
+    def _clean_label_maps(tally, gt, maps, min_region, segments=None, truth_regions=None):
         """The small regions of the finished label maps [M, H, W] removed in place (one labelling and one clean-up call over
         all of them); with a tally the raw counts kept, the counts taken again on the cleaned maps and the region statistics
-        stored.  Returns the statistics, device int64 [M, 4]."""
+        stored.  With segments the maps are matched against the truth before they change (tally.raw_segments), on the
+        clean-up's own labelling when the connectivities agree.  Returns the statistics, device int64 [M, 4]."""
         min_area, connectivity = min_region
-        _, stats = ops.clean_labels(maps, min_area, connectivity, regions=ops.label_regions(maps, connectivity), out=maps,
-                                    want_stats=True)
+        regions = ops.label_regions(maps, connectivity)
+        if segments is not None:
+            HotPath._match_segments(gt, maps, segments, truth_regions, regions if segments[1] == connectivity else None,
+                                    tally.raw_segments)
+        _, stats = ops.clean_labels(maps, min_area, connectivity, regions=regions, out=maps, want_stats=True)
         if tally is not None:
             tally.raw[:] = tally.counts
             for j in range(maps.shape[0]):
@@ -566,15 +599,15 @@ class HotPath:
 
 # HotPath.label_options' value: band widths | None and the label left out of the bands (-1: none), confusion labels (0: off),
 # float32 threshold factors | None, the guide's (radius, eps) | None, coverages | None; sizes: (B, L, T, C, R), 0 where off (R: 1
-# with min_region); min_region: (min_area, connectivity) | None
-LabelOptions = namedtuple("LabelOptions", "bands band_ignore n_conf factors guide covs sizes min_region")
+# with min_region); min_region: (min_area, connectivity) | None; segments: (num_labels, connectivity, include_zero) | None
+LabelOptions = namedtuple("LabelOptions", "bands band_ignore n_conf factors guide covs sizes min_region segments")
 
 
 class _LabelCounts:
     """The counts of run_image_labels on the device, one int64 allocation so that they reach the host in one copy: the fields
     of label_record.label_layout one after another; after them, with C coverages, C + 1 pixel totals (the counted pixels each
     coverage retained, then all of them).  Each field that is on is the attribute of its prefix's name -- counts, band,
-    confusion, sweep, coverage, raw, regions -- as [len(keys), *shape]: what the ops.*_counts(out=...) call of that score writes into."""
+    confusion, sweep, coverage, raw, regions, segments, raw_segments -- as [len(keys), *shape]: what the ops.*_counts(out=...) call of that score writes into."""
 
     def __init__(self, fields, device):
         spans, end = label_layout(fields, with_miou=False)

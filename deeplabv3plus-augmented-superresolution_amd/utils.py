@@ -218,6 +218,51 @@ def region_stats(label_map, min_area, connectivity=4):
     return _clean_on_device(label_map, min_area, connectivity)[1].cpu().numpy()
 
 
+def segment_counts(truth, pred, num_labels=21, connectivity=8, include_zero=False):
+    """The region-by-region counts of a prediction against a ground truth (include/asr_hip.h, "segments"): host int64 [L, 4],
+    per label TP, FP, FN and Q, the matched IoUs summed in units of 2^-30.  A numpy array or tensor each, on the host or the
+    device, [H, W] / [H, W, 1]; pred may be [M, H, W], which gives [M, L, 4]."""
+    num_labels, connectivity, include_zero = ops.check_segments((num_labels, connectivity, include_zero))
+    shapes = []
+    for m in (truth, pred):
+        shape = tuple(m.shape) if hasattr(m, "shape") else np.asarray(m).shape
+        shapes.append(shape[:2] if len(shape) == 3 and shape[-1] == 1 else shape)
+    if len(shapes[0]) != 2 or len(shapes[1]) not in (2, 3) or shapes[1][-2:] != shapes[0]:
+        raise ValueError(f"a truth of shape {shapes[0]} and a prediction of shape {shapes[1]}: segments are two-dimensional, "
+                         f"[H, W] against [H, W] or [M, H, W]")
+    dev = _lib.require_gpu()
+    t = _as_label_tensor(truth, dev).view(shapes[0])
+    p = _as_label_tensor(pred, dev).view(shapes[1])
+    return ops.segment_match(t, p, num_labels, connectivity, include_zero).cpu().numpy()
+
+
+def metrics_from_segments(counts):
+    """Panoptic quality from segment counts [L, 4] (TP, FP, FN, Q; utils.segment_counts, or their sum over images).  Pure
+    numpy, float64, NaN where a denominator is 0:
+
+      RQ [L]         TP / (TP + FP / 2 + FN / 2)
+      SQ [L]         Q / 2^30 / TP                   the mean IoU of the matches
+      PQ [L]         SQ * RQ = Q / 2^30 / (TP + FP / 2 + FN / 2), taken in that second form: 0, not NaN, for a label that has
+                     segments and no match
+      precision [L]  TP / (TP + FP)
+      recall [L]     TP / (TP + FN)
+      mean_PQ, mean_SQ, mean_RQ   over the labels with TP + FP + FN > 0 (mean_SQ: those of them with a match; NaN when there
+                     is none)"""
+    c = np.asarray(counts, dtype=np.int64)
+    if c.ndim != 2 or c.shape[1] != 4:
+        raise ValueError(f"segment counts must be [L, 4], got {c.shape}")
+    tp, fp, fn, q = (np.float64(c[:, k]) for k in range(4))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        rq = tp / (tp + fp / 2 + fn / 2)
+        sq = q / float(_lib.SEGMENTS_IOU_ONE) / tp
+        res = {"PQ": q / float(_lib.SEGMENTS_IOU_ONE) / (tp + fp / 2 + fn / 2), "SQ": sq, "RQ": rq, "precision": tp / (tp + fp), "recall": tp / (tp + fn)}
+    seen = (c[:, :3].sum(axis=1) > 0)
+    for name in ("PQ", "SQ", "RQ"):
+        vals = res[name][seen & ~np.isnan(res[name])]
+        res["mean_" + name] = float(np.mean(vals)) if vals.size else float("nan")
+    return res
+
+
 def metrics_from_confusion(M, other="ignore"):
     """The usual result table of a segmentation from one confusion matrix M [L+1, L+1] (truth in the rows, the last row and
     column the "other" bin).  Pure numpy, float64.  With row_l, col_l the sums of row and column l and d_l = M[l, l]:

@@ -587,6 +587,61 @@ int asr_clean_labels_i32(const int32_t* labels, const int32_t* root, const int32
                          void* workspace, size_t workspace_bytes, int maps, int h, int w, int connectivity, int min_area,
                          asr_stream_t stream);
 
+/* --- segments: a label map scored region by region against the ground truth (panoptic quality) -----------------------------
+ * The rule takes a truth map, a prediction map, a label count, a connectivity and a background flag (everything is integer):
+ *  - the truth T and a prediction P are int32 [h, w]; L = num_labels is the number of labels told apart, 1 <= L <= 64
+ *    (ASR_SEGMENTS_MAX_LABELS); the connectivity c is 4 or 8; the flag include_zero is off by default;
+ *  - the SEGMENT VALUES are v0 .. L-1, with v0 = 0 when include_zero is set, else 1: value 0 is "no class" and makes no segments
+ *    by default;
+ *  - a pixel is VOID when T there is outside 0 .. L-1 (255, negatives, ids >= L).  Void pixels belong to no truth segment; they
+ *    are taken out of every predicted segment's area and out of every intersection;
+ *  - a TRUTH SEGMENT g is a region of T (the regions section's definition, connectivity c) with a segment value; A_g is its
+ *    pixel count;
+ *  - a PREDICTED SEGMENT p is a region of P with a segment value.  It is labelled on the whole map, so void pixels do not cut a
+ *    region; A_p is the number of its pixels where T is not void.  A predicted segment with A_p = 0 is DROPPED and counted
+ *    nowhere;
+ *  - the INTERSECTION I(g, p) = |g n p|;
+ *  - g and p MATCH when their values are equal and 3 I > A_g + A_p, that is I / (A_g + A_p - I) > 1/2, strictly, in integers:
+ *    an IoU of exactly 1/2 is no match.  A segment is in at most one match: 3 I > A_g + A_p with A_g >= I gives 2 I > A_p, so
+ *    two matches (g, p) and (g', p) of one p would have I + I' > A_p, but truth segments are disjoint and hold no void pixel,
+ *    so I + I' <= A_p: two matches would need more than all of p's pixels.  The same with the roles swapped (A_p >= I, the
+ *    predicted segments disjoint) holds for one g and two predicted segments;
+ *  - per segment value v: TP_v the matches, FN_v the unmatched truth segments of value v, FP_v the unmatched, non-dropped
+ *    predicted segments of value v, and Q_v = sum over the matches of floor(I * 2^30 / (A_g + A_p - I))
+ *    (ASR_SEGMENTS_IOU_ONE = 1 << 30; I < 2^31, so the product fits an int64; one 64-bit integer division per match).
+ * Nothing is rounded except that one floor, and Q_v is a sum of integers: the result does not depend on arrival order, is
+ * bit-identical from call to call and to a restatement in Python integers; the error per match is below 2^-30.
+ *
+ * asr_segment_match_i32: truth, truth_root, truth_area [h, w] and preds, pred_root [maps, h, w] int32, the roots and the area
+ * those of asr_label_regions_i32 at the caller's connectivity (the match itself does not need c) -> counts [maps, L, 4] int64
+ * (TP, FP, FN, Q), zeroed by the call, rows below v0 left zero: one entry for each prediction map against the one shared truth.
+ * Two optional int32 planes [maps, h, w], either of which may be NULL:
+ *    pred_match   pixels of P in a matched segment: the root of the matched truth segment; in an unmatched, non-dropped
+ *                 segment: -1; of a non-segment value or in a dropped segment: -2
+ *    truth_match  pixels of T in a matched segment: the matched predicted root; in an unmatched segment: -1; void or of a
+ *                 non-segment value: -2
+ * The workspace holds at least asr_segment_match_workspace_bytes(maps, h, w) bytes, 8-byte aligned (as counts is), and is fully
+ * rewritten by each call (host arithmetic, 0 for a size below 1); a short one returns ASR_ERR_WORKSPACE.  Null pointers among
+ * the required arguments, num_labels outside 1..64, h or w < 1, h * w > 2^31 - 1 and maps outside 1..65535 (a map is a grid
+ * layer) return ASR_ERR_INVALID_ARG.  Refusals happen before any launch and nothing is written.
+ * How: the pixels that count are those whose predicted value is a segment value and whose truth is not void.  A workgroup of
+ * 256 threads owns an ASR_REGIONS_TILE_W x ASR_REGIONS_TILE_H tile and gathers the tile's distinct (truth root, predicted root)
+ * pairs with their pixel counts in an open-addressed LDS table (a tile has at most 1024 of them, the table 2048 slots); it then
+ * adds each distinct pair once to the map's table in the workspace, keyed by the 64-bit pair: the key is claimed with a 64-bit
+ * compare-and-swap, the count added with an integer atomic add, so an address receives one atomic per pair and tile, never one
+ * per pixel.  That table has the power of two at or above 2 h w slots and a map at most h w distinct pairs, so no input can
+ * fill it: there is no overflow path.  Later launches walk the table: one accumulates A_p, the next decides the matches and
+ * adds TP and Q (per workgroup in LDS first); a last pass over the pixels counts FN and FP from the pixels that are their own
+ * root and writes the planes.  Phases are separate launches on the caller's stream: no workgroup ever waits for another, every
+ * probe sequence and every walk is a counted loop, and the atomics are integer, device scope, relaxed -- a kernel boundary is
+ * the only ordering relied on.  A root outside the map (the planes are the caller's) takes its pixel out of the count. */
+#define ASR_SEGMENTS_MAX_LABELS 64
+#define ASR_SEGMENTS_IOU_ONE (1 << 30)
+size_t asr_segment_match_workspace_bytes(int maps, int h, int w);
+int asr_segment_match_i32(const int32_t* truth, const int32_t* truth_root, const int32_t* truth_area, const int32_t* preds,
+                          const int32_t* pred_root, int64_t* counts, int32_t* pred_match, int32_t* truth_match, void* workspace,
+                          size_t workspace_bytes, int maps, int h, int w, int num_labels, int include_zero, asr_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * DeepLabV3+ (Xception-65, OS16) layers -- model.py.  BatchNorm is folded by the caller.
  * ------------------------------------------------------------------------------------------ */

@@ -44,7 +44,15 @@ fewer than two copies saw the pixel).  Without these flags nothing else is compu
 A pixels before it is scored and saved (include/asr_hip.h, "regions": a small region takes the one value of its non-small
 surround, or 0), so every CSV above is the cleaned maps'; FILE (evaluation.write_regions_csv) holds, per label map, how many
 regions there were, how many were small, how many pixels changed, and both mIoUs before and after.  Not together with
---th_sweep / --th_factors, whose label maps are never written.  Without --min_region nothing else is computed or written."""
+--th_sweep / --th_factors, whose label maps are never written.  Without --min_region nothing else is computed or written.
+
+--segments_out seg.csv [--segment_labels 21] [--segment_connectivity {4,8}] [--segment_zero] [--class_names FILE]: the region-level
+score as well -- the connected segments of every label map matched against those of the ground truth (include/asr_hip.h,
+"segments": equal values and IoU > 1/2), summed over the images, in long form (evaluation.write_segments_csv: key, stage, label,
+TP, FP, FN, precision, recall, SQ, RQ, PQ and a mean row).  With --min_region the maps before the clean-up are matched too (stage
+"raw" next to "final"): fewer FPs at the same TPs says the clean-up removed spurious segments and lost no true one.  Value 0 makes
+segments only with --segment_zero.  Not together with --th_sweep / --th_factors.  Without --segments_out nothing else is computed
+or written."""
 import argparse
 import os
 import sys
@@ -97,7 +105,11 @@ parser.add_argument("--min_region", type=int, default=None,
                     help="remove connected regions of fewer than this many pixels from every label map before scoring it")
 parser.add_argument("--region_connectivity", type=int, choices=[4, 8], default=4, help="the regions' connectivity (default 4)")
 parser.add_argument("--regions_out", default=None, help="CSV file for the region statistics (default: <--out stem>_regions.csv)")
-parser.add_argument("--no_prune", action="store_true", help="solve every class, also those that win no pixel (same results)")
+parser.add_argument("--segments_out", default=None, help="CSV file for the region-level scores (not matched when omitted)")
+parser.add_argument("--segment_labels", type=int, default=21, help="labels 0..N-1 whose regions are segments (1..64)")
+parser.add_argument("--segment_connectivity", type=int, choices=[4, 8], default=8, help="the segments' connectivity (default 8)")
+parser.add_argument("--segment_zero", action="store_true", help="regions of value 0 are segments too")
+parser.add_argument("--no_prune",action="store_true", help="solve every class, also those that win no pixel (same results)")
 
 
 def main():
@@ -106,8 +118,9 @@ def main():
     from asr_amd import distributed as D
     from asr_amd.evaluation import (LABELMAP_KEYS, best_threshold_factors, dataset_miou, evaluate_labelmaps,
                                     write_confusion_csv, write_confusion_metrics_csv, write_labelmap_csv,
-                                    write_coverage_csv, write_labelmap_threshold_csv, write_regions_csv, write_trimap_csv)
-    from asr_amd.ops import check_coverages, check_min_region
+                                    write_coverage_csv, write_labelmap_threshold_csv, write_regions_csv, write_segments_csv,
+                                    write_trimap_csv)
+    from asr_amd.ops import check_coverages, check_min_region, check_segments
     from asr_amd.model import DeeplabV3Plus
     from asr_amd.pipeline import HotPath
     from asr_amd.superresolution_scripts.optimizer import Optimizer
@@ -145,6 +158,15 @@ def main():
             min_region = check_min_region((args.min_region, args.region_connectivity))
         except ValueError as e:
             parser.error(f"--min_region: {e}")
+    segments = None
+    if args.segments_out:
+        if factors is not None:
+            parser.error("--segments_out with --th_sweep / --th_factors: the sweep counts label maps that are never written, so "
+                         "there are no segments to match")
+        try:
+            segments = check_segments((args.segment_labels, args.segment_connectivity, args.segment_zero))
+        except ValueError as e:
+            parser.error(f"--segment_labels: {e}")
     if args.guide_eps is not None and args.guide_radius is None:
         parser.error("--guide_eps needs --guide_radius")
     guide = None
@@ -168,6 +190,8 @@ def main():
             names = [line.strip() for line in fh if line.strip()]
         if args.confusion_out and len(names) < args.confusion_labels:
             parser.error(f"--class_names holds {len(names)} names for {args.confusion_labels} labels")
+        if segments is not None and len(names) < segments[0]:
+            parser.error(f"--class_names holds {len(names)} names for {segments[0]} segment labels")
     rank, world, local_rank = D.init_from_env()
     torch.cuda.set_device(D.local_device(local_rank))
     paths = list_images(args.images, args.num_samples)
@@ -189,7 +213,8 @@ def main():
                              **(dict(th_factors=factors) if factors is not None else {}),
                              **(dict(guide=guide) if guide is not None else {}),
                              **(dict(coverages=covs, uncertainty_dir=args.uncertainty_dir) if covs is not None else {}),
-                             **(dict(min_region=min_region) if min_region is not None else {}))
+                             **(dict(min_region=min_region) if min_region is not None else {}),
+                             **(dict(segments=segments) if segments is not None else {}))
     rows, counts = out.rows, out.counts
     if rank == 0:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
@@ -235,6 +260,17 @@ def main():
                           f"{int(out.regions[j, 3])} pixels changed, dataset mIoU {dataset_miou(out.raw_counts[j]):.4f} -> "
                           f"{dataset_miou(counts[j]):.4f}")
             print(f"Wrote {reg_csv}")
+        if segments is not None:
+            from asr_amd.utils import metrics_from_segments
+            os.makedirs(os.path.dirname(os.path.abspath(args.segments_out)), exist_ok=True)
+            write_segments_csv(args.segments_out, out.segments, out.raw_segments, names)
+            for j, key in enumerate(LABELMAP_KEYS):
+                for stage, seg in (("raw", out.raw_segments), ("final", out.segments)):
+                    if seg is not None and seg[j, :, :3].any():
+                        tp, fp, fn = (int(v) for v in seg[j, :, :3].sum(axis=0))
+                        print(f"{key} ({stage}): {tp} segments matched, {fp} spurious, {fn} missed, mean PQ "
+                              f"{metrics_from_segments(seg[j])['mean_PQ']:.4f}")
+            print(f"Wrote {args.segments_out}")
     if world > 1:
         torch.distributed.barrier()
         torch.distributed.destroy_process_group()
