@@ -74,6 +74,10 @@ SIGNATURES = {
     "asr_sr_backward_cfg_f32": (_i, [_vp] * 10 + [_i] * 6 + [_fl] * 4 + [_cfg, _vp]),
     "asr_sr_loss_terms_cfg_f64": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _cfg, _vp]),
     "asr_sr_solve_cfg_f32": (_i, [_vp] * 10 + [_i, _vp, _vp, _sz] + [_i] * 6 + [_fl] * 4 + [_cfg, _vp]),
+    "asr_tv_edge_weights_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _fl, _vp]),
+    "asr_sr_backward_wtv_f32": (_i, [_vp] * 10 + [_i] * 6 + [_fl] * 4 + [_cfg, _vp, _vp, _i, _vp]),
+    "asr_sr_loss_terms_wtv_f64": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _cfg, _vp, _vp, _i, _vp]),
+    "asr_sr_solve_wtv_f32": (_i, [_vp] * 10 + [_i, _vp, _vp, _sz] + [_i] * 6 + [_fl] * 4 + [_cfg, _vp, _vp, _i, _vp]),
     "asr_realign_max_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "asr_realign_mean_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "asr_realign_max_mean_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),

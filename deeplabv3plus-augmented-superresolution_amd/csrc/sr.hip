@@ -290,6 +290,14 @@ struct SrStep {
     float btv_w[9];           // alpha^k, k = |h| + |v| (float32 pow like tf.pow)
 };
 
+// Edge weights of the weighted TV prior (include/asr_hip.h: the rule): wy[Y,X] prices the jump (Y,X) -> (Y+1,X), wx[Y,X] the
+// jump (Y,X) -> (Y,X+1).  Read only by the WTV = true instantiations; the others never touch the argument.
+struct SrTvW {
+    const float* wy;
+    const float* wx;
+    int64_t stride;           // floats between the planes of two images: H * W, or 0 for one pair shared by the batch
+};
+
 // One axis of the inverse-translate stage for one integer G_R coordinate c (pure translation:
 // the map is c + shift exactly, so x and y separate).  Bitwise the same values the generic
 // asr_tf_sample path produces, computed once per axis instead of once per tap.
@@ -323,13 +331,14 @@ __device__ __forceinline__ SrAxisTap sr_axis_tap(int c, float shift, int size, i
 }
 
 // Everything after the data-term gradient of one HR pixel: prior gradients and the optimiser update (shared by the
-// fused and the gather backward kernels).
+// fused and the gather backward kernels).  WTV: the TV branch takes (lambda_tv * w) of the edge each sign belongs to.
+template <bool WTV>
 __device__ __forceinline__ void sr_prior_and_update(const float* __restrict__ x, float* __restrict__ x_new, float* __restrict__ m,
                                                     float* __restrict__ v, float* __restrict__ vhat,
                                                     const float* __restrict__ alphas, float* __restrict__ grad_out,
                                                     const SrDims& d, int b, int X, int Y, float g_df, float lambda_tv,
                                                     float two_lambda_l2, float lambda_l1, const SrStep& st,
-                                                    float* __restrict__ x_bordered_out = nullptr) {
+                                                    const SrTvW& tw, float* __restrict__ x_bordered_out = nullptr) {
     const int H = d.H, W = d.W;
     // priors (superresolution.py:81-98): TV (forward differences, last row/col 0) or bilateral TV, L2, L1
     const float* img = x + (int64_t)b * H * W;
@@ -357,6 +366,15 @@ __device__ __forceinline__ void sr_prior_and_update(const float* __restrict__ x,
                 if (xt >= 0 && xt < W && yt >= 0 && yt < H) gb -= sgn(img[yt * W + xt] - xc) * c;
             }
         g_tv = ga + gb;
+    } else if (WTV) {
+        // four coalesced loads per pixel; the weights of the last row / column are never read
+        const float* wyp = tw.wy + (int64_t)b * tw.stride;
+        const float* wxp = tw.wx + (int64_t)b * tw.stride;
+        const float sy = (Y < H - 1) ? sgn(img[(Y + 1) * W + X] - xc) * (lambda_tv * wyp[Y * W + X]) : 0.0f;
+        const float sx = (X < W - 1) ? sgn(img[Y * W + X + 1] - xc) * (lambda_tv * wxp[Y * W + X]) : 0.0f;
+        g_tv = -sy - sx;
+        if (Y > 0) g_tv += sgn(xc - img[(Y - 1) * W + X]) * (lambda_tv * wyp[(Y - 1) * W + X]);
+        if (X > 0) g_tv += sgn(xc - img[Y * W + X - 1]) * (lambda_tv * wxp[Y * W + X - 1]);
     } else {
         const float sy = (Y < H - 1) ? sgn(img[(Y + 1) * W + X] - xc) * lambda_tv : 0.0f;
         const float sx = (X < W - 1) ? sgn(img[Y * W + X + 1] - xc) * lambda_tv : 0.0f;
@@ -520,13 +538,13 @@ __global__ __launch_bounds__(256) void sr_grad_translate_kernel(const float* __r
     }
 }
 
-template <int LOG2F>
+template <int LOG2F, bool WTV>
 __global__ __launch_bounds__(256) void sr_backward_adam_kernel(
     const float* __restrict__ x, float* __restrict__ x_new, const float* __restrict__ resid,
     const float* __restrict__ inv_rot_tf, const float* __restrict__ inv_trans_tf,
     float* __restrict__ m, float* __restrict__ v, float* __restrict__ vhat,
     const float* __restrict__ alphas /* [batch] for this iteration */, float* __restrict__ grad_out,
-    SrDims d, float two_lambda_df, float lambda_tv, float two_lambda_l2, float lambda_l1, SrStep st) {
+    SrDims d, float two_lambda_df, float lambda_tv, float two_lambda_l2, float lambda_l1, SrStep st, SrTvW tw) {
     extern __shared__ float contrib[];                     // [n][kBwdPix]
     const int X = blockIdx.x * kBwdPixX + threadIdx.x;
     const int Y = blockIdx.y * kBwdPixY + threadIdx.y;
@@ -639,7 +657,7 @@ __global__ __launch_bounds__(256) void sr_backward_adam_kernel(
     float g_df = 0.0f;
     for (int n = 0; n < d.n; ++n) g_df += contrib[n * kBwdPix + pix];   // fixed order n = 0..N-1
 
-    sr_prior_and_update(x, x_new, m, v, vhat, alphas, grad_out, d, b, X, Y, g_df, lambda_tv, two_lambda_l2, lambda_l1, st);
+    sr_prior_and_update<WTV>(x, x_new, m, v, vhat, alphas, grad_out, d, b, X, Y, g_df, lambda_tv, two_lambda_l2, lambda_l1, st, tw);
 }
 
 // Backward, gather form: one thread per HR pixel walks the copies in order (the oracle's summation order) and takes
@@ -691,12 +709,13 @@ __global__ __launch_bounds__(64) void sr_affine_flags_kernel(const float* __rest
 // it): the running sum of the data-term gradient crosses the launches through `acc` [batch, H, W] as a float32 -- the same
 // sequence of float32 additions, in copy order, as one pass over all copies, so the result does not depend on the chunking.
 // The last chunk adds the priors and applies the update.
+template <bool WTV>
 __global__ __launch_bounds__(256) void sr_backward_gather_kernel(
     const float* __restrict__ x, float* __restrict__ x_new, const float* __restrict__ gr_planes,
     const float* __restrict__ inv_rot_tf, float* __restrict__ m, float* __restrict__ v, float* __restrict__ vhat,
     const float* __restrict__ alphas, float* __restrict__ grad_out, SrDims d, float lambda_tv, float two_lambda_l2,
     float lambda_l1, SrStep st, float* __restrict__ x_bordered_out, float* __restrict__ acc, int n0, int cn,
-    const int* __restrict__ affine_flags) {
+    const int* __restrict__ affine_flags, SrTvW tw) {
     const int X = blockIdx.x * 64 + threadIdx.x;
     const int Y = blockIdx.y * 4 + threadIdx.y;
     const int b = blockIdx.z;
@@ -717,21 +736,23 @@ __global__ __launch_bounds__(256) void sr_backward_gather_kernel(
         for (; n < cn; ++n) g_df = sr_gather_chunk<1, false>(g_df, tfs + n * 8, planes + n * plane, plane, WP, H, W, fx, fy);
     }
     if (n0 + cn < d.n) { acc[o] = g_df; return; }
-    sr_prior_and_update(x, x_new, m, v, vhat, alphas, grad_out, d, b, X, Y, g_df, lambda_tv, two_lambda_l2, lambda_l1, st,
-                        x_bordered_out);
+    sr_prior_and_update<WTV>(x, x_new, m, v, vhat, alphas, grad_out, d, b, X, Y, g_df, lambda_tv, two_lambda_l2, lambda_l1, st,
+                             tw, x_bordered_out);
 }
 
 typedef void (*SrBwdKernel)(const float*, float*, const float*, const float*, const float*, float*, float*, float*,
-                            const float*, float*, SrDims, float, float, float, float, SrStep);
+                            const float*, float*, SrDims, float, float, float, float, SrStep, SrTvW);
 
-SrBwdKernel sr_backward_kernel_for(int f) {
+template <bool WTV>
+SrBwdKernel sr_backward_kernel_of(int f) {
     switch (f) {
-        case 2: return sr_backward_adam_kernel<1>;
-        case 4: return sr_backward_adam_kernel<2>;
-        case 8: return sr_backward_adam_kernel<3>;
-        default: return sr_backward_adam_kernel<0>;   // any other even factor: integer division
+        case 2: return sr_backward_adam_kernel<1, WTV>;
+        case 4: return sr_backward_adam_kernel<2, WTV>;
+        case 8: return sr_backward_adam_kernel<3, WTV>;
+        default: return sr_backward_adam_kernel<0, WTV>;   // any other even factor: integer division
     }
 }
+SrBwdKernel sr_backward_kernel_for(int f, bool wtv) { return wtv ? sr_backward_kernel_of<true>(f) : sr_backward_kernel_of<false>(f); }
 
 typedef void (*SrGradTranslateKernel)(const float*, const float*, float*, SrDims, float, int, int);
 SrGradTranslateKernel sr_grad_translate_kernel_for(int f) {
@@ -757,8 +778,9 @@ __global__ __launch_bounds__(256) void sr_loss_df_kernel(const float* __restrict
     if ((threadIdx.x & 63) == 0) atomicAdd(out + (int64_t)b * 4 + 0, acc);
 }
 
+template <bool WTV>
 __global__ __launch_bounds__(256) void sr_loss_prior_kernel(const float* __restrict__ x, double* __restrict__ out,
-                                                            int H, int W, SrStep st) {
+                                                            int H, int W, SrStep st, SrTvW tw) {
     const int b = blockIdx.y;
     const float* img = x + (int64_t)b * H * W;
     double tv = 0.0, l2 = 0.0, l1 = 0.0;
@@ -773,6 +795,11 @@ __global__ __launch_bounds__(256) void sr_loss_prior_kernel(const float* __restr
                     const float sv = (xs >= 0 && xs < W && ys >= 0 && ys < H) ? img[(int64_t)ys * W + xs] : 0.0f;
                     tv += (double)st.btv_w[abs(hh) + vv] * (double)fabsf(xc - sv);
                 }
+        } else if (WTV) {
+            const float dy = (Y < H - 1) ? img[p + W] - xc : 0.0f;
+            const float dx = (X < W - 1) ? img[p + 1] - xc : 0.0f;
+            const int64_t q = (int64_t)b * tw.stride + p;      // the last row / column: weight read, times |0|
+            tv += (double)(tw.wy[q] * fabsf(dy) + tw.wx[q] * fabsf(dx));
         } else {
             const float dy = (Y < H - 1) ? img[p + W] - xc : 0.0f;
             const float dx = (X < W - 1) ? img[p + 1] - xc : 0.0f;
@@ -1194,13 +1221,13 @@ int check_dims(const char* fn, int batch, int n, int H, int W, int h, int w, SrD
     return ASR_OK;
 }
 
-int prepare_backward(const SrDims& d) {
+int prepare_backward(const SrDims& d, bool wtv) {
     const size_t lds = sizeof(float) * (size_t)d.n * 64;
     ASR_UNSUPPORTED(lds > 160 * 1024, "asr_sr: num_aug=%d needs %zu bytes of LDS in the backward kernel (max 640 copies)", d.n, lds);
-    static AsrDeviceOnce once[4];
-    const int idx = d.f == 2 ? 1 : (d.f == 4 ? 2 : (d.f == 8 ? 3 : 0));
+    static AsrDeviceOnce once[8];
+    const int idx = (d.f == 2 ? 1 : (d.f == 4 ? 2 : (d.f == 8 ? 3 : 0))) + (wtv ? 4 : 0);
     if (lds > 64 * 1024)
-        ASR_HIP_CHECK(asr_allow_dynamic_lds(once[idx], reinterpret_cast<const void*>(sr_backward_kernel_for(d.f)), 160 * 1024));
+        ASR_HIP_CHECK(asr_allow_dynamic_lds(once[idx], reinterpret_cast<const void*>(sr_backward_kernel_for(d.f, wtv)), 160 * 1024));
     return ASR_OK;
 }
 dim3 gr_grid(const SrDims& d, int cn) {
@@ -1303,6 +1330,72 @@ asr_sr_config adam_tv_config(float one_minus_beta1, float one_minus_beta2, float
     return c;
 }
 
+// The weights of a *_wtv entry point (nullptr, nullptr, 0, false for its *_cfg twin) -> kernel argument.  Called after
+// make_step, so every refusal of the twin comes first.
+struct SrTvWArg {
+    const float* wy;
+    const float* wx;
+    int shared;
+    bool weighted;
+};
+const SrTvWArg kNoTvW = {nullptr, nullptr, 0, false};
+
+int make_tv_weights(const char* fn, const asr_sr_config* cfg, const SrTvWArg& a, int H, int W, SrTvW* tw) {
+    tw->wy = a.wy; tw->wx = a.wx; tw->stride = a.shared ? 0 : (int64_t)H * W;
+    if (!a.weighted) return ASR_OK;
+    ASR_REQUIRE(a.wy && a.wx, "%s: null pointer (wy, wx)", fn);
+    ASR_UNSUPPORTED(cfg->prior == ASR_PRIOR_BTV, "%s: bilateral TV has no weighted form here (edge weights need ASR_PRIOR_TV)", fn);
+    return ASR_OK;
+}
+
+int sr_backward_impl(const char* fn, const float* x, float* x_new, const float* resid, const float* inv_rot_tf,
+                     const float* inv_trans_tf, float* m, float* v, float* vhat, const float* alphas, float* grad_out,
+                     int batch, int n, int H, int W, int h, int w, float lambda_df, float lambda_tv, float lambda_l2,
+                     float lambda_l1, const asr_sr_config* cfg, const SrTvWArg& wa, asr_stream_t stream) {
+    ASR_REQUIRE(x && resid && inv_rot_tf && inv_trans_tf, "%s: null pointer", fn);
+    ASR_REQUIRE(x_new || grad_out, "%s: need x_new and/or grad_out", fn);
+    ASR_REQUIRE(!x_new || alphas, "%s: alphas required with x_new", fn);
+    ASR_REQUIRE(x != x_new, "%s: x_new must not alias x (the priors read neighbours)", fn);
+    SrDims d;
+    int rc = check_dims(fn, batch, n, H, W, h, w, &d);
+    if (rc != ASR_OK) return rc;
+    SrStep st;
+    rc = make_step(fn, cfg, x_new != nullptr, m, v, vhat, &st);
+    if (rc != ASR_OK) return rc;
+    SrTvW tw;
+    rc = make_tv_weights(fn, cfg, wa, H, W, &tw);
+    if (rc != ASR_OK) return rc;
+    rc = prepare_backward(d, wa.weighted);
+    if (rc != ASR_OK) return rc;
+    hipLaunchKernelGGL(sr_backward_kernel_for(d.f, wa.weighted), bwd_grid(d), kBwdBlock, bwd_lds(d), asr_stream(stream), x, x_new,
+                       resid, inv_rot_tf, inv_trans_tf, m, v, vhat, alphas, grad_out, d, 2.0f * lambda_df, lambda_tv,
+                       2.0f * lambda_l2, lambda_l1, st, tw);
+    ASR_LAUNCH_CHECK();
+    return ASR_OK;
+}
+
+int sr_loss_terms_impl(const char* fn, const float* x, const float* resid, double* terms, int batch, int n, int H, int W, int h,
+                       int w, const asr_sr_config* cfg, const SrTvWArg& wa, asr_stream_t stream) {
+    ASR_REQUIRE(x && resid && terms, "%s: null pointer", fn);
+    ASR_REQUIRE(batch > 0 && batch <= 65535, "%s: bad batch %d", fn, batch);
+    SrStep st;
+    int rc = make_step(fn, cfg, false, nullptr, nullptr, nullptr, &st);
+    if (rc != ASR_OK) return rc;
+    SrTvW tw;
+    rc = make_tv_weights(fn, cfg, wa, H, W, &tw);
+    if (rc != ASR_OK) return rc;
+    if (wa.weighted) ASR_REQUIRE(n > 0 && H > 0 && W > 0 && h > 0 && w > 0, "%s: bad shape n=%d %dx%d <- %dx%d", fn, n, H, W, h, w);
+    hipStream_t s = asr_stream(stream);
+    ASR_HIP_CHECK(hipMemsetAsync(terms, 0, sizeof(double) * 4 * batch, s));
+    const int64_t per_image = (int64_t)n * h * w;
+    hipLaunchKernelGGL(sr_loss_df_kernel, dim3(64, batch), dim3(256), 0, s, resid, terms, per_image);
+    ASR_LAUNCH_CHECK();
+    if (wa.weighted) hipLaunchKernelGGL(sr_loss_prior_kernel<true>, dim3(64, batch), dim3(256), 0, s, x, terms, H, W, st, tw);
+    else hipLaunchKernelGGL(sr_loss_prior_kernel<false>, dim3(64, batch), dim3(256), 0, s, x, terms, H, W, st, tw);
+    ASR_LAUNCH_CHECK();
+    return ASR_OK;
+}
+
 }  // namespace
 
 extern "C" int asr_sr_backward_cfg_f32(const float* x, float* x_new, const float* resid, const float* inv_rot_tf,
@@ -1310,23 +1403,18 @@ extern "C" int asr_sr_backward_cfg_f32(const float* x, float* x_new, const float
                                        float* grad_out, int batch, int n, int H, int W, int h, int w, float lambda_df,
                                        float lambda_tv, float lambda_l2, float lambda_l1, const asr_sr_config* cfg,
                                        asr_stream_t stream) {
-    ASR_REQUIRE(x && resid && inv_rot_tf && inv_trans_tf, "asr_sr_backward_cfg_f32: null pointer");
-    ASR_REQUIRE(x_new || grad_out, "asr_sr_backward_cfg_f32: need x_new and/or grad_out");
-    ASR_REQUIRE(!x_new || alphas, "asr_sr_backward_cfg_f32: alphas required with x_new");
-    ASR_REQUIRE(x != x_new, "asr_sr_backward_cfg_f32: x_new must not alias x (the priors read neighbours)");
-    SrDims d;
-    int rc = check_dims("asr_sr_backward_cfg_f32", batch, n, H, W, h, w, &d);
-    if (rc != ASR_OK) return rc;
-    SrStep st;
-    rc = make_step("asr_sr_backward_cfg_f32", cfg, x_new != nullptr, m, v, vhat, &st);
-    if (rc != ASR_OK) return rc;
-    rc = prepare_backward(d);
-    if (rc != ASR_OK) return rc;
-    hipLaunchKernelGGL(sr_backward_kernel_for(d.f), bwd_grid(d), kBwdBlock, bwd_lds(d), asr_stream(stream), x, x_new, resid, inv_rot_tf,
-                       inv_trans_tf, m, v, vhat, alphas, grad_out, d, 2.0f * lambda_df, lambda_tv, 2.0f * lambda_l2,
-                       lambda_l1, st);
-    ASR_LAUNCH_CHECK();
-    return ASR_OK;
+    return sr_backward_impl("asr_sr_backward_cfg_f32", x, x_new, resid, inv_rot_tf, inv_trans_tf, m, v, vhat, alphas, grad_out,
+                            batch, n, H, W, h, w, lambda_df, lambda_tv, lambda_l2, lambda_l1, cfg, kNoTvW, stream);
+}
+
+extern "C" int asr_sr_backward_wtv_f32(const float* x, float* x_new, const float* resid, const float* inv_rot_tf,
+                                       const float* inv_trans_tf, float* m, float* v, float* vhat, const float* alphas,
+                                       float* grad_out, int batch, int n, int H, int W, int h, int w, float lambda_df,
+                                       float lambda_tv, float lambda_l2, float lambda_l1, const asr_sr_config* cfg,
+                                       const float* wy, const float* wx, int w_shared, asr_stream_t stream) {
+    const SrTvWArg wa = {wy, wx, w_shared, true};
+    return sr_backward_impl("asr_sr_backward_wtv_f32", x, x_new, resid, inv_rot_tf, inv_trans_tf, m, v, vhat, alphas, grad_out,
+                            batch, n, H, W, h, w, lambda_df, lambda_tv, lambda_l2, lambda_l1, cfg, wa, stream);
 }
 
 extern "C" int asr_sr_backward_adam_f32(const float* x, float* x_new, const float* resid, const float* inv_rot_tf,
@@ -1342,19 +1430,14 @@ extern "C" int asr_sr_backward_adam_f32(const float* x, float* x_new, const floa
 
 extern "C" int asr_sr_loss_terms_cfg_f64(const float* x, const float* resid, double* terms, int batch, int n, int H, int W,
                                          int h, int w, const asr_sr_config* cfg, asr_stream_t stream) {
-    ASR_REQUIRE(x && resid && terms, "asr_sr_loss_terms_cfg_f64: null pointer");
-    ASR_REQUIRE(batch > 0 && batch <= 65535, "asr_sr_loss_terms_cfg_f64: bad batch %d", batch);
-    SrStep st;
-    int rc = make_step("asr_sr_loss_terms_cfg_f64", cfg, false, nullptr, nullptr, nullptr, &st);
-    if (rc != ASR_OK) return rc;
-    hipStream_t s = asr_stream(stream);
-    ASR_HIP_CHECK(hipMemsetAsync(terms, 0, sizeof(double) * 4 * batch, s));
-    const int64_t per_image = (int64_t)n * h * w;
-    hipLaunchKernelGGL(sr_loss_df_kernel, dim3(64, batch), dim3(256), 0, s, resid, terms, per_image);
-    ASR_LAUNCH_CHECK();
-    hipLaunchKernelGGL(sr_loss_prior_kernel, dim3(64, batch), dim3(256), 0, s, x, terms, H, W, st);
-    ASR_LAUNCH_CHECK();
-    return ASR_OK;
+    return sr_loss_terms_impl("asr_sr_loss_terms_cfg_f64", x, resid, terms, batch, n, H, W, h, w, cfg, kNoTvW, stream);
+}
+
+extern "C" int asr_sr_loss_terms_wtv_f64(const float* x, const float* resid, double* terms, int batch, int n, int H, int W,
+                                         int h, int w, const asr_sr_config* cfg, const float* wy, const float* wx,
+                                         int w_shared, asr_stream_t stream) {
+    const SrTvWArg wa = {wy, wx, w_shared, true};
+    return sr_loss_terms_impl("asr_sr_loss_terms_wtv_f64", x, resid, terms, batch, n, H, W, h, w, cfg, wa, stream);
 }
 
 extern "C" int asr_sr_loss_terms_f64(const float* x, const float* resid, double* terms, int batch, int n, int H, int W,
@@ -1376,27 +1459,29 @@ extern "C" size_t asr_sr_solve_workspace_bytes_cfg(int batch, int n, int H, int 
 // workspace.  alphas[it*batch + b] = the per-step scalar of image b at its own global optimiser
 // step (device array, prepared by the host wrapper so that the schedule and the persistent step
 // counter follow optimizer.py exactly).
-extern "C" int asr_sr_solve_cfg_f32(float* x, const float* y, const float* rot_tf, const float* trans_tf,
-                                    const float* inv_rot_tf, const float* inv_trans_tf, float* m, float* v, float* vhat,
-                                    const float* alphas, int num_iter, double* last_loss_terms, void* workspace,
-                                    size_t workspace_bytes, int batch, int n, int H, int W, int h, int w,
-                                    float lambda_df, float lambda_tv, float lambda_l2, float lambda_l1,
-                                    const asr_sr_config* cfg, asr_stream_t stream) {
-    ASR_REQUIRE(x && y && rot_tf && trans_tf && inv_rot_tf && inv_trans_tf && alphas && workspace,
-                "asr_sr_solve_cfg_f32: null pointer");
-    ASR_REQUIRE(num_iter >= 0, "asr_sr_solve_cfg_f32: num_iter < 0");
+namespace {
+int sr_solve_impl(const char* fn, float* x, const float* y, const float* rot_tf, const float* trans_tf, const float* inv_rot_tf,
+                  const float* inv_trans_tf, float* m, float* v, float* vhat, const float* alphas, int num_iter,
+                  double* last_loss_terms, void* workspace, size_t workspace_bytes, int batch, int n, int H, int W, int h, int w,
+                  float lambda_df, float lambda_tv, float lambda_l2, float lambda_l1, const asr_sr_config* cfg,
+                  const SrTvWArg& wa, asr_stream_t stream) {
+    ASR_REQUIRE(x && y && rot_tf && trans_tf && inv_rot_tf && inv_trans_tf && alphas && workspace, "%s: null pointer", fn);
+    ASR_REQUIRE(num_iter >= 0, "%s: num_iter < 0", fn);
     SrDims d;
-    int rc = check_dims("asr_sr_solve_cfg_f32", batch, n, H, W, h, w, &d);
+    int rc = check_dims(fn, batch, n, H, W, h, w, &d);
     if (rc != ASR_OK) return rc;
     SrStep st;
-    rc = make_step("asr_sr_solve_cfg_f32", cfg, true, m, v, vhat, &st);
+    rc = make_step(fn, cfg, true, m, v, vhat, &st);
     if (rc != ASR_OK) return rc;
-    ASR_REQUIRE(cfg->plane_chunk >= 0, "asr_sr_solve_cfg_f32: plane_chunk %d < 0", cfg->plane_chunk);
+    SrTvW tw;
+    rc = make_tv_weights(fn, cfg, wa, H, W, &tw);
+    if (rc != ASR_OK) return rc;
+    ASR_REQUIRE(cfg->plane_chunk >= 0, "%s: plane_chunk %d < 0", fn, cfg->plane_chunk);
     const int chunk = sr_plane_chunk(batch, n, H, W, cfg->plane_chunk);
-    ASR_REQUIRE((int64_t)batch * chunk <= 65535, "asr_sr_solve_cfg_f32: batch*chunk=%lld exceeds 65535 (grid.z)", (long long)batch * chunk);
+    ASR_REQUIRE((int64_t)batch * chunk <= 65535, "%s: batch*chunk=%lld exceeds 65535 (grid.z)", fn, (long long)batch * chunk);
     const size_t need = sr_workspace_bytes(batch, n, H, W, h, w, chunk);
     if (workspace_bytes < need) {
-        asr_set_error("asr_sr_solve_cfg_f32: workspace %zu < required %zu bytes", workspace_bytes, need);
+        asr_set_error("%s: workspace %zu < required %zu bytes", fn, workspace_bytes, need);
         return ASR_ERR_WORKSPACE;
     }
     hipStream_t s = asr_stream(stream);
@@ -1426,22 +1511,87 @@ extern "C" int asr_sr_solve_cfg_f32(float* x, const float* y, const float* rot_t
         hipLaunchKernelGGL(sr_forward_residual_kernel<true>, lr_grid(d), kBlock, 0, s, xb, y, rot_tf, trans_tf, resid, d);
         ASR_LAUNCH_CHECK();
         if (last_loss_terms && it == num_iter - 1) {
-            rc = asr_sr_loss_terms_cfg_f64(cur, resid, last_loss_terms, batch, n, H, W, h, w, cfg, stream);
+            rc = sr_loss_terms_impl(fn, cur, resid, last_loss_terms, batch, n, H, W, h, w, cfg, wa, stream);
             if (rc != ASR_OK) return rc;
         }
         for (int n0 = 0; n0 < n; n0 += chunk) {
             const int cn = n - n0 < chunk ? n - n0 : chunk;
             hipLaunchKernelGGL(gr_kernel, gr_grid(d, cn), dim3(64, 4), 0, s, resid, inv_trans_tf, gr, d, 2.0f * lambda_df, n0, cn);
             ASR_LAUNCH_CHECK();
-            hipLaunchKernelGGL(sr_backward_gather_kernel, gather_grid(d), dim3(64, 4), 0, s, cur, nxt, gr, inv_rot_tf, m, v, vhat,
+            const auto bwd_kernel = wa.weighted ? sr_backward_gather_kernel<true> : sr_backward_gather_kernel<false>;
+            hipLaunchKernelGGL(bwd_kernel, gather_grid(d), dim3(64, 4), 0, s, cur, nxt, gr, inv_rot_tf, m, v, vhat,
                                alphas + (size_t)it * batch, (float*)nullptr, d, lambda_tv, 2.0f * lambda_l2, lambda_l1, st, xb,
-                               acc, n0, cn, affine_flags);
+                               acc, n0, cn, affine_flags, tw);
             ASR_LAUNCH_CHECK();
         }
         float* t = cur; cur = nxt; nxt = t;
     }
     if (cur != x) ASR_HIP_CHECK(hipMemcpyAsync(x, cur, sizeof(float) * (size_t)batch * H * W, hipMemcpyDeviceToDevice, s));
     return ASR_OK;
+}
+
+// wy[Y,X] = 1 / (1 + beta * |I[Y+1,X] - I[Y,X]|^2), wx the same along X; the last row of wy and the last column of wx are 1
+// (include/asr_hip.h: the rule).  One thread per pixel; every product and sum rounds by itself, in the order written.
+__global__ __launch_bounds__(256) SR_NO_PK_F32 void sr_tv_edge_weights_kernel(const float* __restrict__ guide, float* __restrict__ wy,
+                                                                              float* __restrict__ wx, int H, int W, float beta) {
+    const int X = blockIdx.x * kTileX + threadIdx.x;
+    const int Y = blockIdx.y * kTileY + threadIdx.y;
+    if (X >= W || Y >= H) return;
+    const int64_t o = ((int64_t)blockIdx.z * H + Y) * W + X;
+    // (no lambda: one would not inherit the kernel's target attribute and would stay a call with its captures in scratch)
+    const float* c = guide + o * 3;
+    const float c0 = c[0], c1 = c[1], c2 = c[2];
+    float vy = 1.0f, vx = 1.0f;
+    if (Y < H - 1) {
+        const float* q = c + (int64_t)W * 3;
+        const float a0 = q[0] - c0, a1 = q[1] - c1, a2 = q[2] - c2;
+        const float dd = (a0 * a0 + a1 * a1) + a2 * a2;
+        vy = 1.0f / (1.0f + beta * dd);
+    }
+    if (X < W - 1) {
+        const float a0 = c[3] - c0, a1 = c[4] - c1, a2 = c[5] - c2;
+        const float dd = (a0 * a0 + a1 * a1) + a2 * a2;
+        vx = 1.0f / (1.0f + beta * dd);
+    }
+    wy[o] = vy;
+    wx[o] = vx;
+}
+}  // namespace
+
+extern "C" int asr_tv_edge_weights_f32(const float* guide, float* wy, float* wx, int batch, int H, int W, float beta,
+                                       asr_stream_t stream) {
+    ASR_REQUIRE(guide && wy && wx, "asr_tv_edge_weights_f32: null pointer");
+    ASR_REQUIRE(batch > 0 && batch <= 65535 && H > 0 && W > 0, "asr_tv_edge_weights_f32: bad shape batch=%d %dx%d", batch, H, W);
+    ASR_REQUIRE(beta >= 0.0f && beta < __builtin_inff(), "asr_tv_edge_weights_f32: beta=%g must be finite and >= 0", (double)beta);
+    SrDims d;
+    d.batch = batch; d.n = 1; d.H = H; d.W = W; d.h = H; d.w = W; d.f = 0;
+    hipLaunchKernelGGL(sr_tv_edge_weights_kernel, hr_grid(d), kBlock, 0, asr_stream(stream), guide, wy, wx, H, W, beta);
+    ASR_LAUNCH_CHECK();
+    return ASR_OK;
+}
+
+extern "C" int asr_sr_solve_cfg_f32(float* x, const float* y, const float* rot_tf, const float* trans_tf,
+                                    const float* inv_rot_tf, const float* inv_trans_tf, float* m, float* v, float* vhat,
+                                    const float* alphas, int num_iter, double* last_loss_terms, void* workspace,
+                                    size_t workspace_bytes, int batch, int n, int H, int W, int h, int w,
+                                    float lambda_df, float lambda_tv, float lambda_l2, float lambda_l1,
+                                    const asr_sr_config* cfg, asr_stream_t stream) {
+    return sr_solve_impl("asr_sr_solve_cfg_f32", x, y, rot_tf, trans_tf, inv_rot_tf, inv_trans_tf, m, v, vhat, alphas, num_iter,
+                         last_loss_terms, workspace, workspace_bytes, batch, n, H, W, h, w, lambda_df, lambda_tv, lambda_l2,
+                         lambda_l1, cfg, kNoTvW, stream);
+}
+
+extern "C" int asr_sr_solve_wtv_f32(float* x, const float* y, const float* rot_tf, const float* trans_tf,
+                                    const float* inv_rot_tf, const float* inv_trans_tf, float* m, float* v, float* vhat,
+                                    const float* alphas, int num_iter, double* last_loss_terms, void* workspace,
+                                    size_t workspace_bytes, int batch, int n, int H, int W, int h, int w,
+                                    float lambda_df, float lambda_tv, float lambda_l2, float lambda_l1,
+                                    const asr_sr_config* cfg, const float* wy, const float* wx, int w_shared,
+                                    asr_stream_t stream) {
+    const SrTvWArg wa = {wy, wx, w_shared, true};
+    return sr_solve_impl("asr_sr_solve_wtv_f32", x, y, rot_tf, trans_tf, inv_rot_tf, inv_trans_tf, m, v, vhat, alphas, num_iter,
+                         last_loss_terms, workspace, workspace_bytes, batch, n, H, W, h, w, lambda_df, lambda_tv, lambda_l2,
+                         lambda_l1, cfg, wa, stream);
 }
 
 extern "C" int asr_sr_solve_f32(float* x, const float* y, const float* rot_tf, const float* trans_tf,

@@ -286,7 +286,7 @@ def dataset_miou(counts):
 def evaluate_labelmaps(path, image_paths, gt_paths, class_ids=tuple(range(1, 21)), num_aug=100, angle_max=0.3, shift_max=30,
                        img_size=(512, 512), rank=0, world=1, seed=1234, sr_types=("aug", "max", "mean"), prune=True,
                        save_dir=None, band_widths=None, band_ignore_label=255, confusion_labels=None, th_factors=None,
-                       guide=None, min_region=None, segments=None, coverages=None, uncertainty_dir=None):
+                       guide=None, tv_guide=None, min_region=None, segments=None, coverages=None, uncertainty_dir=None):
     """One fused label map per image and SR type (HotPath.run_image_labels) and its score.  Returns on every rank a
     LabelmapScores, the tuple (rows, counts) plus what the options below append, every entry also an attribute by the name
     given here: rows [images, 4] per-image Mean_IOU in LABELMAP_KEYS order (the reference's per-image-then-mean convention;
@@ -317,6 +317,10 @@ def evaluate_labelmaps(path, image_paths, gt_paths, class_ids=tuple(range(1, 21)
     guide ((radius, eps)): every SR score map is refined with the guided filter against its image before the fusion
     (run_image_labels' guide; img_size must be the SR output size).  The return value keeps its form.
 
+    tv_guide (beta, finite and >= 0): every image's "aug" solves weight their TV prior by the image's own edges
+    (run_image_labels' tv_guide; img_size must be the SR output size, no bilateral TV).  Independent of guide.  The return
+    value keeps its form.
+
     coverages (C whole percentages in [1, 100], 1..16): the same loop also collects each label map's counts over its p % most
     certain pixels (run_image_labels' coverages: the variance of the class stacks over the copies, no further forward pass
     or solve) and the return value ends in two more entries, after the sweep's: cov_rows [images, 4, C] per-image Mean_IOU
@@ -341,6 +345,8 @@ def evaluate_labelmaps(path, image_paths, gt_paths, class_ids=tuple(range(1, 21)
         raise ValueError("uncertainty_dir needs coverages: the uncertainty map is only built for the risk-coverage curve")
     opts = path.label_options(tuple(img_size) + (3,), True, band_widths, band_ignore_label, confusion_labels, th_factors,
                               guide, coverages, bool(uncertainty_dir), min_region, segments)
+    tv_beta = path.check_tv_guide(tv_guide, tuple(img_size) + (3,))
+    tv_kw = {} if tv_beta is None else {"tv_guide": tv_beta}
     if uncertainty_dir:
         os.makedirs(uncertainty_dir, exist_ok=True)
     class_ids, params, mine = _class_set_run(class_ids, image_paths, gt_paths, rank, world, num_aug=num_aug,
@@ -359,7 +365,7 @@ def evaluate_labelmaps(path, image_paths, gt_paths, class_ids=tuple(range(1, 21)
                                     band_widths=opts.bands, band_ignore_label=band_ignore_label,
                                     confusion_labels=opts.n_conf or None, th_factors=opts.factors, guide=opts.guide,
                                     coverages=opts.covs, keep_uncertainty=bool(uncertainty_dir), min_region=opts.min_region,
-                                    segments=opts.segments)
+                                    segments=opts.segments, **tv_kw)
         for f, (mious, counts) in local.items():        # a label map that was not produced: NaN Mean_IOU, zero counts
             if f.scored:
                 mious.append([res[f.prefix + "Mean_IOU"].get(key, np.full(f.shape[:-2], np.nan)) for key in f.keys])

@@ -123,10 +123,56 @@ def _adam_config(one_minus_beta1, one_minus_beta2, epsilon, amsgrad):
     return sr_config(_lib.OPT_ADAM, amsgrad, one_minus_beta1, one_minus_beta2, epsilon)
 
 
-def sr_backward(x, resid, inv_rot_tf, inv_trans_tf, lambdas, cfg, state=None, want_grad=False):
+def check_tv_beta(beta, name="tv_edge_weights"):
+    """beta of the edge weights: a finite number >= 0 (host check, before any launch)."""
+    import numbers
+    ok = isinstance(beta, numbers.Real) and not isinstance(beta, bool) and np.isfinite(float(beta)) and float(beta) >= 0.0
+    if not ok:
+        raise ValueError(f"{name}: beta must be a finite number >= 0, got {beta!r}")
+    return float(beta)
+
+
+def tv_edge_weights(guide, beta):
+    """guide [H,W,3] or [B,H,W,3] (RGB in [0, 1]) -> (wy, wx), each [H,W] or [B,H,W]: the edge weights of the weighted TV
+    prior, w = 1 / (1 + beta * |forward difference of the guide|^2), 1 in the last row (wy) / column (wx)
+    (include/asr_hip.h: the rule)."""
+    beta = check_tv_beta(beta)
+    if not isinstance(guide, torch.Tensor) or guide.dim() not in (3, 4) or guide.shape[-1] != 3:
+        raise AsrError(f"tv_edge_weights: guide must be a [H,W,3] or [B,H,W,3] tensor, got "
+                       f"{tuple(guide.shape) if hasattr(guide, 'shape') else type(guide).__name__}")
+    if guide.dtype != f32 or not guide.is_contiguous():
+        raise AsrError("tv_edge_weights: guide must be contiguous float32")
+    shape = tuple(guide.shape[:-1])
+    if min(shape) < 1:
+        raise AsrError(f"tv_edge_weights: empty guide {tuple(guide.shape)}")
+    b = shape[0] if guide.dim() == 4 else 1
+    wy = torch.empty(shape, dtype=f32, device=guide.device)
+    wx = torch.empty(shape, dtype=f32, device=guide.device)
+    call("asr_tv_edge_weights_f32", ptr(guide), ptr(wy), ptr(wx), b, shape[-2], shape[-1], beta, stream_ptr())
+    return wy, wx
+
+
+def _tv_weights(tv_weights, x, name):
+    """(wy, wx) of a weighted-TV call -> (wy, wx, shared): [H,W] planes are shared by the batch, [B,H,W] are per image."""
+    if not isinstance(tv_weights, (tuple, list)) or len(tv_weights) != 2:
+        raise AsrError(f"{name}: tv_weights must be a pair (wy, wx)")
+    wy, wx = tv_weights
+    b, H, W = x.shape
+    for t, nm in ((wy, "wy"), (wx, "wx")):
+        if not isinstance(t, torch.Tensor) or t.dtype != f32 or not t.is_contiguous() or t.device != x.device:
+            raise AsrError(f"{name}: tv_weights {nm} must be a contiguous float32 tensor on the device of x")
+    if tuple(wy.shape) != tuple(wx.shape) or tuple(wy.shape) not in ((H, W), (b, H, W)):
+        raise AsrError(f"{name}: tv_weights must both be [{H},{W}] (shared) or [{b},{H},{W}], got {tuple(wy.shape)} "
+                       f"{tuple(wx.shape)}")
+    return wy, wx, int(wy.dim() == 2)
+
+
+def sr_backward(x, resid, inv_rot_tf, inv_trans_tf, lambdas, cfg, state=None, want_grad=False, tv_weights=None):
     """One step with the update rule / prior of cfg.  state = dict(m, v, vhat, alphas[B]) (slots the optimizer
-    does not use may be None) or None for the gradient only.  Returns (x_new | None, grad | None)."""
+    does not use may be None) or None for the gradient only.  tv_weights = (wy, wx): the edge-weighted TV prior
+    (tv_edge_weights, or any finite weights >= 0).  Returns (x_new | None, grad | None)."""
     b, n, H, W, h, w = _sr_dims(x, resid)
+    tvw = _tv_weights(tv_weights, x, "sr_backward") if tv_weights is not None else None
     _check_tf(inv_rot_tf, b, n, "inv_rot_tf")
     _check_tf(inv_trans_tf, b, n, "inv_trans_tf")
     grad = torch.empty_like(x) if (want_grad or state is None) else None
@@ -138,11 +184,14 @@ def sr_backward(x, resid, inv_rot_tf, inv_trans_tf, lambdas, cfg, state=None, wa
                 raise AsrError(f"state['{k}'] shape mismatch")
         if st["alphas"].numel() != b:
             raise AsrError("state['alphas'] must hold one value per image")
-    call("asr_sr_backward_cfg_f32", ptr(x), ptr(x_new, allow_none=True), ptr(resid), ptr(inv_rot_tf),
-         ptr(inv_trans_tf), ptr(st.get("m"), allow_none=True), ptr(st.get("v"), allow_none=True),
-         ptr(st.get("vhat"), allow_none=True), ptr(st.get("alphas"), allow_none=True), ptr(grad, allow_none=True),
-         b, n, H, W, h, w, float(lambdas[0]), float(lambdas[1]), float(lambdas[2]), float(lambdas[3]), C.byref(cfg),
-         stream_ptr())
+    args = (ptr(x), ptr(x_new, allow_none=True), ptr(resid), ptr(inv_rot_tf),
+            ptr(inv_trans_tf), ptr(st.get("m"), allow_none=True), ptr(st.get("v"), allow_none=True),
+            ptr(st.get("vhat"), allow_none=True), ptr(st.get("alphas"), allow_none=True), ptr(grad, allow_none=True),
+            b, n, H, W, h, w, float(lambdas[0]), float(lambdas[1]), float(lambdas[2]), float(lambdas[3]), C.byref(cfg))
+    if tvw is None:
+        call("asr_sr_backward_cfg_f32", *args, stream_ptr())
+    else:
+        call("asr_sr_backward_wtv_f32", *args, ptr(tvw[0]), ptr(tvw[1]), tvw[2], stream_ptr())
     return x_new, grad
 
 
@@ -170,11 +219,15 @@ def sr_backward_adam(x, resid, inv_rot_tf, inv_trans_tf, lambdas, adam=None, wan
     return x_new, grad
 
 
-def sr_loss_terms(x, resid, cfg=None):
-    """[B,4] float64 {sum resid^2, TV or bilateral TV (cfg), sum x^2, sum |x|}."""
+def sr_loss_terms(x, resid, cfg=None, tv_weights=None):
+    """[B,4] float64 {sum resid^2, TV or bilateral TV (cfg) or the edge-weighted TV (tv_weights), sum x^2, sum |x|}."""
     b, n, H, W, h, w = _sr_dims(x, resid)
+    tvw = _tv_weights(tv_weights, x, "sr_loss_terms") if tv_weights is not None else None
     terms = torch.empty((b, 4), dtype=torch.float64, device=x.device)
-    if cfg is None:
+    if tvw is not None:
+        call("asr_sr_loss_terms_wtv_f64", ptr(x), ptr(resid), ptr(terms, torch.float64), b, n, H, W, h, w,
+             C.byref(cfg if cfg is not None else sr_config()), ptr(tvw[0]), ptr(tvw[1]), tvw[2], stream_ptr())
+    elif cfg is None:
         call("asr_sr_loss_terms_f64", ptr(x), ptr(resid), ptr(terms, torch.float64), b, n, H, W, h, w, stream_ptr())
     else:
         call("asr_sr_loss_terms_cfg_f64", ptr(x), ptr(resid), ptr(terms, torch.float64), b, n, H, W, h, w, C.byref(cfg),
@@ -183,12 +236,17 @@ def sr_loss_terms(x, resid, cfg=None):
 
 
 def sr_solve(x, y, rot_tf, trans_tf, inv_rot_tf, inv_trans_tf, alphas, lambdas, one_minus_beta1=None, one_minus_beta2=None,
-             epsilon=None, amsgrad=False, want_loss=True, cfg=None, slot_init=None, state=None):
+             epsilon=None, amsgrad=False, want_loss=True, cfg=None, slot_init=None, state=None, tv_weights=None):
     """Runs alphas.shape[0] iterations in place on x.  alphas [num_iter, B] (device).  Either the Adam
     hyper-parameters (asr_sr_solve_f32) or cfg (+ slot_init = {"m"/"v"/"vhat": initial value}) for
     asr_sr_solve_cfg_f32.  state: a dict that carries the optimiser slots and the workspace from one call to the next --
-    a solve cut into several calls (the verbose loss print-outs) then performs exactly the updates of a single call."""
+    a solve cut into several calls (the verbose loss print-outs) then performs exactly the updates of a single call.
+    tv_weights = (wy, wx): the edge-weighted TV prior; with the Adam hyper-parameters instead of cfg the call goes through
+    the equivalent {Adam, TV} config."""
     b, n, H, W, h, w = _sr_dims(x, y)
+    tvw = _tv_weights(tv_weights, x, "sr_solve") if tv_weights is not None else None
+    if tvw is not None and cfg is None:
+        cfg = _adam_config(one_minus_beta1, one_minus_beta2, epsilon, amsgrad)
     for t, name in ((rot_tf, "rot_tf"), (trans_tf, "trans_tf"), (inv_rot_tf, "inv_rot_tf"), (inv_trans_tf, "inv_trans_tf")):
         _check_tf(t, b, n, name)
     if alphas.dim() != 2 or alphas.shape[1] != b:
@@ -212,7 +270,12 @@ def sr_solve(x, y, rot_tf, trans_tf, inv_rot_tf, inv_trans_tf, alphas, lambdas, 
         if state is not None:
             state.update(ws=ws, m=m, v=v, vhat=vhat)
     terms = torch.zeros((b, 4), dtype=torch.float64, device=x.device) if want_loss else None
-    if cfg is None:
+    if tvw is not None:
+        call("asr_sr_solve_wtv_f32", ptr(x), ptr(y), ptr(rot_tf), ptr(trans_tf), ptr(inv_rot_tf), ptr(inv_trans_tf), ptr(m),
+             ptr(v), ptr(vhat), ptr(alphas), num_iter, ptr(terms, torch.float64, allow_none=True), ptr(ws),
+             C.c_size_t(ws_bytes), b, n, H, W, h, w, float(lambdas[0]), float(lambdas[1]), float(lambdas[2]),
+             float(lambdas[3]), C.byref(cfg), ptr(tvw[0]), ptr(tvw[1]), tvw[2], stream_ptr())
+    elif cfg is None:
         call("asr_sr_solve_f32", ptr(x), ptr(y), ptr(rot_tf), ptr(trans_tf), ptr(inv_rot_tf), ptr(inv_trans_tf), ptr(m),
              ptr(v), ptr(vhat), ptr(alphas), num_iter, ptr(terms, torch.float64, allow_none=True), ptr(ws),
              C.c_size_t(ws_bytes), b, n, H, W, h, w, float(lambdas[0]), float(lambdas[1]), float(lambdas[2]),

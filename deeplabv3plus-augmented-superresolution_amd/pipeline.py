@@ -227,12 +227,13 @@ class HotPath:
             return [it0 + j * self._solves * sr.num_iter for j in range(len(ids))]
         return [int(adam_starts[c]) for c in ids]
 
-    def _classes_scores(self, y, ymax, angles, fshifts, starts, sr_types):
+    def _classes_scores(self, y, ymax, angles, fshifts, starts, sr_types, tv_weights=None):
         """_sr_scores of a class set: class k's solve starts at the Adam step starts[k], its max map's num_iter later; the
-        counter itself is left as it was."""
+        counter itself is left as it was.  tv_weights: the image's edge weights (wy, wx), shared by every solve."""
         sr = self.sr
+        kw = {} if tv_weights is None else {"tv_guide": tv_weights}
         solve = lambda stack, a, s, second: sr.augmented_superresolution_classes(
-            stack, a[0], s[0], [st + second * sr.num_iter for st in starts])[0]
+            stack, a[0], s[0], [st + second * sr.num_iter for st in starts], **kw)[0]
         return self._sr_scores(y, ymax, angles, fshifts, sr_types, solve)
 
     def _advance_past(self, starts, adam_starts, sr_types):
@@ -295,7 +296,7 @@ class HotPath:
     def run_image_labels(self, image_dev, angles, shifts, class_ids=range(1, 21), gt_dev=None, adam_starts=None,
                          sr_types=("aug", "max", "mean"), want_standard=True, prune=True, profile=None, keep_scores=False,
                          band_widths=None, band_ignore_label=255, confusion_labels=None, th_factors=None, guide=None,
-                         coverages=None, keep_uncertainty=False, min_region=None, segments=None):
+                         coverages=None, keep_uncertainty=False, min_region=None, tv_guide=None, segments=None):
         """One label map per SR type from one forward pass: stage 1 and the solves are run_image_classes's; stage 2 ends in the
         fusion kernel (ops.fuse_labels) instead of K thresholds.  class_ids: K <= 32 distinct ids, none 0 (the label of "no
         class").  At each pixel the label is the class whose single-class mask is set there and whose SR output is greatest
@@ -374,8 +375,17 @@ class HotPath:
         utils.segment_counts gives for that label map; utils.metrics_from_segments} in the same single copy to the host as
         "counts".  With min_region on, the maps before the clean-up are matched too, "raw_segments" {key: int64 [L, 4]}, against
         the same labelling of the truth; the clean-up's labelling of the maps is reused when the two connectivities agree.  With
-        segments=None nothing else is launched and nothing else returned."""
+        segments=None nothing else is launched and nothing else returned.
+
+        tv_guide (beta, a finite number >= 0; image_dev must be [H, W, 3] at the SR output size; not with use_BTV): a solver
+        option, not a scoring option -- the image goes INTO the "aug" solves as the edge weights of their TV prior
+        (include/asr_hip.h, "edge-weighted TV": w = 1 / (1 + beta * |forward difference of the image|^2)), so a boundary is
+        cheap where the image has an edge.  One ops.tv_edge_weights call per image inside the timed SR stage; the pair is
+        shared by the K classes' solve and, in slice_max, by the max maps' solve.  Independent of guide (which refines the
+        scores afterwards).  beta = 0 gives weights of one: every result is tv_guide=None's bit for bit.  With
+        tv_guide=None nothing else is launched and every result is what it was."""
         ids = [int(c) for c in class_ids]
+        tv_beta = self.check_tv_guide(tv_guide, None if image_dev is None else tuple(image_dev.shape))
         opts = self.label_options(None if image_dev is None else tuple(image_dev.shape), gt_dev is not None, band_widths,
                                   band_ignore_label, confusion_labels, th_factors, guide, coverages, keep_uncertainty,
                                   min_region, segments)
@@ -420,8 +430,12 @@ class HotPath:
             if opts.guide is not None and kept and sr_types:
                 g_image = image_dev.to(torch.float32).contiguous()
                 g_state = ops.guided_prepare(g_image, *opts.guide)
+            tv_weights = None
+            if tv_beta is not None and kept and "aug" in sr_types:
+                tv_weights = ops.tv_edge_weights(image_dev.to(torch.float32).contiguous(), tv_beta)
             if kept:
-                for t, tgt, tmax in self._classes_scores(y, ymax, angles, fshifts, [starts[k] for k in kept], sr_types):
+                for t, tgt, tmax in self._classes_scores(y, ymax, angles, fshifts, [starts[k] for k in kept], sr_types,
+                                                         tv_weights):
                     j = keys.index(t)
                     if g_state is not None:
                         ops.guided_apply(g_state, g_image, tgt, out=tgt)
@@ -462,6 +476,19 @@ class HotPath:
             res["uncertainty"] = u_map
             res["uncertainty_stacks"] = y if kept else None
         return res
+
+    def check_tv_guide(self, tv_guide, image_shape):
+        """run_image_labels' tv_guide, checked on the host before any launch: None, or beta as a float.  ValueError for a beta
+        that is not a finite number >= 0, an image that is not [H, W, 3] at the SR output size, and a bilateral-TV solver."""
+        if tv_guide is None:
+            return None
+        beta = ops.check_tv_beta(tv_guide, "tv_guide")
+        if image_shape != tuple(self.sr.output_size) + (3,):
+            raise ValueError(f"tv_guide needs the image as [H, W, 3] at the SR output size {tuple(self.sr.output_size)}, got "
+                             f"{image_shape}")
+        if self.sr.use_BTV:
+            raise ValueError("tv_guide: bilateral TV (use_BTV=True) has no edge-weighted form")
+        return beta
 
     def label_options(self, image_shape, has_gt, band_widths=None, band_ignore_label=255, confusion_labels=None,
                       th_factors=None, guide=None, coverages=None, keep_uncertainty=False, min_region=None, segments=None):

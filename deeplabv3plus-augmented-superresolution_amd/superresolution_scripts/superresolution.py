@@ -12,6 +12,10 @@ kernels); ``copy_dropout`` drops a fixed random subset of the copies from the da
 reference draws the mask with np.random.shuffle inside a @tf.function (superresolution.py:44-53),
 i.e. ONCE, when the function is traced on the first solve of a Superresolution object, and every
 later iteration and image reuses it -- ``_drop_mask`` restates exactly that.
+
+``tv_guide`` (not in the reference) puts the RGB image into the prior: the solves and ``loss_function`` take an image at
+``output_size`` and weight every edge of the TV prior by 1 / (1 + tv_beta * |forward difference of the image|^2), so a jump
+of the solution is cheap across an image edge and costs full price elsewhere (include/asr_hip.h: the rule).
 """
 from __future__ import annotations
 
@@ -71,7 +75,8 @@ COVER_MODES = ("frame", "validity")
 class Superresolution:
     def __init__(self, lambda_df, lambda_tv, lambda_L2, lambda_L1, num_iter=200, num_aug=100,
                  optimizer: Optimizer = None, feature_size=(64, 64), output_size=(512, 512), use_BTV=False,
-                 verbose=False, copy_dropout=0.0, trim=0.1, cover="frame", cov_min=0.5, valid_min=0.5):
+                 verbose=False, copy_dropout=0.0, trim=0.1, cover="frame", cov_min=0.5, valid_min=0.5, tv_beta=100.0):
+        self.tv_beta = ops.check_tv_beta(tv_beta, "Superresolution: tv_beta")
         if not 0.0 <= float(trim) < 0.5:
             raise ValueError(f"trim must be in [0, 0.5), got {trim}")
         if cover not in COVER_MODES:
@@ -133,6 +138,33 @@ class Superresolution:
             return ops.sr_config(use_btv=self.use_BTV)
         return self.optimizer.optimizer.config(use_btv=self.use_BTV)
 
+    def _check_tv_guide(self, tv_guide):
+        """Host checks of a tv_guide argument, before anything touches the device: None, an RGB image [H,W,3] or a batch
+        [B,H,W,3] at output_size (host array or device tensor), or a pair (wy, wx) of edge weights already on the device
+        (ops.tv_edge_weights' output, [H,W] shared or [B,H,W]; ops checks their shape against the solve's)."""
+        if tv_guide is None:
+            return
+        if self.use_BTV:
+            raise ValueError("tv_guide: bilateral TV (use_BTV=True) has no edge-weighted form")
+        if isinstance(tv_guide, (tuple, list)) and len(tv_guide) == 2 and all(isinstance(t, torch.Tensor) for t in tv_guide):
+            return
+        shape = tuple(tv_guide.shape) if hasattr(tv_guide, "shape") else tuple(np.shape(tv_guide))
+        if len(shape) not in (3, 4) or shape[-1] != 3 or shape[-3:-1] != self.output_size:
+            raise ValueError(f"tv_guide must be an RGB image [H,W,3] or [B,H,W,3] at output_size {self.output_size}, got "
+                             f"{shape}")
+
+    def _tv_weights(self, tv_guide, batch, dev):
+        """tv_guide (checked) -> None or the (wy, wx) of ops.sr_solve / sr_backward / sr_loss_terms for `batch` images."""
+        if tv_guide is None:
+            return None
+        if isinstance(tv_guide, (tuple, list)):
+            return tuple(tv_guide)
+        g = tv_guide if isinstance(tv_guide, torch.Tensor) else torch.as_tensor(np.asarray(tv_guide, dtype=np.float32))
+        g = g.to(device=dev, dtype=torch.float32).contiguous()
+        if g.dim() == 4 and g.shape[0] != batch:
+            raise ValueError(f"tv_guide holds {g.shape[0]} images, the solve {batch}")
+        return ops.tv_edge_weights(g, self.tv_beta)
+
     @staticmethod
     def _batchify(angles, shifts):
         a = np.asarray(angles, dtype=np.float32)
@@ -140,7 +172,8 @@ class Superresolution:
         return (a[None], s[None]) if a.ndim == 1 else (a, s)
 
     # -- superresolution.py:44-100 ------------------------------------------------------------------
-    def loss_function(self, target_image, augmented_samples, angles, shifts, n_drop=0):
+    def loss_function(self, target_image, augmented_samples, angles, shifts, n_drop=0, tv_guide=None):
+        self._check_tv_guide(tv_guide)
         dev = _lib.require_gpu()
         y = _stack_copies(augmented_samples, dev)[None]
         a, s = self._batchify(angles, shifts)
@@ -151,7 +184,8 @@ class Superresolution:
                                        dtype=np.float32)).to(dev).reshape(1, *self.output_size).contiguous()
         rot, tr = self._transforms(a, s, dev)
         resid = ops.sr_forward_residual(x, y, rot, tr)
-        return self._loss_from_terms(ops.sr_loss_terms(x, resid, self._config()).cpu().numpy()[0])
+        tvw = self._tv_weights(tv_guide, 1, dev)
+        return self._loss_from_terms(ops.sr_loss_terms(x, resid, self._config(), tv_weights=tvw).cpu().numpy()[0])
 
     def _loss_from_terms(self, t):
         f = np.float32
@@ -162,18 +196,22 @@ class Superresolution:
         return float(loss)
 
     # -- superresolution.py:102-137 -------------------------------------------------------------------
-    def augmented_superresolution_batch(self, copies, angles, shifts):
+    def augmented_superresolution_batch(self, copies, angles, shifts, tv_guide=None):
         """copies [B,N,h,w] device tensor, angles [B,N], shifts [B,N,2] -> (device [B,H,W], [B] losses).
         The global Adam step counter advances image by image (reference order), the device then
-        iterates all images together."""
+        iterates all images together.  tv_guide: one RGB image [H,W,3] shared by the batch or [B,H,W,3] (_check_tv_guide)."""
+        self._check_tv_guide(tv_guide)
         return self._solve_batch(copies, angles, shifts,
-                                 lambda b: np.stack([self.optimizer.schedule_alphas(self.num_iter) for _ in range(b)], axis=1))
+                                 lambda b: np.stack([self.optimizer.schedule_alphas(self.num_iter) for _ in range(b)], axis=1),
+                                 tv_guide)
 
-    def augmented_superresolution_classes(self, copies, angles, shifts, start_steps):
+    def augmented_superresolution_classes(self, copies, angles, shifts, start_steps, tv_guide=None):
         """The copies of K classes of ONE image in one batched solve: copies [K,N,h,w] device tensor, angles [N], shifts [N,2]
         (the image's transforms, repeated for every class), start_steps [K] -> (device [K,H,W], [K] losses).  Class k's
         step scalars are those of a solve that starts at the global step counter start_steps[k]; the counter itself is left
-        as it was (the caller decides what the classes' solves count as).  copy_dropout uses the object's frozen mask."""
+        as it was (the caller decides what the classes' solves count as).  copy_dropout uses the object's frozen mask.
+        tv_guide: the image's RGB [H,W,3], or its edge weights (wy, wx) [H,W], shared by the K classes."""
+        self._check_tv_guide(tv_guide)
         if self.optimizer is None:
             raise Exception("You must provide an instance of the Optimizer class to compute the augmented SR")
         k = copies.shape[0]
@@ -191,9 +229,9 @@ class Superresolution:
             state.iterations = saved
         a = np.repeat(np.asarray(angles, dtype=np.float32)[None], k, axis=0)
         s = np.repeat(np.asarray(shifts, dtype=np.float32)[None], k, axis=0)
-        return self._solve_batch(copies, a, s, lambda b: np.stack(columns, axis=1).reshape(self.num_iter, b))
+        return self._solve_batch(copies, a, s, lambda b: np.stack(columns, axis=1).reshape(self.num_iter, b), tv_guide)
 
-    def _solve_batch(self, copies, angles, shifts, make_alphas):
+    def _solve_batch(self, copies, angles, shifts, make_alphas, tv_guide=None):
         """The batched solve; make_alphas(B) -> float32 [num_iter, B] step scalars."""
         if self.optimizer is None:
             raise Exception("You must provide an instance of the Optimizer class to compute the augmented SR")
@@ -217,6 +255,8 @@ class Superresolution:
         state = self.optimizer.optimizer
         alphas_dev = ops.to_device(alphas, device=dev)
         kw = dict(want_loss=True, cfg=state.config(use_btv=self.use_BTV), slot_init=state.slot_init)
+        if tv_guide is not None:
+            kw["tv_weights"] = self._tv_weights(tv_guide, b, dev)
         if not self.verbose:
             return ops.sr_solve(x, copies, rot, tr, irot, itr, alphas_dev, self._lambdas, **kw)
         # superresolution.py:130-131 prints the loss of iteration i (evaluated before that iteration's update) for
@@ -233,14 +273,15 @@ class Superresolution:
                     print(f"{tag}{i + 1}/{self.num_iter} -- loss = {self._loss_from_terms(t)}")
         return x, terms
 
-    def augmented_superresolution(self, augmented_copies, angles, shifts):
+    def augmented_superresolution(self, augmented_copies, angles, shifts, tv_guide=None):
+        self._check_tv_guide(tv_guide)
         if self.optimizer is None:
             raise Exception(
                 "You must provide an instance of the Optimizer class to compute the augmented SR")
         dev = _lib.require_gpu()
         y = _stack_copies(augmented_copies, dev)[None]
         a, s = self._batchify(angles, shifts)
-        x, terms = self.augmented_superresolution_batch(y, a, s)
+        x, terms = self.augmented_superresolution_batch(y, a, s, tv_guide=tv_guide)
         loss = self._loss_from_terms(terms.cpu().numpy()[0]) if isinstance(terms, torch.Tensor) else None
         return x[0].cpu().numpy()[..., None], loss
 

@@ -177,6 +177,50 @@ int asr_sr_solve_cfg_f32(float* x, const float* y, const float* rot_tf, const fl
                          int h, int w, float lambda_df, float lambda_tv, float lambda_l2, float lambda_l1,
                          const asr_sr_config* cfg, asr_stream_t stream);
 
+/* --- edge-weighted (image-guided) TV ---------------------------------------------------------------------------
+ * The TV prior charges every unit of boundary the same; the weighted form makes a jump of the solution cheap across an
+ * edge of the RGB image and full price elsewhere (the guided depth / label super-resolution prior).  The rule:
+ *
+ *   Edge weights.  guide I [batch, H, W, 3] float32 (the project's images, in [0, 1]; values are not checked), beta finite, >= 0.
+ *     Y < H-1:  a_c = I[Y+1,X,c] - I[Y,X,c];  d = (a_0*a_0 + a_1*a_1) + a_2*a_2  in float32, in that order, no contraction;
+ *               wy[Y,X] = 1.0f / (1.0f + beta*d), one IEEE division.      wy[H-1,X] = 1.0f.
+ *     wx the same with X+1;  wx[Y,W-1] = 1.0f.  beta = 0 or a constant guide: every weight is exactly 1.
+ *   Prior.  TV_w(x) = sum wy*|x[Y+1,X] - x[Y,X]| + wx*|x[Y,X+1] - x[Y,X]|; the gradient is the TV prior's statements with
+ *     each lambda_tv replaced by (lambda_tv * w) of the edge it belongs to:
+ *       sy   = (Y < H-1) ? sgn(x[Y+1,X] - xc) * (lambda_tv * wy[Y,X]) : 0
+ *       sx   = (X < W-1) ? sgn(x[Y,X+1] - xc) * (lambda_tv * wx[Y,X]) : 0
+ *       g_tv = -sy - sx
+ *       if (Y > 0) g_tv += sgn(xc - x[Y-1,X]) * (lambda_tv * wy[Y-1,X])
+ *       if (X > 0) g_tv += sgn(xc - x[Y,X-1]) * (lambda_tv * wx[Y,X-1])
+ *     L2, L1 and every optimiser follow unchanged.  terms[b][1] accumulates (double)(wy*fabsf(dy) + wx*fabsf(dx)): product
+ *     and sum in float32, the accumulation in float64 as for TV.
+ *   The *_wtv entry points take ANY finite weights >= 0 (not only asr_tv_edge_weights_f32's): wy, wx [H, W] shared by the
+ *   whole batch (w_shared != 0: the K classes of one image) or [batch, H, W].  Hence, bit for bit: weights of all ones are
+ *   the TV prior (lambda_tv * 1.0f is lambda_tv), weights of all zeros are lambda_tv = 0, shared planes are the same planes
+ *   broadcast.  Refusals, before any launch: every refusal of the *_cfg twin; null wy / wx -> ASR_ERR_INVALID_ARG;
+ *   cfg->prior == ASR_PRIOR_BTV -> ASR_ERR_UNSUPPORTED (bilateral TV has no weighted form here). */
+int asr_tv_edge_weights_f32(const float* guide, float* wy, float* wx, int batch, int H, int W, float beta,
+                            asr_stream_t stream);
+
+/* asr_sr_backward_cfg_f32 with the edge-weighted TV prior. */
+int asr_sr_backward_wtv_f32(const float* x, float* x_new, const float* resid, const float* inv_rot_tf,
+                            const float* inv_trans_tf, float* m, float* v, float* vhat, const float* alphas,
+                            float* grad_out, int batch, int n, int H, int W, int h, int w, float lambda_df,
+                            float lambda_tv, float lambda_l2, float lambda_l1, const asr_sr_config* cfg, const float* wy,
+                            const float* wx, int w_shared, asr_stream_t stream);
+
+/* asr_sr_loss_terms_cfg_f64 with terms[b][1] = TV_w(x). */
+int asr_sr_loss_terms_wtv_f64(const float* x, const float* resid, double* terms, int batch, int n, int H, int W,
+                              int h, int w, const asr_sr_config* cfg, const float* wy, const float* wx, int w_shared,
+                              asr_stream_t stream);
+
+/* asr_sr_solve_cfg_f32 with the edge-weighted TV prior; the workspace is that of asr_sr_solve_workspace_bytes_cfg. */
+int asr_sr_solve_wtv_f32(float* x, const float* y, const float* rot_tf, const float* trans_tf, const float* inv_rot_tf,
+                         const float* inv_trans_tf, float* m, float* v, float* vhat, const float* alphas, int num_iter,
+                         double* last_loss_terms, void* workspace, size_t workspace_bytes, int batch, int n, int H, int W,
+                         int h, int w, float lambda_df, float lambda_tv, float lambda_l2, float lambda_l1,
+                         const asr_sr_config* cfg, const float* wy, const float* wx, int w_shared, asr_stream_t stream);
+
 /* out[b] = max / mean over copies of rotate(translate(resize(y[b,i], (H,W)), trans_tf), rot_tf)
  * -- max_superresolution / mean_superresolution, superresolution.py:139-161 (trans_tf built
  * from -shifts, rot_tf from -angles).  out [batch,H,W]; (H, W) need not be a multiple of (h, w).  The maximum runs

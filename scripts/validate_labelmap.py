@@ -32,6 +32,12 @@ window radius R in 0..32, regulariser E, default 1e-3) against its own image bef
 boundaries onto the image's edges; compare the --band_widths curve with and without it.  Off when omitted: every CSV keeps its
 columns either way.
 
+--tv_guide_beta B: the image goes INTO the iterative solve instead -- the TV prior of every "aug" solve is weighted by the image's
+own edges (include/asr_hip.h, "edge-weighted TV": w = 1 / (1 + B * |forward difference of the image|^2), B finite and >= 0; 100
+is a good start for images in [0, 1]), so a boundary is cheap where the image has an edge and costs full price elsewhere.
+Independent of --guide_radius and combinable with it; compare the --band_widths curve with and without it.  Off when omitted:
+nothing else is launched and every CSV is what it was.
+
 --coverages 50,60,70,80,90,100 [--coverage_out FILE] [--uncertainty_dir DIR]: the risk-coverage curve as well -- the variance of
 the class stacks over the realigned copies (include/asr_hip.h at asr_realign_moments_f32; utils.uncertainty_map) says where the
 copies disagreed, and every label map is scored on each image's p % most certain non-void pixels (asr_binned_class_counts_f32),
@@ -97,6 +103,8 @@ parser.add_argument("--th_sweep_out", default=None, help="CSV file for the thres
 parser.add_argument("--guide_radius", type=int, default=None,
                     help="refine the SR score maps with the guided filter of this window radius (0..32) against the image")
 parser.add_argument("--guide_eps", type=float, default=None, help="the guided filter's regulariser (default 1e-3)")
+parser.add_argument("--tv_guide_beta", type=float, default=None,
+                    help="weight the solver's TV prior by the image's edges with this beta (finite, >= 0; e.g. 100)")
 parser.add_argument("--coverages", default=None,
                     help="comma-separated whole percentages (1..100, at most 16), e.g. 50,60,70,80,90,100: the risk-coverage curve too")
 parser.add_argument("--coverage_out", default=None, help="CSV file for the risk-coverage curve (default: <--out stem>_coverage.csv)")
@@ -120,7 +128,7 @@ def main():
                                     write_confusion_csv, write_confusion_metrics_csv, write_labelmap_csv,
                                     write_coverage_csv, write_labelmap_threshold_csv, write_regions_csv, write_segments_csv,
                                     write_trimap_csv)
-    from asr_amd.ops import check_coverages, check_min_region, check_segments
+    from asr_amd.ops import check_coverages, check_min_region, check_segments, check_tv_beta
     from asr_amd.model import DeeplabV3Plus
     from asr_amd.pipeline import HotPath
     from asr_amd.superresolution_scripts.optimizer import Optimizer
@@ -176,6 +184,11 @@ def main():
         guide = (args.guide_radius, 1e-3 if args.guide_eps is None else args.guide_eps)
         if not 0.0 < guide[1] < float("inf"):
             parser.error("--guide_eps must be finite and > 0")
+    if args.tv_guide_beta is not None:
+        try:
+            check_tv_beta(args.tv_guide_beta, "--tv_guide_beta")
+        except ValueError as e:
+            parser.error(str(e))
     if (args.coverage_out or args.uncertainty_dir) and not args.coverages:
         parser.error("--coverage_out and --uncertainty_dir need --coverages")
     covs = None
@@ -212,6 +225,7 @@ def main():
                              confusion_labels=args.confusion_labels if args.confusion_out else None,
                              **(dict(th_factors=factors) if factors is not None else {}),
                              **(dict(guide=guide) if guide is not None else {}),
+                             **(dict(tv_guide=args.tv_guide_beta) if args.tv_guide_beta is not None else {}),
                              **(dict(coverages=covs, uncertainty_dir=args.uncertainty_dir) if covs is not None else {}),
                              **(dict(min_region=min_region) if min_region is not None else {}),
                              **(dict(segments=segments) if segments is not None else {}))
