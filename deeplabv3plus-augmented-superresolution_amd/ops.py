@@ -601,8 +601,11 @@ def standard_mask(logits0, out_hw, class_id, out=None):
     """logits0 [h,w,C] of the un-augmented image -> int32 mask [H,W] in {0, class_id}: bilinear upsample + argmax + class
     filter in one kernel (generate_standard_output.py:52-65)."""
     h, w, c = logits0.shape
+    out_hw = (int(out_hw[0]), int(out_hw[1]))
     if out is None:
-        out = torch.empty(tuple(out_hw), dtype=torch.int32, device=logits0.device)
+        out = torch.empty(out_hw, dtype=torch.int32, device=logits0.device)
+    elif tuple(out.shape) != out_hw:
+        raise AsrError(f"standard_mask: out must be {out_hw}, got {tuple(out.shape)}")
     call("asr_standard_mask_i32", ptr(logits0), ptr(out, torch.int32), h, w, c, int(out_hw[0]), int(out_hw[1]), int(class_id),
          stream_ptr())
     return out
@@ -664,11 +667,16 @@ def opm_slice(logits, class_id, new_min=0.0, new_max=1.0, out=None):
 
 
 def threshold(image, th_value, th_factor=0.15, th_mask=None, segments=1, out=None):
-    per = image.numel() // segments
+    per = image.numel() // segments if segments > 0 else 0
+    if per * segments != image.numel() or per == 0:
+        raise AsrError("threshold: image does not split into equal non-empty segments")
     if out is None:
         out = torch.empty(image.shape, dtype=torch.int32, device=image.device)
     elif out.numel() != image.numel():
         raise AsrError("threshold: out size mismatch")
+    elif out.dtype != torch.int32 or not out.is_contiguous():
+        raise AsrError(f"threshold: out must be a contiguous int32 tensor, got {out.dtype}"
+                       f"{'' if out.is_contiguous() else ' (not contiguous)'}")
     ws = torch.empty((segments, 2), dtype=f32, device=image.device)
     if th_mask is not None and th_mask.shape != image.shape:
         raise AsrError("threshold: th_mask shape mismatch")
@@ -692,7 +700,9 @@ def iou_counts_shared_truth(truth, preds, class_id, include_bg=False):
 def iou_counts(truth, pred, class_id, include_bg=False, segments=1):
     if truth.numel() != pred.numel():
         raise AsrError("iou_counts: size mismatch")
-    per = truth.numel() // segments
+    per = truth.numel() // segments if segments > 0 else 0
+    if per * segments != truth.numel() or per == 0:
+        raise AsrError("iou_counts: truth / pred do not split into equal non-empty segments")
     counts = torch.empty((segments, 4), dtype=torch.int64, device=truth.device)
     call("asr_iou_counts_i32", ptr(truth, torch.int32), ptr(pred, torch.int32), ptr(counts, torch.int64), per, segments,
          int(class_id), int(bool(include_bg)), stream_ptr())

@@ -4,11 +4,17 @@ kernels, so for them this checks plane placement and that a class's result does 
 independent pin of the K = 1 bytes is tests/golden/reduce_single_class_digests.json (test_gpu_reduce_digests.py).  Logits are built so that every class of the set really decides pixels: it is the
 argmax of at least 1 % of them and ties for the maximum on some, with +-0.0 entries and magnitudes up to 1e4, on pixel
 counts that are not a multiple of 256."""
+import os
+import sys
+
 import numpy as np
 import pytest
 import torch
 
 from oracle import augment as o_aug
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))      # tests/base_kernel_cases.py, whatever pytest's import mode
+from base_kernel_cases import first_argmax as _first_argmax, make_logits  # noqa: E402,F401  (make_logits: also imported from here)
 
 pytestmark = pytest.mark.gpu
 
@@ -19,51 +25,6 @@ def _sets(classes):
     rng = np.random.default_rng(classes)
     rest = [int(c) for c in rng.permutation(np.arange(1, classes))[:20]]
     return {1: [0], 3: [0, classes // 2 - 3, classes - 1], 21: [int(c) for c in rng.permutation([0] + rest)]}
-
-
-def _first_argmax(x):
-    return np.argmax(x, axis=-1)             # numpy: first maximum, like tf.argmax and the kernels
-
-
-def make_logits(classes, ids, seed, shape=SHAPE):
-    """Seeded [copies, h, w, classes] logits in which every id of `ids` wins >= 1 % of the pixels and ties for the maximum
-    on some; rows of +-0.0 maxima and rows scaled to ~1e4."""
-    rng = np.random.default_rng(seed)
-    n = int(np.prod(shape))
-    x = rng.standard_normal((n, classes)).astype(np.float32)
-    big = rng.random(n) < 0.2
-    x[big] *= np.float32(1e4)
-    order = rng.permutation(n)
-    per = max(n // 60, 1)                    # 1.7 % of the pixels per id: strict wins
-    cur = 0
-    for c in ids:
-        rows = order[cur:cur + per]
-        cur += per
-        x[rows, c] = np.abs(x[rows]).max(axis=1) + np.float32(1.0)
-    for c in ids:                            # exact ties for the maximum: with the next class, and with the previous one
-        for other in ((c + 1) % classes, (c - 1) % classes):
-            rows = order[cur:cur + 3]
-            cur += 3
-            m = np.abs(x[rows]).max(axis=1) + np.float32(2.0)
-            x[rows, c] = m
-            x[rows, other] = m
-    for c in ids:                            # +-0.0: the maximum is a zero of either sign
-        rows = order[cur:cur + 2]
-        cur += 2
-        x[rows] = -np.abs(x[rows]) - np.float32(1.0)
-        x[rows, c] = np.float32(-0.0)
-        x[rows, (c + 3) % classes] = np.float32(0.0)
-    assert cur < n
-    # the non-vacuity condition, checked on the host
-    arg = _first_argmax(x)
-    rowmax = x.max(axis=1)
-    for c in ids:
-        assert (arg == c).mean() >= 0.01, c
-        at_max = x == rowmax[:, None]
-        assert (at_max[:, c] & (at_max.sum(axis=1) >= 2)).any(), c
-    assert (x == 0).any() and np.signbit(x[x == 0]).any() and (~np.signbit(x[x == 0])).any()
-    assert np.abs(x).max() > 1e4
-    return x.reshape(tuple(shape) + (classes,))
 
 
 def _bits(t):
