@@ -53,7 +53,15 @@ class SrConfig(C.Structure):
                 ("prior", C.c_int), ("btv_alpha", C.c_float), ("btv_shift", C.c_int), ("plane_chunk", C.c_int)]
 
 
+class CrfConfig(C.Structure):
+    """struct asr_crf_config (include/asr_hip.h): window, iterations and kernels of asr_crf_refine_f32."""
+    _fields_ = [("radius", C.c_int), ("dilation", C.c_int), ("iterations", C.c_int), ("w_app", C.c_float),
+                ("w_smooth", C.c_float), ("theta_pos", C.c_float), ("theta_rgb", C.c_float), ("theta_smooth", C.c_float)]
+
+
+MAX_CRF_RADIUS, MAX_CRF_HALO, MAX_CRF_ITERATIONS, MAX_CRF_LABELS = 7, 16, 32, 32     # asr_crf_refine_f32's caps
 _cfg = C.POINTER(SrConfig)
+_crf = C.POINTER(CrfConfig)
 ABI_VERSION = 3          # ASR_ABI_VERSION of include/asr_hip.h this table mirrors
 
 # name -> (restype, argtypes).  Order and types mirror include/asr_hip.h exactly.
@@ -121,6 +129,10 @@ SIGNATURES = {
     "asr_clean_labels_i32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _vp]),
     "asr_segment_match_workspace_bytes": (_sz, [_i, _i, _i]),
     "asr_segment_match_i32": (_i, [_vp] * 9 + [_sz, _i, _i, _i, _i, _i, _vp]),
+    "asr_crf_workspace_bytes": (_sz, [_i, _i, _i]),
+    "asr_crf_unaries_scores_f32": (_i, [_vp, _vp, _vp, _i64, _i, _fl, _fl, _vp]),
+    "asr_crf_unaries_labels_f32": (_i, [_vp, _vp, _i64, _ip, _i, _fl, _vp]),
+    "asr_crf_refine_f32": (_i, [_vp, _vp, _ip, _i, _i, _i, _crf, _vp, _vp, _vp, _vp]),
     "asr_pwconv_packed_floats": (_sz, [_i, _i]),
     "asr_pwconv_pack_weights_f32": (_i, [_vp, _vp, _i, _i, _vp]),
     "asr_pwconv_mfma_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),

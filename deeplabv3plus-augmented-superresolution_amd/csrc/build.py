@@ -53,6 +53,7 @@ LATER_SOURCES = [
     ("guided.hip", ["-ffp-contract=off"] + NO_PK_F32),  # the guided filter's sums and its 3x3 solve round term by term, like its f32 restatement
     ("regions.hip", NO_PK_F32),                         # connected regions of label maps: integer only
     ("segments.hip", NO_PK_F32),                        # region-by-region scores of label maps: integer only
+    ("crf.hip", ["-ffp-contract=off"] + NO_PK_F32),     # the windowed CRF's sums round term by term, like its f32 restatement
 ]
 ALL_SOURCES = SOURCES + LATER_SOURCES
 # Units that keep packed-f32 arithmetic although the compiler emits the erratum form in them: compiled to device assembly, ONLY the

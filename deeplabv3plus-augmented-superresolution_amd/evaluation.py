@@ -286,7 +286,8 @@ def dataset_miou(counts):
 def evaluate_labelmaps(path, image_paths, gt_paths, class_ids=tuple(range(1, 21)), num_aug=100, angle_max=0.3, shift_max=30,
                        img_size=(512, 512), rank=0, world=1, seed=1234, sr_types=("aug", "max", "mean"), prune=True,
                        save_dir=None, band_widths=None, band_ignore_label=255, confusion_labels=None, th_factors=None,
-                       guide=None, tv_guide=None, min_region=None, segments=None, coverages=None, uncertainty_dir=None):
+                       guide=None, tv_guide=None, crf=None, min_region=None, segments=None, coverages=None,
+                       uncertainty_dir=None):
     """One fused label map per image and SR type (HotPath.run_image_labels) and its score.  Returns on every rank a
     LabelmapScores, the tuple (rows, counts) plus what the options below append, every entry also an attribute by the name
     given here: rows [images, 4] per-image Mean_IOU in LABELMAP_KEYS order (the reference's per-image-then-mean convention;
@@ -321,6 +322,10 @@ def evaluate_labelmaps(path, image_paths, gt_paths, class_ids=tuple(range(1, 21)
     (run_image_labels' tv_guide; img_size must be the SR output size, no bilateral TV).  Independent of guide.  The return
     value keeps its form.
 
+    crf (a dict of the windowed CRF's fields plus tau and standard_conf): every SR label map is decided by the windowed CRF over
+    classes and image instead of the fusion (run_image_labels' crf; img_size must be the SR output size; not in slice_max mode
+    and not together with th_factors).  The return value keeps its form.
+
     coverages (C whole percentages in [1, 100], 1..16): the same loop also collects each label map's counts over its p % most
     certain pixels (run_image_labels' coverages: the variance of the class stacks over the copies, no further forward pass
     or solve) and the return value ends in two more entries, after the sweep's: cov_rows [images, 4, C] per-image Mean_IOU
@@ -347,6 +352,10 @@ def evaluate_labelmaps(path, image_paths, gt_paths, class_ids=tuple(range(1, 21)
                               guide, coverages, bool(uncertainty_dir), min_region, segments)
     tv_beta = path.check_tv_guide(tv_guide, tuple(img_size) + (3,))
     tv_kw = {} if tv_beta is None else {"tv_guide": tv_beta}
+    if crf is not None:
+        class_ids = list(class_ids)
+        path.check_crf(crf, tuple(img_size) + (3,), th_factors, len(class_ids))
+        tv_kw["crf"] = dict(crf)
     if uncertainty_dir:
         os.makedirs(uncertainty_dir, exist_ok=True)
     class_ids, params, mine = _class_set_run(class_ids, image_paths, gt_paths, rank, world, num_aug=num_aug,

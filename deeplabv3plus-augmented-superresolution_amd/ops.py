@@ -7,6 +7,7 @@ returns device tensors.  Nothing here computes on the CPU.
 from __future__ import annotations
 
 import ctypes as C
+from collections import namedtuple
 
 import numpy as np
 import torch
@@ -955,6 +956,122 @@ def guided_apply(state, guide, p, out=None):
 def guided_filter(guide, p, radius=8, eps=1e-3, out=None):
     """guided_apply(guided_prepare(guide, radius, eps), guide, p, out): one-shot use."""
     return guided_apply(guided_prepare(guide, radius, eps), guide, p, out=out)
+
+
+# ---------------------------------------------------------------------------------------------
+# windowed CRF: label maps decided jointly over classes and image (asr_crf_unaries_* / asr_crf_refine_f32)
+# ---------------------------------------------------------------------------------------------
+MAX_CRF_LABELS = _lib.MAX_CRF_LABELS
+CrfParams = namedtuple("CrfParams", "radius dilation iterations w_app w_smooth theta_pos theta_rgb theta_smooth")
+CRF_DEFAULTS = CrfParams(radius=3, dilation=1, iterations=5, w_app=4.0, w_smooth=1.0, theta_pos=2.0, theta_rgb=0.1,
+                         theta_smooth=1.0)
+
+
+def _crf_int(v, name):
+    whole = isinstance(v, (int, np.integer)) or (isinstance(v, (float, np.floating)) and np.isfinite(v) and v == int(v))
+    if isinstance(v, (bool, np.bool_, str, bytes)) or not whole:
+        raise ValueError(f"crf: {name} must be an integer, got {v!r}")
+    return int(v)
+
+
+def check_crf(params):
+    """The config of the windowed CRF (include/asr_hip.h) as a CrfParams: a dict of any of its fields, or None, over
+    CRF_DEFAULTS; floats rounded to float32.  ValueError with the wording of asr_crf_refine_f32's own checks for an unknown
+    field, a bad value or a value beyond a cap."""
+    params = {} if params is None else dict(params)
+    unknown = sorted(set(params) - set(CrfParams._fields))
+    if unknown:
+        raise ValueError(f"crf: unknown field(s) {unknown} (the fields are {list(CrfParams._fields)})")
+    p = CRF_DEFAULTS._replace(**params)
+    r, d, t = (_crf_int(getattr(p, f), f) for f in ("radius", "dilation", "iterations"))
+    if r < 1:
+        raise ValueError(f"crf: radius {r} below 1")
+    if d < 1:
+        raise ValueError(f"crf: dilation {d} below 1")
+    if t < 0:
+        raise ValueError(f"crf: {t} iterations")
+    fl = {}
+    for f in ("w_app", "w_smooth"):
+        fl[f] = float(np.float32(getattr(p, f)))
+        if not (np.isfinite(fl[f]) and fl[f] >= 0.0):
+            raise ValueError(f"crf: {f} must be finite and >= 0 (got {fl[f]!r})")
+    for f in ("theta_pos", "theta_rgb", "theta_smooth"):
+        fl[f] = float(np.float32(getattr(p, f)))
+        if not (np.isfinite(fl[f]) and fl[f] > 0.0):
+            raise ValueError(f"crf: {f} must be finite and > 0 (got {fl[f]!r})")
+    if r > _lib.MAX_CRF_RADIUS:
+        raise ValueError(f"crf: radius {r} above the cap of {_lib.MAX_CRF_RADIUS}")
+    if r * d > _lib.MAX_CRF_HALO:
+        raise ValueError(f"crf: radius {r} x dilation {d} above the cap of {_lib.MAX_CRF_HALO}")
+    if t > _lib.MAX_CRF_ITERATIONS:
+        raise ValueError(f"crf: {t} iterations above the cap of {_lib.MAX_CRF_ITERATIONS}")
+    return CrfParams(r, d, t, **fl)
+
+
+def check_crf_tau(tau):
+    """tau of crf_unaries as a float32-rounded float: finite and > 0."""
+    tau = float(np.float32(tau))
+    if not (np.isfinite(tau) and tau > 0.0):
+        raise ValueError(f"crf: tau must be finite and > 0 (got {tau!r})")
+    return tau
+
+
+def check_crf_conf(conf, num_labels):
+    """conf of crf_unaries_from_labels as a float32-rounded float: inside (1 / num_labels, 1), compared in float32 as the
+    library compares it."""
+    conf = float(np.float32(conf))
+    if not np.float32(1) / np.float32(num_labels) < np.float32(conf) < np.float32(1):
+        raise ValueError(f"crf: conf must lie in (1/{num_labels}, 1) (got {conf!r})")
+    return conf
+
+
+def crf_unaries(scores, th_factor, tau=0.1):
+    """scores [K, H, W] float32 (plane k: the SR output of class k, what fuse_labels reads) -> unaries z [K + 1, H, W]:
+    z[0] = 0, z[k + 1] = (scores[k] - th_factor * max(scores[k])) / tau (asr_crf_unaries_scores_f32): the margin by which
+    class k passes fuse_labels' threshold, in units of tau."""
+    if not isinstance(scores, torch.Tensor) or scores.dim() < 2 or not 1 <= scores.shape[0] <= _lib.MAX_CRF_LABELS - 1:
+        shape = tuple(scores.shape) if isinstance(scores, torch.Tensor) else type(scores)
+        raise ValueError(f"crf_unaries: scores must be [K, ...] with K in 1..{_lib.MAX_CRF_LABELS - 1}, got {shape}")
+    tau = check_crf_tau(tau)
+    k = int(scores.shape[0])
+    z = torch.empty((k + 1,) + tuple(scores.shape[1:]), dtype=f32, device=scores.device)
+    ws = torch.empty((k, 2), dtype=f32, device=scores.device)
+    call("asr_crf_unaries_scores_f32", ptr(scores), ptr(ws), ptr(z), scores.numel() // k, k, float(np.float32(th_factor)), tau,
+         stream_ptr())
+    return z
+
+
+def crf_unaries_from_labels(labels, ids, conf):
+    """labels int32 [H, W], ids: the K class ids -> unaries z [K + 1, H, W]: log(conf) for the label the map holds (0: label 0),
+    log((1 - conf) / K) for the others, all 0 where the map holds none of them (asr_crf_unaries_labels_f32)."""
+    cids, k = class_set(ids)
+    conf = check_crf_conf(conf, k + 1)
+    z = torch.empty((k + 1,) + tuple(labels.shape), dtype=f32, device=labels.device)
+    call("asr_crf_unaries_labels_f32", ptr(labels, torch.int32), ptr(z), labels.numel(), cids, k + 1, conf, stream_ptr())
+    return z
+
+
+def crf_refine(guide, z, ids, params=None, out=None, want_q=False):
+    """The windowed CRF of include/asr_hip.h: guide [H, W, 3] float32, unaries z [L, H, W] float32, ids: the L - 1 class ids of
+    labels 1 .. L-1, params: check_crf's argument -> the int32 label map [H, W] (into out when given), or with want_q
+    (labels, Q [L, H, W]).  Device tensors only.  The workspace (the two Q buffers) comes from torch's caching allocator."""
+    H, W = _check_guide(guide, "crf_refine")
+    p = params if isinstance(params, CrfParams) else check_crf(params)
+    cids, k = class_set(ids)
+    if not isinstance(z, torch.Tensor) or tuple(z.shape) != (k + 1, H, W):
+        shape = tuple(z.shape) if isinstance(z, torch.Tensor) else type(z)
+        raise ValueError(f"crf_refine: z must be [{k + 1}, {H}, {W}] (label 0 and {k} ids), got {shape}")
+    if out is None:
+        out = torch.empty((H, W), dtype=torch.int32, device=z.device)
+    elif tuple(out.shape) != (H, W):
+        raise ValueError(f"crf_refine: out must be {(H, W)}, got {tuple(out.shape)}")
+    q = torch.empty_like(z) if want_q else None
+    lib = _lib.load()
+    ws = torch.empty(lib.asr_crf_workspace_bytes(k + 1, H, W) // 4, dtype=f32, device=z.device)
+    cfg = _lib.CrfConfig(*p)
+    call("asr_crf_refine_f32", ptr(guide), ptr(z), cids, k + 1, H, W, C.byref(cfg), ptr(ws), ptr(out, torch.int32),
+         ptr(q, allow_none=True), stream_ptr())
+    return (out, q) if want_q else out
 
 
 # ---------------------------------------------------------------------------------------------

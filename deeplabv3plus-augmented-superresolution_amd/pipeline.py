@@ -296,7 +296,7 @@ class HotPath:
     def run_image_labels(self, image_dev, angles, shifts, class_ids=range(1, 21), gt_dev=None, adam_starts=None,
                          sr_types=("aug", "max", "mean"), want_standard=True, prune=True, profile=None, keep_scores=False,
                          band_widths=None, band_ignore_label=255, confusion_labels=None, th_factors=None, guide=None,
-                         coverages=None, keep_uncertainty=False, min_region=None, tv_guide=None, segments=None):
+                         coverages=None, keep_uncertainty=False, min_region=None, tv_guide=None, crf=None, segments=None):
         """One label map per SR type from one forward pass: stage 1 and the solves are run_image_classes's; stage 2 ends in the
         fusion kernel (ops.fuse_labels) instead of K thresholds.  class_ids: K <= 32 distinct ids, none 0 (the label of "no
         class").  At each pixel the label is the class whose single-class mask is set there and whose SR output is greatest
@@ -383,9 +383,25 @@ class HotPath:
         cheap where the image has an edge.  One ops.tv_edge_weights call per image inside the timed SR stage; the pair is
         shared by the K classes' solve and, in slice_max, by the max maps' solve.  Independent of guide (which refines the
         scores afterwards).  beta = 0 gives weights of one: every result is tv_guide=None's bit for bit.  With
-        tv_guide=None nothing else is launched and every result is what it was."""
+        tv_guide=None nothing else is launched and every result is what it was.
+
+        crf (a dict of any of the fields of include/asr_hip.h's asr_crf_config -- radius, dilation, iterations, w_app, w_smooth,
+        theta_pos, theta_rgb, theta_smooth; ops.check_crf -- plus tau and standard_conf; image_dev must be [H, W, 3] at the SR
+        output size): the windowed CRF of include/asr_hip.h decides each SR type's label map jointly over the classes and the
+        image instead of ops.fuse_labels: the map is ops.crf_refine of ops.crf_unaries(scores, th_factor, tau) with the image as
+        the guide -- after the guided refinement when guide is on too, inside the timed SR stage -- and its counts are
+        ops.class_counts'.  With iterations = 0 and tau <= 1 the map is the fusion's wherever at most one class passes; where
+        several pass, the margin over the threshold ranks them, not the score.  standard_conf (default None: the standard map is left alone):
+        the standard label map goes through ops.crf_unaries_from_labels(map, class_ids, standard_conf) and ops.crf_refine before
+        it is counted.  Everything downstream sees the CRF maps: the clean-up, the segments, the trimap, the confusion matrix
+        and the risk-coverage counts.  Refused on the host, before the model: slice_max mode (its pass rule S >= Smax is not a
+        threshold, so there is no unary), th_factors (the sweep counts the fusion rule's maps), more than 31 class ids (the CRF has
+        at most 32 labels) and an image of another shape.
+        With no class left after pruning the SR maps are 0 as before.  With crf=None nothing else is launched and every result is
+        what it was."""
         ids = [int(c) for c in class_ids]
         tv_beta = self.check_tv_guide(tv_guide, None if image_dev is None else tuple(image_dev.shape))
+        crf_opts = self.check_crf(crf, None if image_dev is None else tuple(image_dev.shape), th_factors, len(ids))
         opts = self.label_options(None if image_dev is None else tuple(image_dev.shape), gt_dev is not None, band_widths,
                                   band_ignore_label, confusion_labels, th_factors, guide, coverages, keep_uncertainty,
                                   min_region, segments)
@@ -424,11 +440,16 @@ class HotPath:
             tally = (_LabelCounts(label_fields(keys, *opts.sizes, n_segments=opts.segments[0] if opts.segments else 0),
                                   image_dev.device) if gt is not None else None)
             f_dev = ops.to_device(opts.factors, device=image_dev.device) if opts.factors is not None and kept and sr_types else None
+            g_image = None
+            if crf_opts is not None or (opts.guide is not None and kept and sr_types):
+                g_image = image_dev.to(torch.float32).contiguous()
+            if crf_opts is not None and crf_opts.standard_conf is not None and want_standard:
+                ops.crf_refine(g_image, ops.crf_unaries_from_labels(maps[0], ids, crf_opts.standard_conf), ids, crf_opts.params,
+                               out=maps[0])
             if tally is not None and want_standard:
                 tally.counts[0] = ops.class_counts(gt, maps[0])[0]
             g_state = None
             if opts.guide is not None and kept and sr_types:
-                g_image = image_dev.to(torch.float32).contiguous()
                 g_state = ops.guided_prepare(g_image, *opts.guide)
             tv_weights = None
             if tv_beta is not None and kept and "aug" in sr_types:
@@ -441,8 +462,13 @@ class HotPath:
                         ops.guided_apply(g_state, g_image, tgt, out=tgt)
                         if tmax is not None:
                             ops.guided_apply(g_state, g_image, tmax, out=tmax)
-                    _, c = ops.fuse_labels(tgt, solved, th_factor=self.th_factor, max_scores=tmax, truth=gt, out=maps[j],
-                                           classes=classes)
+                    if crf_opts is not None:
+                        ops.crf_refine(g_image, ops.crf_unaries(tgt, self.th_factor, crf_opts.tau), solved, crf_opts.params,
+                                       out=maps[j])
+                        c = ops.class_counts(gt, maps[j])[0] if gt is not None else None
+                    else:
+                        _, c = ops.fuse_labels(tgt, solved, th_factor=self.th_factor, max_scores=tmax, truth=gt, out=maps[j],
+                                               classes=classes)
                     if c is not None:
                         tally.counts[j] = c
                     if f_dev is not None:
@@ -489,6 +515,33 @@ class HotPath:
         if self.sr.use_BTV:
             raise ValueError("tv_guide: bilateral TV (use_BTV=True) has no edge-weighted form")
         return beta
+
+    def check_crf(self, crf, image_shape, th_factors=None, num_ids=None):
+        """run_image_labels' crf, checked on the host before any launch: None, or a CrfOptions (params: ops.CrfParams; tau;
+        standard_conf | None).  ValueError for a bad field (ops.check_crf's wording), slice_max mode, th_factors next to it and an
+        image that is not [H, W, 3] at the SR output size.  num_ids: the number of class ids, for standard_conf's range."""
+        if crf is None:
+            return None
+        if not isinstance(crf, dict):
+            raise ValueError(f"crf must be a dict of the CRF's fields, got {type(crf).__name__}")
+        fields = dict(crf)
+        tau = ops.check_crf_tau(fields.pop("tau", 0.1))
+        conf = fields.pop("standard_conf", None)
+        params = ops.check_crf(fields)
+        if num_ids is not None and num_ids > ops.MAX_CRF_LABELS - 1:
+            raise ValueError(f"crf: {num_ids} class ids above the cap of {ops.MAX_CRF_LABELS - 1} (label 0 and the ids make at most "
+                             f"{ops.MAX_CRF_LABELS} labels)")
+        if conf is not None:
+            conf = ops.check_crf_conf(conf, (num_ids or 1) + 1)
+        if self.mode == "slice_max":
+            raise ValueError("crf in slice_max mode: a class passes against its max map there (S >= Smax), which is not a "
+                             "threshold, so there is no unary")
+        if th_factors is not None:
+            raise ValueError("th_factors with crf: the sweep counts the fusion rule's label maps, not the CRF's")
+        if image_shape != tuple(self.sr.output_size) + (3,):
+            raise ValueError(f"crf needs the image as [H, W, 3] at the SR output size {tuple(self.sr.output_size)}, got "
+                             f"{image_shape}")
+        return CrfOptions(params, tau, conf)
 
     def label_options(self, image_shape, has_gt, band_widths=None, band_ignore_label=255, confusion_labels=None,
                       th_factors=None, guide=None, coverages=None, keep_uncertainty=False, min_region=None, segments=None):
@@ -627,6 +680,8 @@ class HotPath:
 # HotPath.label_options' value: band widths | None and the label left out of the bands (-1: none), confusion labels (0: off),
 # float32 threshold factors | None, the guide's (radius, eps) | None, coverages | None; sizes: (B, L, T, C, R), 0 where off (R: 1
 # with min_region); min_region: (min_area, connectivity) | None; segments: (num_labels, connectivity, include_zero) | None
+# HotPath.check_crf's value: ops.CrfParams, the unaries' tau, the standard map's conf | None (left alone)
+CrfOptions = namedtuple("CrfOptions", "params tau standard_conf")
 LabelOptions = namedtuple("LabelOptions", "bands band_ignore n_conf factors guide covs sizes min_region segments")
 
 

@@ -147,6 +147,30 @@ def guided_refine(image, guide, radius=8, eps=1e-3):
     return out if was_tensor else out.cpu().numpy()
 
 
+def crf_labels(scores, guide, class_ids, th_factor, tau=0.1, **params):
+    """The windowed CRF of include/asr_hip.h on the SR outputs of one image: ``scores`` [K, H, W] float32 (plane k: the SR output
+    of class_ids[k]) and the colour ``guide`` [H, W, 3] (the RGB image at the score maps' size, values in [0, 1]) -> the int32
+    label map [H, W]: ops.crf_refine of ops.crf_unaries(scores, th_factor, tau).  params: the fields of ops.check_crf (radius,
+    dilation, iterations, w_app, w_smooth, theta_pos, theta_rgb, theta_smooth).  Runs on the device; returns a host array for
+    host ``scores``, a device tensor otherwise."""
+    was_tensor = isinstance(scores, torch.Tensor)
+    p = ops.check_crf(params)
+    tau = ops.check_crf_tau(tau)
+    g = guide if isinstance(guide, torch.Tensor) else torch.as_tensor(np.asarray(guide, dtype=np.float32))
+    if g.dim() != 3 or g.shape[2] != 3:
+        raise ValueError(f"crf_labels: the guide must be [H, W, 3], got {tuple(g.shape)}")
+    H, W = int(g.shape[0]), int(g.shape[1])
+    ids = [int(c) for c in class_ids]
+    s = scores if was_tensor else torch.as_tensor(np.asarray(scores, dtype=np.float32))
+    if tuple(s.shape) != (len(ids), H, W):
+        raise ValueError(f"crf_labels: scores must be [{len(ids)}, {H}, {W}], got {tuple(s.shape)}")
+    dev = _lib.require_gpu()
+    g = g.to(device=dev, dtype=torch.float32).contiguous()
+    s = s.to(device=dev, dtype=torch.float32).contiguous()
+    out = ops.crf_refine(g, ops.crf_unaries(s, th_factor, tau), ids, p)
+    return out if was_tensor else out.cpu().numpy()
+
+
 def threshold_sweep_IoU(true_image, image, class_id, th_factors, include_bg=False):
     """float64 [K]: the single-class IoU of ``image`` thresholded at each factor of ``th_factors`` (threshold_tests.py:113-121),
     i.e. ``[compute_IoU(true_image, threshold_image(image, class_id, th_factor=f), class_id=class_id, include_bg=include_bg)

@@ -686,6 +686,72 @@ int asr_segment_match_i32(const int32_t* truth, const int32_t* truth_root, const
                           const int32_t* pred_root, int64_t* counts, int32_t* pred_match, int32_t* truth_match, void* workspace,
                           size_t workspace_bytes, int maps, int h, int w, int num_labels, int include_zero, asr_stream_t stream);
 
+/* --- windowed CRF: label maps decided jointly over classes and image ------------------------------------------------------
+ * Mean-field inference of a dense CRF with Potts compatibility whose pairwise terms reach a (dilated) window round each pixel
+ * -- the locally connected form of ConvCRF (Teichmann and Cipolla, "Convolutional CRFs for Semantic Segmentation") of the
+ * dense CRF of Kraehenbuehl and Koltun: exact message passing inside the window, no lattice, no atomics.
+ *  - labels l = 0 .. L-1, 2 <= L <= 32: label 0 is "no class", label l >= 1 is class ids[l-1] (ids: K = L - 1 distinct ids >= 1,
+ *    a HOST int array as in the label-map section);
+ *  - unaries z [L, H, W] f32, finite; guide I [H, W, 3] f32 (the project's images are in [0, 1]);
+ *  - asr_crf_config: radius r in 1..7; dilation d >= 1 with r d <= 16; iterations T in 0..32; w_app, w_smooth finite and >= 0;
+ *    theta_pos, theta_rgb, theta_smooth finite and > 0.
+ * Weights.  The neighbours of p are q = p + d (dy, dx), |dy|, |dx| <= r, (dy, dx) != (0, 0), q inside the image (a CLIPPED
+ * window, as in the guided filter).  With delta^2 = d^2 (dy^2 + dx^2):
+ *    a(p,q) = exp(max(-delta^2 / (2 theta_pos^2) - |I_p - I_q|^2 / (2 theta_rgb^2), -80))
+ *    g(p,q) = exp(max(-delta^2 / (2 theta_smooth^2), -80))
+ * The clamp keeps every weight a normal f32 number: no normaliser underflows to 0, and a pixel whose colour is far from all
+ * its neighbours still averages them by distance.
+ * Iteration.  Q^0 = softmax_l(z).  For t = 1 .. T, all pixels in parallel from Q^{t-1} (ping-pong buffers):
+ *    s_l(p) = z_l(p) + w_app sum_q a Q_l^{t-1}(q) / sum_q a + w_smooth sum_q g Q_l^{t-1}(q) / sum_q g
+ *    Q^t = softmax_l(s), the maximum subtracted first.
+ * A pixel without neighbours (the 1 x 1 image) has both terms equal to 0.
+ * Output.  labels[p] = the id of argmax_l over the FINAL LOGITS s (z when T = 0), equal values going to the lowest l; q_out,
+ * when not NULL, receives Q^T [L, H, W].  Everything is f32; the sums run over the offsets in ascending (dy, dx) order; the same
+ * input gives the same bits on every call.
+ *
+ * Unaries, both specified to the bit:
+ * asr_crf_unaries_scores_f32: scores [K, pixels] (plane k: the SR output S_k of class ids[k], what asr_fuse_labels_f32 reads)
+ *   -> z [K + 1, pixels]: z_0 = 0, z_{k+1} = (S_k - t_k) / tau with t_k = max(S_k) * th_factor, the f32 product of
+ *   asr_fuse_labels_f32, then one f32 subtraction and one f32 division; tau finite and > 0.  minmax_ws: [K, 2] floats of scratch
+ *   (asr_minmax_f32's extrema, as in the fusion).  S_k > t_k exactly when S_k - t_k > 0 (gradual underflow), and with tau <= 1
+ *   the division cannot round a non-zero margin to zero; hence, for tau <= 1, with T = 0 the label map is asr_fuse_labels_f32's
+ *   bit for bit at K = 1, and for K > 1 wherever at most one class passes.  (With tau > 1 a subnormal margin can round to 0 and
+ *   the pixel then falls to label 0.)  Where several classes pass, the MARGIN S_k - t_k ranks them here, not S_k as
+ *   in the fusion: a class of a small maximum can win over a class of a greater score.  There is no max-map (slice_max) form: the
+ *   pass rule S >= Smax there is not a threshold.
+ * asr_crf_unaries_labels_f32: an int32 label map [pixels] -> z [L, pixels], the unary_from_labels of common CRF practice:
+ *   z_l = log(conf) where the map holds label l's id (0 for l = 0), log((1 - conf) / (L - 1)) for the other l; all z_l = 0 where
+ *   the map holds a value outside {0} u ids.  conf in (1/L, 1); the two logarithms are taken on the host in double, of the f32
+ *   conf, and rounded once to f32.
+ * asr_crf_refine_f32: one launch for Q^0, one per iteration, the last of which writes the labels (T = 0: a single launch).
+ *   workspace: asr_crf_workspace_bytes(L, H, W) = 2 * 4 * L * H * W bytes (the two Q buffers; host arithmetic, 0 for a bad size),
+ *   4-byte aligned, required whatever T is.  q_out must not overlap z (the launches read z while they park logits in q_out):
+ *   an overlap returns ASR_ERR_INVALID_ARG.
+ * Null pointers and bad values return ASR_ERR_INVALID_ARG; a value beyond a cap (radius > 7, radius * dilation > 16,
+ * iterations > 32, L > 32 or K > 31) returns ASR_ERR_UNSUPPORTED and the message names the cap.  Refusals happen before any
+ * launch and nothing is written.
+ * How: a workgroup of 1024 threads owns a 32 x 32 tile, one pixel per thread, and stages the guide tile with its r d halo in
+ * LDS once, then the Q planes with halo in chunks of 8 labels (4 when L <= 4 or when r d > 14, so that the planes fit):
+ * 4 * (452 + (3 + chunk) * R * (R + 1)) bytes with R = 32 + 2 r d (452 floats: two per-offset tables).  Within a chunk the offset loop is outermost, so a and g are formed
+ * once per pixel, offset and chunk.  No workgroup ever waits for another. */
+typedef struct asr_crf_config {
+    int radius;          /* r: the window is (2r+1)^2 offsets */
+    int dilation;        /* d: offsets are d * (dy, dx) */
+    int iterations;      /* T mean-field iterations */
+    float w_app;         /* weight of the appearance (bilateral) kernel a */
+    float w_smooth;      /* weight of the smoothness kernel g */
+    float theta_pos;     /* spatial width of a, pixels */
+    float theta_rgb;     /* colour width of a, in the guide's units */
+    float theta_smooth;  /* spatial width of g, pixels */
+} asr_crf_config;
+size_t asr_crf_workspace_bytes(int L, int H, int W);
+int asr_crf_unaries_scores_f32(const float* scores, float* minmax_ws, float* z, int64_t pixels, int K, float th_factor,
+                               float tau, asr_stream_t stream);
+int asr_crf_unaries_labels_f32(const int32_t* labels, float* z, int64_t pixels, const int* ids, int L, float conf,
+                               asr_stream_t stream);
+int asr_crf_refine_f32(const float* guide, const float* z, const int* ids, int L, int H, int W, const asr_crf_config* cfg,
+                       void* workspace, int32_t* labels, float* q_out, asr_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * DeepLabV3+ (Xception-65, OS16) layers -- model.py.  BatchNorm is folded by the caller.
  * ------------------------------------------------------------------------------------------ */

@@ -38,6 +38,14 @@ is a good start for images in [0, 1]), so a boundary is cheap where the image ha
 Independent of --guide_radius and combinable with it; compare the --band_widths curve with and without it.  Off when omitted:
 nothing else is launched and every CSV is what it was.
 
+--crf_iters T [--crf_radius R --crf_dilation D --crf_w_app A --crf_w_smooth S --crf_theta_pos P --crf_theta_rgb C --crf_theta_smooth G
+--crf_tau U --crf_standard_conf F]: every SR label map is decided by the windowed CRF (include/asr_hip.h, "windowed CRF": T mean-field
+iterations in a (2R+1)^2 window of dilation D) over all classes and the image at once, instead of pixel by pixel: the unaries are
+each class's margin over its threshold divided by U (default 0.1), and neighbours that look alike in the image vote jointly.  With
+--crf_standard_conf F the standard label map is refined too, from unaries that trust the map with confidence F.  Not in slice_max
+mode and not together with --th_sweep / --th_factors.  What it does to real network output is not known: compare the --band_widths
+curve with and without it.  Off when omitted: nothing else is launched and every CSV keeps its columns either way.
+
 --coverages 50,60,70,80,90,100 [--coverage_out FILE] [--uncertainty_dir DIR]: the risk-coverage curve as well -- the variance of
 the class stacks over the realigned copies (include/asr_hip.h at asr_realign_moments_f32; utils.uncertainty_map) says where the
 copies disagreed, and every label map is scored on each image's p % most certain non-void pixels (asr_binned_class_counts_f32),
@@ -105,6 +113,18 @@ parser.add_argument("--guide_radius", type=int, default=None,
 parser.add_argument("--guide_eps", type=float, default=None, help="the guided filter's regulariser (default 1e-3)")
 parser.add_argument("--tv_guide_beta", type=float, default=None,
                     help="weight the solver's TV prior by the image's edges with this beta (finite, >= 0; e.g. 100)")
+parser.add_argument("--crf_iters", type=int, default=None,
+                    help="decide the SR label maps with the windowed CRF of this many mean-field iterations (0..32)")
+parser.add_argument("--crf_radius", type=int, default=None, help="the CRF's window radius (1..7, default 3)")
+parser.add_argument("--crf_dilation", type=int, default=None, help="the CRF window's dilation (radius x dilation <= 16, default 1)")
+parser.add_argument("--crf_w_app", type=float, default=None, help="weight of the CRF's appearance kernel (default 4)")
+parser.add_argument("--crf_w_smooth", type=float, default=None, help="weight of the CRF's smoothness kernel (default 1)")
+parser.add_argument("--crf_theta_pos", type=float, default=None, help="spatial width of the appearance kernel (default 2)")
+parser.add_argument("--crf_theta_rgb", type=float, default=None, help="colour width of the appearance kernel (default 0.1)")
+parser.add_argument("--crf_theta_smooth", type=float, default=None, help="width of the smoothness kernel (default 1)")
+parser.add_argument("--crf_tau", type=float, default=None, help="temperature of the CRF's unaries (default 0.1)")
+parser.add_argument("--crf_standard_conf", type=float, default=None,
+                    help="also refine the standard label map with the CRF, its unaries from the map at this confidence")
 parser.add_argument("--coverages", default=None,
                     help="comma-separated whole percentages (1..100, at most 16), e.g. 50,60,70,80,90,100: the risk-coverage curve too")
 parser.add_argument("--coverage_out", default=None, help="CSV file for the risk-coverage curve (default: <--out stem>_coverage.csv)")
@@ -128,7 +148,7 @@ def main():
                                     write_confusion_csv, write_confusion_metrics_csv, write_labelmap_csv,
                                     write_coverage_csv, write_labelmap_threshold_csv, write_regions_csv, write_segments_csv,
                                     write_trimap_csv)
-    from asr_amd.ops import check_coverages, check_min_region, check_segments, check_tv_beta
+    from asr_amd.ops import check_coverages, check_crf, check_min_region, check_segments, check_tv_beta
     from asr_amd.model import DeeplabV3Plus
     from asr_amd.pipeline import HotPath
     from asr_amd.superresolution_scripts.optimizer import Optimizer
@@ -189,6 +209,23 @@ def main():
             check_tv_beta(args.tv_guide_beta, "--tv_guide_beta")
         except ValueError as e:
             parser.error(str(e))
+    crf_flags = {"radius": args.crf_radius, "dilation": args.crf_dilation, "w_app": args.crf_w_app, "w_smooth": args.crf_w_smooth,
+                 "theta_pos": args.crf_theta_pos, "theta_rgb": args.crf_theta_rgb, "theta_smooth": args.crf_theta_smooth,
+                 "tau": args.crf_tau, "standard_conf": args.crf_standard_conf}
+    crf = None
+    if args.crf_iters is None:
+        if any(v is not None for v in crf_flags.values()):
+            parser.error("the --crf_* flags need --crf_iters")
+    else:
+        crf = dict({k: v for k, v in crf_flags.items() if v is not None}, iterations=args.crf_iters)
+        if args.mode == "slice_max":
+            parser.error("--crf_iters in slice_max mode: a class passes against its max map there, so there is no unary")
+        if factors is not None:
+            parser.error("--crf_iters with --th_sweep / --th_factors: the sweep counts the fusion rule's label maps")
+        try:                # every field's range: the library's own check, ahead of the model
+            check_crf({k: v for k, v in crf.items() if k not in ("tau", "standard_conf")})
+        except ValueError as e:
+            parser.error(f"--crf_*: {e}")
     if (args.coverage_out or args.uncertainty_dir) and not args.coverages:
         parser.error("--coverage_out and --uncertainty_dir need --coverages")
     covs = None
@@ -226,6 +263,7 @@ def main():
                              **(dict(th_factors=factors) if factors is not None else {}),
                              **(dict(guide=guide) if guide is not None else {}),
                              **(dict(tv_guide=args.tv_guide_beta) if args.tv_guide_beta is not None else {}),
+                             **(dict(crf=crf) if crf is not None else {}),
                              **(dict(coverages=covs, uncertainty_dir=args.uncertainty_dir) if covs is not None else {}),
                              **(dict(min_region=min_region) if min_region is not None else {}),
                              **(dict(segments=segments) if segments is not None else {}))
