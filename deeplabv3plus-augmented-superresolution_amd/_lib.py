@@ -53,6 +53,17 @@ class SrConfig(C.Structure):
                 ("prior", C.c_int), ("btv_alpha", C.c_float), ("btv_shift", C.c_int), ("plane_chunk", C.c_int)]
 
 
+DF_L2, DF_L1, DF_HUBER = 0, 1, 2                     # ASR_DF_*
+DF_LOSSES = {"l2": DF_L2, "l1": DF_L1, "huber": DF_HUBER}
+CONF_KINDS = {"maxprob": 1, "margin": 2}             # ASR_CONF_*
+
+
+class SrDataTerm(C.Structure):
+    """struct asr_sr_data_term (include/asr_hip.h): loss, per-measurement weights and TV planes of the *_dt SR entry points."""
+    _fields_ = [("loss", C.c_int), ("delta", C.c_float), ("weights", C.c_void_p), ("weights_shared", C.c_int),
+                ("wy", C.c_void_p), ("wx", C.c_void_p), ("tv_shared", C.c_int)]
+
+
 class CrfConfig(C.Structure):
     """struct asr_crf_config (include/asr_hip.h): window, iterations and kernels of asr_crf_refine_f32."""
     _fields_ = [("radius", C.c_int), ("dilation", C.c_int), ("iterations", C.c_int), ("w_app", C.c_float),
@@ -62,6 +73,7 @@ class CrfConfig(C.Structure):
 MAX_CRF_RADIUS, MAX_CRF_HALO, MAX_CRF_ITERATIONS, MAX_CRF_LABELS = 7, 16, 32, 32     # asr_crf_refine_f32's caps
 _cfg = C.POINTER(SrConfig)
 _crf = C.POINTER(CrfConfig)
+_dt = C.POINTER(SrDataTerm)
 ABI_VERSION = 3          # ASR_ABI_VERSION of include/asr_hip.h this table mirrors
 
 # name -> (restype, argtypes).  Order and types mirror include/asr_hip.h exactly.
@@ -86,6 +98,10 @@ SIGNATURES = {
     "asr_sr_backward_wtv_f32": (_i, [_vp] * 10 + [_i] * 6 + [_fl] * 4 + [_cfg, _vp, _vp, _i, _vp]),
     "asr_sr_loss_terms_wtv_f64": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _cfg, _vp, _vp, _i, _vp]),
     "asr_sr_solve_wtv_f32": (_i, [_vp] * 10 + [_i, _vp, _vp, _sz] + [_i] * 6 + [_fl] * 4 + [_cfg, _vp, _vp, _i, _vp]),
+    "asr_sr_forward_residual_dt_f32": (_i, [_vp] * 6 + [_i] * 6 + [_dt, _vp]),
+    "asr_sr_loss_terms_dt_f64": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _cfg, _dt, _vp]),
+    "asr_sr_solve_workspace_bytes_dt": (_sz, [_i] * 6 + [_cfg]),
+    "asr_sr_solve_dt_f32": (_i, [_vp] * 10 + [_i, _vp, _vp, _sz] + [_i] * 6 + [_fl] * 4 + [_cfg, _dt, _vp]),
     "asr_realign_max_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "asr_realign_mean_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "asr_realign_max_mean_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
@@ -95,6 +111,7 @@ SIGNATURES = {
     "asr_realign_moments_f32": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _fl, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "asr_minmax_f32": (_i, [_vp, _vp, _i64, _i, _vp]),
     "asr_class_activation_f32": (_i, [_vp, _vp, _i64, _i, _i, _vp]),
+    "asr_opm_confidence_f32": (_i, [_vp, _vp, _i64, _i, _i, _vp]),
     "asr_argmax_i32": (_i, [_vp, _vp, _i64, _i, _vp]),
     "asr_opm_argmax_f32": (_i, [_vp, _vp, _i64, _i, _i, _vp]),
     "asr_opm_slice_max_f32": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp]),

@@ -841,6 +841,37 @@ __global__ __launch_bounds__(256) void class_activation_kernel(const float* __re
     }
 }
 
+// ---- confidence per pixel (asr_opm_confidence_f32; include/asr_hip.h: the rule) ------------------------------------------
+// The statements of activate_row's softmax on the same operands -- the row maximum by fmaxf in class order, the sum of
+// expf(z - max) in class order, one division per entry -- for the largest entry (expf(0) is 1) and the second largest.
+__device__ __forceinline__ float confidence_row(const float* row, int classes, int kind) {
+    float mx = row[0];
+    for (int c = 1; c < classes; ++c) mx = fmaxf(mx, row[c]);
+    float sum = 0.f;
+    for (int c = 0; c < classes; ++c) sum += expf(row[c] - mx);
+    const float top = 1.0f / sum;
+    if (kind == ASR_CONF_MAXPROB) return top;
+    float m1 = row[0], m2 = -__builtin_inff();          // the two largest logits, with multiplicity
+    for (int c = 1; c < classes; ++c) {
+        const float v = row[c];
+        if (v > m1) { m2 = m1; m1 = v; }
+        else if (v > m2) m2 = v;
+    }
+    return top - expf(m2 - mx) / sum;
+}
+
+template <bool STAGED>
+__global__ __launch_bounds__(256) void opm_confidence_kernel(const float* __restrict__ logits, float* __restrict__ out,
+                                                            int64_t pixels, int classes, int kind) {
+    __shared__ float tile[STAGED ? 256 * kMaxStageClasses : 1];
+    for (int64_t first = (int64_t)blockIdx.x * 256; first < pixels; first += (int64_t)gridDim.x * 256) {
+        const int64_t p = first + threadIdx.x;
+        const float* row = STAGED ? stage_rows(logits, first, pixels, classes, tile) : logits + p * classes;
+        if (p < pixels) out[p] = confidence_row(row, classes, kind);
+        if (STAGED) __syncthreads();
+    }
+}
+
 int stream_grid(int64_t n) {
     int64_t g = asr_cdiv(n, 256);
     return (int)(g < 2048 ? (g > 0 ? g : 1) : 2048);
@@ -1182,6 +1213,21 @@ extern "C" int asr_class_activation_f32(const float* logits, float* out, int64_t
     else
         hipLaunchKernelGGL(class_activation_kernel<false>, dim3(stream_grid(pixels)), dim3(256), 0, asr_stream(stream), logits, out,
                            pixels, classes, kind);
+    ASR_LAUNCH_CHECK();
+    return ASR_OK;
+}
+
+extern "C" int asr_opm_confidence_f32(const float* logits, float* out, int64_t pixels, int classes, int kind,
+                                      asr_stream_t stream) {
+    ASR_REQUIRE(logits && out, "asr_opm_confidence_f32: null pointer");
+    ASR_REQUIRE(pixels > 0 && classes > 0, "asr_opm_confidence_f32: bad shape (pixels=%lld classes=%d)", (long long)pixels, classes);
+    ASR_REQUIRE(kind == ASR_CONF_MAXPROB || kind == ASR_CONF_MARGIN, "asr_opm_confidence_f32: unknown kind %d (1 = maxprob, 2 = margin)", kind);
+    if (classes > kMaxStageClasses)      // rows beyond the LDS tile: each thread walks its own row in global memory
+        hipLaunchKernelGGL(opm_confidence_kernel<false>, dim3(stream_grid(pixels)), dim3(256), 0, asr_stream(stream), logits, out,
+                           pixels, classes, kind);
+    else
+        hipLaunchKernelGGL(opm_confidence_kernel<true>, dim3(stream_grid(pixels)), dim3(256), 0, asr_stream(stream), logits, out, pixels,
+                           classes, kind);
     ASR_LAUNCH_CHECK();
     return ASR_OK;
 }

@@ -137,10 +137,33 @@ __device__ __forceinline__ void dg_record(int stage, float i0, float i1, float i
 #else
 #define ASR_KFWD_ATTR
 #endif
-template <bool BORDERED>
+// DT: the data term of asr_sr_data_term (include/asr_hip.h, "data term").  The DT = false instantiations take an empty
+// argument and write the raw residual r, as they always did; the DT = true ones write q = w * psi(r) to `resid` -- what the
+// backward kernels then read as "the residual" -- and, on request, r itself.  loss, the weights and r_out are uniform: three
+// scalar branches after the gathers, one more 4-byte load per element when there are weights.
+template <bool DT>
+struct SrDtArg {};
+template <>
+struct SrDtArg<true> {
+    int loss;                 // ASR_DF_*
+    float delta;              // Huber's threshold
+    const float* w;           // [batch, n, h, w] or [n, h, w] (stride 0), or nullptr: unweighted, no multiply at all
+    int64_t w_stride;         // floats between the weights of two images: n * h * w, or 0 for one stack shared by the batch
+    float* r_out;             // the raw residual as well, or nullptr
+};
+typedef SrDtArg<true> SrDt;
+
+// psi = rho' / 2 of the data term, one statement per loss; a NaN residual stays a NaN under L2 and Huber
+__device__ __forceinline__ float sr_dt_psi(float r, int loss, float delta) {
+    if (loss == ASR_DF_L1) return (r > 0.0f) ? 0.5f : ((r < 0.0f) ? -0.5f : 0.0f);
+    if (loss == ASR_DF_HUBER) return (r < -delta) ? -delta : ((r > delta) ? delta : r);
+    return r;
+}
+
+template <bool BORDERED, bool DT = false>
 __global__ __launch_bounds__(256) ASR_KFWD_ATTR void sr_forward_residual_kernel(
     const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ rot_tf,
-    const float* __restrict__ trans_tf, float* __restrict__ resid, SrDims d) {
+    const float* __restrict__ trans_tf, float* __restrict__ resid, SrDims d, SrDtArg<DT> dt) {
 #ifdef ASR_DIAG_KFWD_TOP_VGPR
     ASR_DIAG_TOUCH_VGPR(ASR_DIAG_KFWD_TOP_VGPR);
 #endif
@@ -271,7 +294,15 @@ __global__ __launch_bounds__(256) ASR_KFWD_ATTR void sr_forward_residual_kernel(
     const float bot = bl + (br - bl) * 0.5f;
     const float dval = top + (bot - top) * 0.5f;
     const int64_t o = ((int64_t)bn * d.h + i) * d.w + j;
-    resid[o] = dval - y[o];
+    if constexpr (DT) {
+        const float r = dval - y[o];
+        if (dt.r_out) dt.r_out[o] = r;
+        float q = sr_dt_psi(r, dt.loss, dt.delta);
+        if (dt.w) q = dt.w[(int64_t)b * dt.w_stride + (o - (int64_t)b * d.n * d.h * d.w)] * q;
+        resid[o] = q;
+    } else {
+        resid[o] = dval - y[o];
+    }
 #ifdef ASR_DIAG_KFWD_CHECK
     {
         const float et = dg_add(tl, dg_mul(dg_sub(trv, tl), 0.5f)), eb = dg_add(bl, dg_mul(dg_sub(br, bl), 0.5f));
@@ -778,6 +809,33 @@ __global__ __launch_bounds__(256) void sr_loss_df_kernel(const float* __restrict
     if ((threadIdx.x & 63) == 0) atomicAdd(out + (int64_t)b * 4 + 0, acc);
 }
 
+// terms[b][0] of a data term: sum w * rho(r) from the RAW residual.  Each term in float32, one operation per statement (at most
+// four roundings: the Huber tail's subtraction and product, and the weight), accumulated in float64 like the sum above.
+__global__ __launch_bounds__(256) void sr_loss_df_dt_kernel(const float* __restrict__ resid, double* __restrict__ out,
+                                                            int64_t per_image, SrDt dt) {
+    const int b = blockIdx.y;
+    const float* r = resid + (int64_t)b * per_image;
+    const float* wgt = dt.w ? dt.w + (int64_t)b * dt.w_stride : nullptr;
+    double acc = 0.0;
+    for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < per_image; p += (int64_t)gridDim.x * 256) {
+        const float t = r[p];
+        const float a = fabsf(t);
+        float rho;
+        if (dt.loss == ASR_DF_L1) {
+            rho = a;
+        } else if (dt.loss == ASR_DF_HUBER && !(a <= dt.delta)) {
+            const float lin = 2.0f * a - dt.delta;      // 2|r| is exact
+            rho = dt.delta * lin;
+        } else {
+            rho = t * t;
+        }
+        if (wgt) rho = wgt[p] * rho;
+        acc += (double)rho;
+    }
+    acc = asr_wave_sum(acc);
+    if ((threadIdx.x & 63) == 0) atomicAdd(out + (int64_t)b * 4 + 0, acc);
+}
+
 template <bool WTV>
 __global__ __launch_bounds__(256) void sr_loss_prior_kernel(const float* __restrict__ x, double* __restrict__ out,
                                                             int H, int W, SrStep st, SrTvW tw) {
@@ -1256,6 +1314,7 @@ size_t sr_workspace_bytes(int batch, int n, int H, int W, int h, int w, int chun
     return sizeof(float) * ((size_t)batch * n * h * w + 2 * (size_t)batch * H * W +
                             ((size_t)batch * chunk + batch) * sr_gr_plane_elems(H, W)) + sizeof(int) * (size_t)batch;
 }
+size_t sr_dt_workspace_extra(int batch, int n, int h, int w) { return sizeof(float) * (size_t)batch * n * h * w; }
 dim3 gather_grid(const SrDims& d) {
     return dim3((unsigned)asr_cdiv(d.W, 64), (unsigned)asr_cdiv(d.H, 4), (unsigned)d.batch);
 }
@@ -1288,7 +1347,45 @@ extern "C" int asr_sr_forward_residual_f32(const float* x, const float* y, const
     int rc = check_dims("asr_sr_forward_residual_f32", batch, n, H, W, h, w, &d);
     if (rc != ASR_OK) return rc;
     hipLaunchKernelGGL(sr_forward_residual_kernel<false>, lr_grid(d), kBlock, 0, asr_stream(stream), x, y, rot_tf, trans_tf,
-                       resid, d);
+                       resid, d, SrDtArg<false>{});
+    ASR_LAUNCH_CHECK();
+    return ASR_OK;
+}
+
+namespace {
+
+// asr_sr_data_term -> kernel argument and the TV planes; every refusal of the data term, before any launch.  n, h, w: the
+// shape the weights are read with.
+int make_data_term(const char* fn, const asr_sr_data_term* dt, int n, int h, int w, SrDt* out) {
+    ASR_REQUIRE(dt, "%s: null data term", fn);
+    ASR_REQUIRE(dt->loss == ASR_DF_L2 || dt->loss == ASR_DF_L1 || dt->loss == ASR_DF_HUBER, "%s: unknown loss %d", fn, dt->loss);
+    if (dt->loss == ASR_DF_HUBER)
+        ASR_REQUIRE(dt->delta > 0.0f && dt->delta < __builtin_inff(), "%s: Huber delta=%g must be finite and > 0", fn, (double)dt->delta);
+    ASR_REQUIRE((dt->wy == nullptr) == (dt->wx == nullptr), "%s: null pointer (wy, wx: both or neither)", fn);
+    if (dt->weights) ASR_REQUIRE(n > 0 && h > 0 && w > 0, "%s: weights with a bad shape n=%d %dx%d", fn, n, h, w);
+    out->loss = dt->loss;
+    out->delta = dt->delta;
+    out->w = dt->weights;
+    out->w_stride = dt->weights_shared ? 0 : (int64_t)n * h * w;
+    out->r_out = nullptr;
+    return ASR_OK;
+}
+
+}  // namespace
+
+extern "C" int asr_sr_forward_residual_dt_f32(const float* x, const float* y, const float* rot_tf, const float* trans_tf,
+                                              float* q_out, float* r_out, int batch, int n, int H, int W, int h, int w,
+                                              const asr_sr_data_term* dt, asr_stream_t stream) {
+    ASR_REQUIRE(x && y && rot_tf && trans_tf && q_out, "asr_sr_forward_residual_dt_f32: null pointer");
+    SrDt a;
+    int rc = make_data_term("asr_sr_forward_residual_dt_f32", dt, n, h, w, &a);
+    if (rc != ASR_OK) return rc;
+    SrDims d;
+    rc = check_dims("asr_sr_forward_residual_dt_f32", batch, n, H, W, h, w, &d);
+    if (rc != ASR_OK) return rc;
+    a.r_out = r_out;
+    hipLaunchKernelGGL((sr_forward_residual_kernel<false, true>), lr_grid(d), kBlock, 0, asr_stream(stream), x, y, rot_tf,
+                       trans_tf, q_out, d, a);
     ASR_LAUNCH_CHECK();
     return ASR_OK;
 }
@@ -1375,7 +1472,8 @@ int sr_backward_impl(const char* fn, const float* x, float* x_new, const float* 
 }
 
 int sr_loss_terms_impl(const char* fn, const float* x, const float* resid, double* terms, int batch, int n, int H, int W, int h,
-                       int w, const asr_sr_config* cfg, const SrTvWArg& wa, asr_stream_t stream) {
+                       int w, const asr_sr_config* cfg, const SrTvWArg& wa, asr_stream_t stream, const SrDt* dt = nullptr) {
+    // dt: resid is the RAW residual and terms[b][0] the data term's sum w * rho(r); nullptr: sum resid^2, as ever
     ASR_REQUIRE(x && resid && terms, "%s: null pointer", fn);
     ASR_REQUIRE(batch > 0 && batch <= 65535, "%s: bad batch %d", fn, batch);
     SrStep st;
@@ -1388,7 +1486,8 @@ int sr_loss_terms_impl(const char* fn, const float* x, const float* resid, doubl
     hipStream_t s = asr_stream(stream);
     ASR_HIP_CHECK(hipMemsetAsync(terms, 0, sizeof(double) * 4 * batch, s));
     const int64_t per_image = (int64_t)n * h * w;
-    hipLaunchKernelGGL(sr_loss_df_kernel, dim3(64, batch), dim3(256), 0, s, resid, terms, per_image);
+    if (dt) hipLaunchKernelGGL(sr_loss_df_dt_kernel, dim3(64, batch), dim3(256), 0, s, resid, terms, per_image, *dt);
+    else hipLaunchKernelGGL(sr_loss_df_kernel, dim3(64, batch), dim3(256), 0, s, resid, terms, per_image);
     ASR_LAUNCH_CHECK();
     if (wa.weighted) hipLaunchKernelGGL(sr_loss_prior_kernel<true>, dim3(64, batch), dim3(256), 0, s, x, terms, H, W, st, tw);
     else hipLaunchKernelGGL(sr_loss_prior_kernel<false>, dim3(64, batch), dim3(256), 0, s, x, terms, H, W, st, tw);
@@ -1440,6 +1539,15 @@ extern "C" int asr_sr_loss_terms_wtv_f64(const float* x, const float* resid, dou
     return sr_loss_terms_impl("asr_sr_loss_terms_wtv_f64", x, resid, terms, batch, n, H, W, h, w, cfg, wa, stream);
 }
 
+extern "C" int asr_sr_loss_terms_dt_f64(const float* x, const float* r, double* terms, int batch, int n, int H, int W, int h,
+                                        int w, const asr_sr_config* cfg, const asr_sr_data_term* dt, asr_stream_t stream) {
+    SrDt a;
+    const int rc = make_data_term("asr_sr_loss_terms_dt_f64", dt, n, h, w, &a);
+    if (rc != ASR_OK) return rc;
+    const SrTvWArg wa = {dt->wy, dt->wx, dt->tv_shared, dt->wy != nullptr};
+    return sr_loss_terms_impl("asr_sr_loss_terms_dt_f64", x, r, terms, batch, n, H, W, h, w, cfg, wa, stream, &a);
+}
+
 extern "C" int asr_sr_loss_terms_f64(const float* x, const float* resid, double* terms, int batch, int n, int H, int W,
                                      int h, int w, asr_stream_t stream) {
     const asr_sr_config c = adam_tv_config(0.f, 0.f, 0.f, 0);
@@ -1464,7 +1572,10 @@ int sr_solve_impl(const char* fn, float* x, const float* y, const float* rot_tf,
                   const float* inv_trans_tf, float* m, float* v, float* vhat, const float* alphas, int num_iter,
                   double* last_loss_terms, void* workspace, size_t workspace_bytes, int batch, int n, int H, int W, int h, int w,
                   float lambda_df, float lambda_tv, float lambda_l2, float lambda_l1, const asr_sr_config* cfg,
-                  const SrTvWArg& wa, asr_stream_t stream) {
+                  const SrTvWArg& wa, asr_stream_t stream, const SrDt* dt = nullptr) {
+    // dt (asr_sr_solve_dt_f32): K_fwd writes q = w * psi(r) where the other entry points write r; everything after reads that
+    // buffer as it always did.  The workspace then ends with a second [batch*n, h, w] buffer: the raw r of the last iteration,
+    // a second output of that one K_fwd launch, for the loss terms.
     ASR_REQUIRE(x && y && rot_tf && trans_tf && inv_rot_tf && inv_trans_tf && alphas && workspace, "%s: null pointer", fn);
     ASR_REQUIRE(num_iter >= 0, "%s: num_iter < 0", fn);
     SrDims d;
@@ -1479,7 +1590,8 @@ int sr_solve_impl(const char* fn, float* x, const float* y, const float* rot_tf,
     ASR_REQUIRE(cfg->plane_chunk >= 0, "%s: plane_chunk %d < 0", fn, cfg->plane_chunk);
     const int chunk = sr_plane_chunk(batch, n, H, W, cfg->plane_chunk);
     ASR_REQUIRE((int64_t)batch * chunk <= 65535, "%s: batch*chunk=%lld exceeds 65535 (grid.z)", fn, (long long)batch * chunk);
-    const size_t need = sr_workspace_bytes(batch, n, H, W, h, w, chunk);
+    const size_t base = sr_workspace_bytes(batch, n, H, W, h, w, chunk);
+    const size_t need = base + (dt ? sr_dt_workspace_extra(batch, n, h, w) : 0);
     if (workspace_bytes < need) {
         asr_set_error("%s: workspace %zu < required %zu bytes", fn, workspace_bytes, need);
         return ASR_ERR_WORKSPACE;
@@ -1494,6 +1606,7 @@ int sr_solve_impl(const char* fn, float* x, const float* y, const float* rot_tf,
     const SrGradTranslateKernel gr_kernel = sr_grad_translate_kernel_for(d.f);
     float* const xb = gr + (size_t)batch * chunk * sr_gr_plane_elems(H, W);   // bordered copy of the current x
     int* const affine_flags = reinterpret_cast<int*>(xb + (size_t)batch * sr_gr_plane_elems(H, W));
+    float* const raw = reinterpret_cast<float*>(static_cast<char*>(workspace) + base);   // dt only
     if (num_iter > 0) {
         hipLaunchKernelGGL(sr_affine_flags_kernel, dim3((unsigned)batch), dim3(64), 0, s, inv_rot_tf, affine_flags, n);
         ASR_LAUNCH_CHECK();
@@ -1508,10 +1621,18 @@ int sr_solve_impl(const char* fn, float* x, const float* y, const float* rot_tf,
                                            hipMemcpyDeviceToDevice, s));
     }
     for (int it = 0; it < num_iter; ++it) {
-        hipLaunchKernelGGL(sr_forward_residual_kernel<true>, lr_grid(d), kBlock, 0, s, xb, y, rot_tf, trans_tf, resid, d);
+        const bool want_terms = last_loss_terms && it == num_iter - 1;
+        if (dt) {
+            SrDt a = *dt;
+            a.r_out = want_terms ? raw : nullptr;
+            hipLaunchKernelGGL((sr_forward_residual_kernel<true, true>), lr_grid(d), kBlock, 0, s, xb, y, rot_tf, trans_tf, resid, d, a);
+        } else {
+            hipLaunchKernelGGL(sr_forward_residual_kernel<true>, lr_grid(d), kBlock, 0, s, xb, y, rot_tf, trans_tf, resid, d,
+                               SrDtArg<false>{});
+        }
         ASR_LAUNCH_CHECK();
-        if (last_loss_terms && it == num_iter - 1) {
-            rc = sr_loss_terms_impl(fn, cur, resid, last_loss_terms, batch, n, H, W, h, w, cfg, wa, stream);
+        if (want_terms) {
+            rc = sr_loss_terms_impl(fn, cur, dt ? raw : resid, last_loss_terms, batch, n, H, W, h, w, cfg, wa, stream, dt);
             if (rc != ASR_OK) return rc;
         }
         for (int n0 = 0; n0 < n; n0 += chunk) {
@@ -1592,6 +1713,25 @@ extern "C" int asr_sr_solve_wtv_f32(float* x, const float* y, const float* rot_t
     return sr_solve_impl("asr_sr_solve_wtv_f32", x, y, rot_tf, trans_tf, inv_rot_tf, inv_trans_tf, m, v, vhat, alphas, num_iter,
                          last_loss_terms, workspace, workspace_bytes, batch, n, H, W, h, w, lambda_df, lambda_tv, lambda_l2,
                          lambda_l1, cfg, wa, stream);
+}
+
+extern "C" size_t asr_sr_solve_workspace_bytes_dt(int batch, int n, int H, int W, int h, int w, const asr_sr_config* cfg) {
+    return asr_sr_solve_workspace_bytes_cfg(batch, n, H, W, h, w, cfg) + sr_dt_workspace_extra(batch, n, h, w);
+}
+
+extern "C" int asr_sr_solve_dt_f32(float* x, const float* y, const float* rot_tf, const float* trans_tf,
+                                   const float* inv_rot_tf, const float* inv_trans_tf, float* m, float* v, float* vhat,
+                                   const float* alphas, int num_iter, double* last_loss_terms, void* workspace,
+                                   size_t workspace_bytes, int batch, int n, int H, int W, int h, int w, float lambda_df,
+                                   float lambda_tv, float lambda_l2, float lambda_l1, const asr_sr_config* cfg,
+                                   const asr_sr_data_term* dt, asr_stream_t stream) {
+    SrDt a;
+    const int rc = make_data_term("asr_sr_solve_dt_f32", dt, n, h, w, &a);
+    if (rc != ASR_OK) return rc;
+    const SrTvWArg wa = {dt->wy, dt->wx, dt->tv_shared, dt->wy != nullptr};
+    return sr_solve_impl("asr_sr_solve_dt_f32", x, y, rot_tf, trans_tf, inv_rot_tf, inv_trans_tf, m, v, vhat, alphas, num_iter,
+                         last_loss_terms, workspace, workspace_bytes, batch, n, H, W, h, w, lambda_df, lambda_tv, lambda_l2,
+                         lambda_l1, cfg, wa, stream, &a);
 }
 
 extern "C" int asr_sr_solve_f32(float* x, const float* y, const float* rot_tf, const float* trans_tf,

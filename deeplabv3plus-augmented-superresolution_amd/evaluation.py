@@ -286,7 +286,7 @@ def dataset_miou(counts):
 def evaluate_labelmaps(path, image_paths, gt_paths, class_ids=tuple(range(1, 21)), num_aug=100, angle_max=0.3, shift_max=30,
                        img_size=(512, 512), rank=0, world=1, seed=1234, sr_types=("aug", "max", "mean"), prune=True,
                        save_dir=None, band_widths=None, band_ignore_label=255, confusion_labels=None, th_factors=None,
-                       guide=None, tv_guide=None, crf=None, min_region=None, segments=None, coverages=None,
+                       guide=None, df_weights=None, tv_guide=None, crf=None, min_region=None, segments=None, coverages=None,
                        uncertainty_dir=None):
     """One fused label map per image and SR type (HotPath.run_image_labels) and its score.  Returns on every rank a
     LabelmapScores, the tuple (rows, counts) plus what the options below append, every entry also an attribute by the name
@@ -322,6 +322,9 @@ def evaluate_labelmaps(path, image_paths, gt_paths, class_ids=tuple(range(1, 21)
     (run_image_labels' tv_guide; img_size must be the SR output size, no bilateral TV).  Independent of guide.  The return
     value keeps its form.
 
+    df_weights ("maxprob" or "margin"): every image's "aug" solves weight each measurement of their data term by the network's
+    confidence there (run_image_labels' df_weights; the loss is the solver's df_loss).  The return value keeps its form.
+
     crf (a dict of the windowed CRF's fields plus tau and standard_conf): every SR label map is decided by the windowed CRF over
     classes and image instead of the fusion (run_image_labels' crf; img_size must be the SR output size; not in slice_max mode
     and not together with th_factors).  The return value keeps its form.
@@ -352,6 +355,8 @@ def evaluate_labelmaps(path, image_paths, gt_paths, class_ids=tuple(range(1, 21)
                               guide, coverages, bool(uncertainty_dir), min_region, segments)
     tv_beta = path.check_tv_guide(tv_guide, tuple(img_size) + (3,))
     tv_kw = {} if tv_beta is None else {"tv_guide": tv_beta}
+    if path.check_df_weights(df_weights) is not None:
+        tv_kw["df_weights"] = df_weights
     if crf is not None:
         class_ids = list(class_ids)
         path.check_crf(crf, tuple(img_size) + (3,), th_factors, len(class_ids))

@@ -101,14 +101,65 @@ def sr_init_target(y, out_hw):
     return x
 
 
-def sr_forward_residual(x, y, rot_tf, trans_tf):
+def check_data_term(loss, delta=0.1, name="data term"):
+    """The data term's loss -> (ASR_DF_* code, delta): loss "l2", "l1" or "huber" (None is "l2"); under Huber delta must be
+    a finite number > 0, elsewhere it is not read.  Host check, before any launch (include/asr_hip.h: the rule)."""
+    import numbers
+    if loss is None:
+        loss = "l2"
+    if not isinstance(loss, str) or loss.lower() not in _lib.DF_LOSSES:
+        raise ValueError(f"{name}: loss must be one of {sorted(_lib.DF_LOSSES)}, got {loss!r}")
+    code = _lib.DF_LOSSES[loss.lower()]
+    if code != _lib.DF_HUBER:
+        return code, 0.0
+    ok = isinstance(delta, numbers.Real) and not isinstance(delta, bool) and np.isfinite(float(delta)) and float(delta) > 0.0
+    if not ok:
+        raise ValueError(f"{name}: Huber delta must be a finite number > 0, got {delta!r}")
+    return code, float(delta)
+
+
+def _data_term(data_term, weights, y, tvw, name):
+    """data_term (None, a loss name, or a pair (loss, delta)) + weights ([N,h,w] shared by the batch or [B,N,h,w], on the device
+    of y) + the checked tv_weights -> the asr_sr_data_term of a *_dt call, or None when the call that ran before data terms
+    existed computes the same thing (L2, no weights).  The struct keeps its tensors alive."""
+    if isinstance(data_term, (tuple, list)):
+        if len(data_term) != 2:
+            raise ValueError(f"{name}: data_term must be a loss name or a pair (loss, delta), got {data_term!r}")
+        code, delta = check_data_term(data_term[0], data_term[1], name)
+    else:
+        code, delta = check_data_term(data_term, name=name)
+    if weights is None and code == _lib.DF_L2:
+        return None
+    shared = 0
+    if weights is not None:
+        b, n, h, w = y.shape
+        if not isinstance(weights, torch.Tensor) or weights.dtype != f32 or not weights.is_contiguous() or weights.device != y.device:
+            raise AsrError(f"{name}: weights must be a contiguous float32 tensor on the device of the copies")
+        if tuple(weights.shape) not in ((n, h, w), (b, n, h, w)):
+            raise AsrError(f"{name}: weights must be [{n},{h},{w}] (shared) or [{b},{n},{h},{w}], got {tuple(weights.shape)}")
+        shared = int(weights.dim() == 3)
+    dt = _lib.SrDataTerm(code, delta, ptr(weights, allow_none=True), shared, ptr(tvw[0]) if tvw else None,
+                         ptr(tvw[1]) if tvw else None, tvw[2] if tvw else 0)
+    dt._keep = (weights, tvw)
+    return dt
+
+
+def sr_forward_residual(x, y, rot_tf, trans_tf, data_term=None, weights=None, want_raw=False):
+    """The residual r = D(T(R(x))) - y, or under a data term q = w * psi(r), what the backward calls take as `resid`
+    (include/asr_hip.h: the rule).  want_raw: the pair (q, r), from one launch."""
     b, n, H, W, h, w = _sr_dims(x, y)
     _check_tf(rot_tf, b, n, "rot_tf")
     _check_tf(trans_tf, b, n, "trans_tf")
+    dt = _data_term(data_term, weights, y, None, "sr_forward_residual")
     resid = torch.empty_like(y)
-    call("asr_sr_forward_residual_f32", ptr(x), ptr(y), ptr(rot_tf), ptr(trans_tf), ptr(resid), b, n, H, W, h, w,
-         stream_ptr())
-    return resid
+    if dt is None:
+        call("asr_sr_forward_residual_f32", ptr(x), ptr(y), ptr(rot_tf), ptr(trans_tf), ptr(resid), b, n, H, W, h, w,
+             stream_ptr())
+        return (resid, resid) if want_raw else resid
+    raw = torch.empty_like(y) if want_raw else None
+    call("asr_sr_forward_residual_dt_f32", ptr(x), ptr(y), ptr(rot_tf), ptr(trans_tf), ptr(resid), ptr(raw, allow_none=True),
+         b, n, H, W, h, w, C.byref(dt), stream_ptr())
+    return (resid, raw) if want_raw else resid
 
 
 def sr_config(optimizer=_lib.OPT_ADAM, flag=False, c0=0.0, c1=0.0, c2=0.0, use_btv=False, btv_alpha=0.6, btv_shift=2,
@@ -220,12 +271,18 @@ def sr_backward_adam(x, resid, inv_rot_tf, inv_trans_tf, lambdas, adam=None, wan
     return x_new, grad
 
 
-def sr_loss_terms(x, resid, cfg=None, tv_weights=None):
-    """[B,4] float64 {sum resid^2, TV or bilateral TV (cfg) or the edge-weighted TV (tv_weights), sum x^2, sum |x|}."""
+def sr_loss_terms(x, resid, cfg=None, tv_weights=None, data_term=None, weights=None):
+    """[B,4] float64 {sum resid^2, TV or bilateral TV (cfg) or the edge-weighted TV (tv_weights), sum x^2, sum |x|}.
+    Under a data term (data_term, weights: as for sr_forward_residual) resid is the RAW residual and the first entry is
+    sum weights * rho(resid)."""
     b, n, H, W, h, w = _sr_dims(x, resid)
     tvw = _tv_weights(tv_weights, x, "sr_loss_terms") if tv_weights is not None else None
+    dt = _data_term(data_term, weights, resid, tvw, "sr_loss_terms")
     terms = torch.empty((b, 4), dtype=torch.float64, device=x.device)
-    if tvw is not None:
+    if dt is not None:
+        call("asr_sr_loss_terms_dt_f64", ptr(x), ptr(resid), ptr(terms, torch.float64), b, n, H, W, h, w,
+             C.byref(cfg if cfg is not None else sr_config()), C.byref(dt), stream_ptr())
+    elif tvw is not None:
         call("asr_sr_loss_terms_wtv_f64", ptr(x), ptr(resid), ptr(terms, torch.float64), b, n, H, W, h, w,
              C.byref(cfg if cfg is not None else sr_config()), ptr(tvw[0]), ptr(tvw[1]), tvw[2], stream_ptr())
     elif cfg is None:
@@ -237,16 +294,19 @@ def sr_loss_terms(x, resid, cfg=None, tv_weights=None):
 
 
 def sr_solve(x, y, rot_tf, trans_tf, inv_rot_tf, inv_trans_tf, alphas, lambdas, one_minus_beta1=None, one_minus_beta2=None,
-             epsilon=None, amsgrad=False, want_loss=True, cfg=None, slot_init=None, state=None, tv_weights=None):
+             epsilon=None, amsgrad=False, want_loss=True, cfg=None, slot_init=None, state=None, tv_weights=None,
+             data_term=None, weights=None):
     """Runs alphas.shape[0] iterations in place on x.  alphas [num_iter, B] (device).  Either the Adam
     hyper-parameters (asr_sr_solve_f32) or cfg (+ slot_init = {"m"/"v"/"vhat": initial value}) for
     asr_sr_solve_cfg_f32.  state: a dict that carries the optimiser slots and the workspace from one call to the next --
     a solve cut into several calls (the verbose loss print-outs) then performs exactly the updates of a single call.
     tv_weights = (wy, wx): the edge-weighted TV prior; with the Adam hyper-parameters instead of cfg the call goes through
-    the equivalent {Adam, TV} config."""
+    the equivalent {Adam, TV} config.  data_term, weights: the data term sum weights * rho(r) (sr_forward_residual; combines
+    freely with tv_weights); with L2 / None and no weights the calls above are made, unchanged."""
     b, n, H, W, h, w = _sr_dims(x, y)
     tvw = _tv_weights(tv_weights, x, "sr_solve") if tv_weights is not None else None
-    if tvw is not None and cfg is None:
+    dt = _data_term(data_term, weights, y, tvw, "sr_solve")
+    if (tvw is not None or dt is not None) and cfg is None:
         cfg = _adam_config(one_minus_beta1, one_minus_beta2, epsilon, amsgrad)
     for t, name in ((rot_tf, "rot_tf"), (trans_tf, "trans_tf"), (inv_rot_tf, "inv_rot_tf"), (inv_trans_tf, "inv_trans_tf")):
         _check_tf(t, b, n, name)
@@ -255,6 +315,7 @@ def sr_solve(x, y, rot_tf, trans_tf, inv_rot_tf, inv_trans_tf, alphas, lambdas, 
     num_iter = alphas.shape[0]
     lib = _lib.load()
     ws_bytes = (lib.asr_sr_solve_workspace_bytes(b, n, H, W, h, w) if cfg is None else
+                lib.asr_sr_solve_workspace_bytes_dt(b, n, H, W, h, w, C.byref(cfg)) if dt is not None else
                 lib.asr_sr_solve_workspace_bytes_cfg(b, n, H, W, h, w, C.byref(cfg)))
     if state is not None and "ws" in state:
         ws, m, v, vhat = state["ws"], state["m"], state["v"], state["vhat"]
@@ -271,7 +332,12 @@ def sr_solve(x, y, rot_tf, trans_tf, inv_rot_tf, inv_trans_tf, alphas, lambdas, 
         if state is not None:
             state.update(ws=ws, m=m, v=v, vhat=vhat)
     terms = torch.zeros((b, 4), dtype=torch.float64, device=x.device) if want_loss else None
-    if tvw is not None:
+    if dt is not None:
+        call("asr_sr_solve_dt_f32", ptr(x), ptr(y), ptr(rot_tf), ptr(trans_tf), ptr(inv_rot_tf), ptr(inv_trans_tf), ptr(m),
+             ptr(v), ptr(vhat), ptr(alphas), num_iter, ptr(terms, torch.float64, allow_none=True), ptr(ws),
+             C.c_size_t(ws_bytes), b, n, H, W, h, w, float(lambdas[0]), float(lambdas[1]), float(lambdas[2]),
+             float(lambdas[3]), C.byref(cfg), C.byref(dt), stream_ptr())
+    elif tvw is not None:
         call("asr_sr_solve_wtv_f32", ptr(x), ptr(y), ptr(rot_tf), ptr(trans_tf), ptr(inv_rot_tf), ptr(inv_trans_tf), ptr(m),
              ptr(v), ptr(vhat), ptr(alphas), num_iter, ptr(terms, torch.float64, allow_none=True), ptr(ws),
              C.c_size_t(ws_bytes), b, n, H, W, h, w, float(lambdas[0]), float(lambdas[1]), float(lambdas[2]),
@@ -618,6 +684,26 @@ def class_activation(logits, kind):
     out = torch.empty_like(logits)
     call("asr_class_activation_f32", ptr(logits), ptr(out), logits.numel() // classes, classes,
          {"softmax": 1, "sigmoid": 2}[kind], stream_ptr())
+    return out
+
+
+def opm_confidence(logits, kind, out=None):
+    """logits [..., C] -> [...] float32: the network's confidence per pixel, "maxprob" (the largest softmax entry) or "margin"
+    (the difference of the two largest); the weights of the SR data term (include/asr_hip.h: the rule).  out: a contiguous
+    float32 tensor of that shape to write into."""
+    if kind not in _lib.CONF_KINDS:
+        raise ValueError(f"opm_confidence: kind must be one of {sorted(_lib.CONF_KINDS)}, got {kind!r}")
+    if not isinstance(logits, torch.Tensor) or logits.dim() < 1 or logits.numel() == 0:
+        raise AsrError("opm_confidence: logits must be a non-empty tensor [..., classes]")
+    shape = tuple(logits.shape[:-1])
+    if out is None:
+        out = torch.empty(shape, dtype=f32, device=logits.device)
+    elif (not isinstance(out, torch.Tensor) or tuple(out.shape) != shape or out.device != logits.device or out.dtype != f32
+          or not out.is_contiguous()):
+        raise AsrError(f"opm_confidence: out must be a contiguous float32 tensor {shape} on the device of the logits, got "
+                       f"{tuple(out.shape) if isinstance(out, torch.Tensor) else type(out).__name__}")
+    call("asr_opm_confidence_f32", ptr(logits), ptr(out), logits.numel() // logits.shape[-1], logits.shape[-1],
+         _lib.CONF_KINDS[kind], stream_ptr())
     return out
 
 

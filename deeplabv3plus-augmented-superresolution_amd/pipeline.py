@@ -15,7 +15,7 @@ from collections import namedtuple
 import numpy as np
 import torch
 
-from . import ops
+from . import _lib, ops
 from .label_record import counts_name, label_fields, label_layout
 from .superresolution_scripts import augmentation_utils as au
 from .utils import (coverage_edges, coverage_retained, iou_from_counts, mean_iou_from_counts, opm_scales,
@@ -46,13 +46,15 @@ class HotPath:
         return ops.standard_mask(logits0.contiguous(), out_hw, self.class_id, out=out)
 
     # ---- stage 1 (model stream): augment -> forward -> OPM (-> standard output) ------------------------
-    def _forward_stacks(self, image_dev, angles, shifts, planes, opm, logits0=None, profile=None, lane=0):
+    def _forward_stacks(self, image_dev, angles, shifts, planes, opm, logits0=None, profile=None, lane=0, confidence=None):
         """The copies go through the model one forward batch at a time (augmentation_utils.py:30-59 draws them in chunks
         for the same reason): each batch is augmented straight into the plan's input buffer, its logits are consumed in
         place by the OPM, which writes its rows of the image's stacks -- nothing of size [N,H,W,3] or [N,h,w,classes]
         outlives a batch.  planes: 1, or the K classes of a class set.  opm(preds, out_rows, out_max_rows) fills the batch's
         rows [planes, k, fh, fw] of the stacks (out_max_rows: None unless slice_max); logits0, when given, gets copy 0's
-        logits [fh, fw, C] (the standard output is made from them).  Returns the raw stacks y, ymax [planes, N, fh, fw]."""
+        logits [fh, fw, C] (the standard output is made from them).  confidence(preds, first, k, n), when given, is called
+        next to the OPM with each batch's logits [k, fh, fw, C], the copies first .. first + k - 1 of n (run_image_labels
+        fills its per-copy confidence stack there).  Returns the raw stacks y, ymax [planes, N, fh, fw]."""
         n = len(angles)
         h, w, _ = image_dev.shape
         eng = self.model.engine
@@ -68,6 +70,8 @@ class HotPath:
             if i == 0 and logits0 is not None:
                 logits0(self.model.logits_of(preds, 0).contiguous())
             opm(preds, y[:, i:i + k], ymax[:, i:i + k] if ymax is not None else None)
+            if confidence is not None:
+                confidence(preds, i, k, n)
             del copies, preds
         return y, ymax
 
@@ -84,11 +88,11 @@ class HotPath:
         y, ymax = self._forward_stacks(image_dev, angles, shifts, 1, opm, standard if want_standard else None, profile, lane)
         return (res,) + self._normalise(y, ymax)
 
-    def _classes_stage_model(self, image_dev, angles, shifts, ids, profile, standard):
+    def _classes_stage_model(self, image_dev, angles, shifts, ids, profile, standard, confidence=None):
         """Stage 1 of a class set: the OPM of every class into raw [K, N, h, w] stacks (y, ymax).
         standard: None, or a function of copy 0's logits [h, w, C] (the standard masks / label map are made from them)."""
         opm = lambda preds, out, out_max: au.output_processing_classes(preds, ids, self.mode, out=out, out_max=out_max)
-        return self._forward_stacks(image_dev, angles, shifts, len(ids), opm, standard, profile)
+        return self._forward_stacks(image_dev, angles, shifts, len(ids), opm, standard, profile, confidence=confidence)
 
     def _normalise(self, y, ymax):
         """load_SR_data's global min-max normalisation of each plane's stack to [0, 1] (superres_utils.py:183-206); not in
@@ -227,11 +231,14 @@ class HotPath:
             return [it0 + j * self._solves * sr.num_iter for j in range(len(ids))]
         return [int(adam_starts[c]) for c in ids]
 
-    def _classes_scores(self, y, ymax, angles, fshifts, starts, sr_types, tv_weights=None):
+    def _classes_scores(self, y, ymax, angles, fshifts, starts, sr_types, tv_weights=None, df_weights=None):
         """_sr_scores of a class set: class k's solve starts at the Adam step starts[k], its max map's num_iter later; the
-        counter itself is left as it was.  tv_weights: the image's edge weights (wy, wx), shared by every solve."""
+        counter itself is left as it was.  tv_weights: the image's edge weights (wy, wx), shared by every solve; df_weights:
+        the copies' confidence stack [N, h, w], the weights of every solve's data term."""
         sr = self.sr
         kw = {} if tv_weights is None else {"tv_guide": tv_weights}
+        if df_weights is not None:
+            kw["df_weights"] = df_weights
         solve = lambda stack, a, s, second: sr.augmented_superresolution_classes(
             stack, a[0], s[0], [st + second * sr.num_iter for st in starts], **kw)[0]
         return self._sr_scores(y, ymax, angles, fshifts, sr_types, solve)
@@ -296,7 +303,8 @@ class HotPath:
     def run_image_labels(self, image_dev, angles, shifts, class_ids=range(1, 21), gt_dev=None, adam_starts=None,
                          sr_types=("aug", "max", "mean"), want_standard=True, prune=True, profile=None, keep_scores=False,
                          band_widths=None, band_ignore_label=255, confusion_labels=None, th_factors=None, guide=None,
-                         coverages=None, keep_uncertainty=False, min_region=None, tv_guide=None, crf=None, segments=None):
+                         coverages=None, keep_uncertainty=False, min_region=None, df_weights=None, tv_guide=None, crf=None,
+                         segments=None):
         """One label map per SR type from one forward pass: stage 1 and the solves are run_image_classes's; stage 2 ends in the
         fusion kernel (ops.fuse_labels) instead of K thresholds.  class_ids: K <= 32 distinct ids, none 0 (the label of "no
         class").  At each pixel the label is the class whose single-class mask is set there and whose SR output is greatest
@@ -398,8 +406,18 @@ class HotPath:
         threshold, so there is no unary), th_factors (the sweep counts the fusion rule's maps), more than 31 class ids (the CRF has
         at most 32 labels) and an image of another shape.
         With no class left after pruning the SR maps are 0 as before.  With crf=None nothing else is launched and every result is
-        what it was."""
+        what it was.
+
+        df_weights ("maxprob" or "margin"): a solver option -- each low-resolution pixel of each copy enters the "aug" solves'
+        data term (include/asr_hip.h, "data term"; the loss itself is the solver's df_loss) with the network's own confidence
+        there as its weight: the largest softmax entry of the copy's logits, or the difference of the two largest.  One
+        ops.opm_confidence call per forward batch, next to the OPM, fills an [N, fh, fw] stack; it is shared by the K classes'
+        solve and, in slice_max, by the max maps' solve, and it is neither pruned nor normalised (copy_dropout drops its
+        copies with the stacks').  The kernel always reads logits: from a model with a last_activation the batch's raw logits
+        are taken, not the probabilities it returns (with final_upsample as well there are none at the stacks' size: refused).  With df_weights=None, or without "aug" in sr_types, nothing else is launched and every
+        result is what it was."""
         ids = [int(c) for c in class_ids]
+        self.check_df_weights(df_weights)
         tv_beta = self.check_tv_guide(tv_guide, None if image_dev is None else tuple(image_dev.shape))
         crf_opts = self.check_crf(crf, None if image_dev is None else tuple(image_dev.shape), th_factors, len(ids))
         opts = self.label_options(None if image_dev is None else tuple(image_dev.shape), gt_dev is not None, band_widths,
@@ -422,7 +440,19 @@ class HotPath:
         def standard(logits0):
             ops.standard_labels(logits0, out_hw, ids, out=maps[0])
 
-        y, ymax = self._classes_stage_model(image_dev, angles, shifts, ids, profile, standard if want_standard else None)
+        conf = []                          # the copies' confidence stack [N, fh, fw], allocated from the first batch's logits
+
+        def confidence(preds, first, k, n):
+            if not conf:
+                conf.append(torch.empty((n,) + tuple(preds.shape[1:3]), dtype=torch.float32, device=preds.device))
+            # the confidence is taken from LOGITS: a model with a last_activation returns probabilities, and its raw logits
+            # are the plan's buffer of this batch (as model.logits_of takes them for the standard output)
+            activated = getattr(self.model, "last_activation", None) in ("softmax", "sigmoid")
+            logits = self.model._raw_logits[:k] if activated else preds
+            ops.opm_confidence(logits.contiguous(), df_weights, out=conf[0][first:first + k])
+
+        y, ymax = self._classes_stage_model(image_dev, angles, shifts, ids, profile, standard if want_standard else None,
+                                            confidence if df_weights is not None and "aug" in sr_types else None)
         kept = list(range(len(ids)))
         if prune and self.mode == "argmax":
             # raw argmax stacks hold ids[k] where the class wins and 0 elsewhere: a maximum of 0 is a class that never wins
@@ -456,7 +486,7 @@ class HotPath:
                 tv_weights = ops.tv_edge_weights(image_dev.to(torch.float32).contiguous(), tv_beta)
             if kept:
                 for t, tgt, tmax in self._classes_scores(y, ymax, angles, fshifts, [starts[k] for k in kept], sr_types,
-                                                         tv_weights):
+                                                         tv_weights, conf[0] if conf else None):
                     j = keys.index(t)
                     if g_state is not None:
                         ops.guided_apply(g_state, g_image, tgt, out=tgt)
@@ -502,6 +532,18 @@ class HotPath:
             res["uncertainty"] = u_map
             res["uncertainty_stacks"] = y if kept else None
         return res
+
+    def check_df_weights(self, df_weights):
+        """run_image_labels' df_weights, checked on the host before any launch: None, "maxprob" or "margin".  The confidence is
+        made from the logits behind each forward batch: a model that both activates and upsamples its output (last_activation
+        with final_upsample) keeps no logits at the size of the stacks and is refused."""
+        if df_weights is not None and (not isinstance(df_weights, str) or df_weights not in _lib.CONF_KINDS):
+            raise ValueError(f"df_weights must be None or one of {sorted(_lib.CONF_KINDS)}, got {df_weights!r}")
+        if (df_weights is not None and getattr(self.model, "last_activation", None) in ("softmax", "sigmoid")
+                and getattr(self.model, "final_upsample", False)):
+            raise ValueError("df_weights needs the logits at the size of the stacks: the model applies a last_activation after "
+                             "its final upsample (build it with final_upsample=False)")
+        return df_weights
 
     def check_tv_guide(self, tv_guide, image_shape):
         """run_image_labels' tv_guide, checked on the host before any launch: None, or beta as a float.  ValueError for a beta

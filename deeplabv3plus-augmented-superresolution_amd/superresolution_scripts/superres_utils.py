@@ -300,14 +300,18 @@ EXTRA_SR_TYPES = ("median", "trimmed_mean") + COVERED_SR_TYPES    # the ones bey
 
 def compute_SR(superresolution_obj, class_masks, angles, shifts, filename, dest_folder,
                SR_type="aug", max_masks=[], save_intermediate_output=False, save_final_output=False, class_id=8,
-               th_factor=0.15, tv_guide=None, guide=None, guide_radius=8, guide_eps=1e-3):
+               th_factor=0.15, df_weights=None, tv_guide=None, guide=None, guide_radius=8, guide_eps=1e-3):
     """Dispatch aug / mean / max / median / trimmed_mean / covered_mean / covered_median SR, then threshold to a {0, class_id} mask [H,W,1] (host int32).
     guide ([H, W, 3] at the output size, the RGB image in [0, 1]): the target (and in slice_max the max map's target) goes
     through guided_refine(., guide, guide_radius, guide_eps) before it is thresholded and saved; None: nothing changes.
     tv_guide (the same kind of image; "aug" only) goes INTO the solve instead: the edge weights of its TV prior
-    (Superresolution.augmented_superresolution(tv_guide=...)), for the class solve and the max map's.  The two are independent."""
+    (Superresolution.augmented_superresolution(tv_guide=...)), for the class solve and the max map's.  The two are independent.
+    df_weights (a device tensor [N, h, w]; "aug" only): the per-measurement weights of the solve's data term
+    (Superresolution.augmented_superresolution(df_weights=...)), again for both solves; the loss itself is the object's df_loss."""
     if SR_type not in SR_TYPES + COVERED_SR_TYPES:
         raise ValueError("SR_type must be one of " + ", ".join(repr(t) for t in SR_TYPES + COVERED_SR_TYPES))
+    if df_weights is not None and SR_type != "aug":
+        raise ValueError(f"df_weights weight the data term of the iterative solve: SR_type must be 'aug', got {SR_type!r}")
     if tv_guide is not None and SR_type != "aug":
         raise ValueError(f"tv_guide weights the TV prior of the iterative solve: SR_type must be 'aug', got {SR_type!r}")
     out_folder = os.path.join(dest_folder, f"{SR_type}_SR")
@@ -328,9 +332,10 @@ def compute_SR(superresolution_obj, class_masks, angles, shifts, filename, dest_
     else:
         SR_function = superresolution_obj.trimmed_mean_superresolution
 
-    if tv_guide is not None:
+    extra = {k: v for k, v in (("tv_guide", tv_guide), ("df_weights", df_weights)) if v is not None}
+    if extra:
         solve = SR_function
-        SR_function = lambda copies, a, s: solve(copies, a, s, tv_guide=tv_guide)
+        SR_function = lambda copies, a, s: solve(copies, a, s, **extra)
     target_image_class, _ = SR_function(class_masks, angles, shifts)
     if guide is not None:
         target_image_class = guided_refine(target_image_class, guide, guide_radius, guide_eps)

@@ -16,6 +16,10 @@ later iteration and image reuses it -- ``_drop_mask`` restates exactly that.
 ``tv_guide`` (not in the reference) puts the RGB image into the prior: the solves and ``loss_function`` take an image at
 ``output_size`` and weight every edge of the TV prior by 1 / (1 + tv_beta * |forward difference of the image|^2), so a jump
 of the solution is cheap across an image edge and costs full price elsewhere (include/asr_hip.h: the rule).
+
+``df_loss`` / ``df_delta`` (not in the reference, which carries the L1 line commented out) choose the data term sum w * rho(r):
+"l2", "l1" or "huber"; ``df_weights`` on the solves and ``loss_function`` are its per-measurement weights w, [N,h,w] or
+[B,N,h,w] on the device (include/asr_hip.h, "data term").  With "l2" and no weights the calls that ran before are made.
 """
 from __future__ import annotations
 
@@ -75,8 +79,14 @@ COVER_MODES = ("frame", "validity")
 class Superresolution:
     def __init__(self, lambda_df, lambda_tv, lambda_L2, lambda_L1, num_iter=200, num_aug=100,
                  optimizer: Optimizer = None, feature_size=(64, 64), output_size=(512, 512), use_BTV=False,
-                 verbose=False, copy_dropout=0.0, trim=0.1, cover="frame", cov_min=0.5, valid_min=0.5, tv_beta=100.0):
+                 verbose=False, copy_dropout=0.0, trim=0.1, cover="frame", cov_min=0.5, valid_min=0.5, tv_beta=100.0,
+                 df_loss="l2", df_delta=0.1):
         self.tv_beta = ops.check_tv_beta(tv_beta, "Superresolution: tv_beta")
+        # the data term sum w * rho(r): "l2" (the reference's), "l1" or "huber" with threshold df_delta, in the units of the
+        # stacks (the path normalises them to [0, 1]); the weights w come per solve (df_weights=)
+        ops.check_data_term(df_loss, df_delta, "Superresolution: df_loss")
+        self.df_loss = "l2" if df_loss is None else df_loss.lower()
+        self.df_delta = float(df_delta) if self.df_loss == "huber" else df_delta
         if not 0.0 <= float(trim) < 0.5:
             raise ValueError(f"trim must be in [0, 0.5), got {trim}")
         if cover not in COVER_MODES:
@@ -165,6 +175,32 @@ class Superresolution:
             raise ValueError(f"tv_guide holds {g.shape[0]} images, the solve {batch}")
         return ops.tv_edge_weights(g, self.tv_beta)
 
+    def _data_term(self):
+        """The data_term argument of the ops calls: None for the reference's L2 (the calls that ran before data terms existed)."""
+        return None if self.df_loss == "l2" else (self.df_loss, self.df_delta)
+
+    def _check_df_weights(self, df_weights):
+        """Host check of a df_weights argument, before anything touches the device: None, or a float32 tensor [N,h,w] (shared
+        by the images / classes of the solve) or [B,N,h,w] at feature_size (ops checks N and B against the solve's)."""
+        if df_weights is None:
+            return
+        if not isinstance(df_weights, torch.Tensor) or df_weights.dtype != torch.float32 or df_weights.dim() not in (3, 4) \
+                or tuple(df_weights.shape[-2:]) != self.feature_size:
+            got = tuple(df_weights.shape) if hasattr(df_weights, "shape") else type(df_weights).__name__
+            raise ValueError(f"df_weights must be a float32 tensor [N,h,w] or [B,N,h,w] at feature_size {self.feature_size}, "
+                             f"got {got}")
+
+    def _masked_weights(self, df_weights, mask, dev):
+        """df_weights (checked) on the device of the solve, without the copies that copy_dropout's mask drops (None: all)."""
+        if df_weights is None:
+            return None
+        wts = df_weights.to(dev)
+        if mask is not None:
+            if wts.shape[-3] != len(mask):
+                raise ValueError(f"copy_dropout needs weights for num_aug={len(mask)} copies, got {tuple(wts.shape)}")
+            wts = wts.index_select(wts.dim() - 3, torch.as_tensor(np.flatnonzero(mask), device=dev))
+        return wts.contiguous()
+
     @staticmethod
     def _batchify(angles, shifts):
         a = np.asarray(angles, dtype=np.float32)
@@ -172,20 +208,27 @@ class Superresolution:
         return (a[None], s[None]) if a.ndim == 1 else (a, s)
 
     # -- superresolution.py:44-100 ------------------------------------------------------------------
-    def loss_function(self, target_image, augmented_samples, angles, shifts, n_drop=0, tv_guide=None):
+    def loss_function(self, target_image, augmented_samples, angles, shifts, n_drop=0, tv_guide=None, df_weights=None):
         self._check_tv_guide(tv_guide)
+        self._check_df_weights(df_weights)
         dev = _lib.require_gpu()
         y = _stack_copies(augmented_samples, dev)[None]
         a, s = self._batchify(angles, shifts)
         if n_drop != 0:
             keep = torch.as_tensor(self._drop_mask(n_drop), device=dev)
             y, a, s = y[:, keep].contiguous(), a[:, self._drop_mask(n_drop)], s[:, self._drop_mask(n_drop)]
+        wts = self._masked_weights(df_weights, self._drop_mask(n_drop) if n_drop != 0 else None, dev)
         x = torch.as_tensor(np.asarray(target_image.cpu() if isinstance(target_image, torch.Tensor) else target_image,
                                        dtype=np.float32)).to(dev).reshape(1, *self.output_size).contiguous()
         rot, tr = self._transforms(a, s, dev)
-        resid = ops.sr_forward_residual(x, y, rot, tr)
         tvw = self._tv_weights(tv_guide, 1, dev)
-        return self._loss_from_terms(ops.sr_loss_terms(x, resid, self._config(), tv_weights=tvw).cpu().numpy()[0])
+        dt = self._data_term()
+        if dt is None and wts is None:
+            resid = ops.sr_forward_residual(x, y, rot, tr)
+            return self._loss_from_terms(ops.sr_loss_terms(x, resid, self._config(), tv_weights=tvw).cpu().numpy()[0])
+        _, raw = ops.sr_forward_residual(x, y, rot, tr, data_term=dt, weights=wts, want_raw=True)
+        terms = ops.sr_loss_terms(x, raw, self._config(), tv_weights=tvw, data_term=dt, weights=wts)
+        return self._loss_from_terms(terms.cpu().numpy()[0])
 
     def _loss_from_terms(self, t):
         f = np.float32
@@ -196,22 +239,26 @@ class Superresolution:
         return float(loss)
 
     # -- superresolution.py:102-137 -------------------------------------------------------------------
-    def augmented_superresolution_batch(self, copies, angles, shifts, tv_guide=None):
+    def augmented_superresolution_batch(self, copies, angles, shifts, tv_guide=None, df_weights=None):
         """copies [B,N,h,w] device tensor, angles [B,N], shifts [B,N,2] -> (device [B,H,W], [B] losses).
         The global Adam step counter advances image by image (reference order), the device then
-        iterates all images together.  tv_guide: one RGB image [H,W,3] shared by the batch or [B,H,W,3] (_check_tv_guide)."""
+        iterates all images together.  tv_guide: one RGB image [H,W,3] shared by the batch or [B,H,W,3] (_check_tv_guide).
+        df_weights: the weights of the data term, a device tensor [N,h,w] shared by the batch or [B,N,h,w] (_check_df_weights)."""
         self._check_tv_guide(tv_guide)
+        self._check_df_weights(df_weights)
         return self._solve_batch(copies, angles, shifts,
                                  lambda b: np.stack([self.optimizer.schedule_alphas(self.num_iter) for _ in range(b)], axis=1),
-                                 tv_guide)
+                                 tv_guide, df_weights)
 
-    def augmented_superresolution_classes(self, copies, angles, shifts, start_steps, tv_guide=None):
+    def augmented_superresolution_classes(self, copies, angles, shifts, start_steps, tv_guide=None, df_weights=None):
         """The copies of K classes of ONE image in one batched solve: copies [K,N,h,w] device tensor, angles [N], shifts [N,2]
         (the image's transforms, repeated for every class), start_steps [K] -> (device [K,H,W], [K] losses).  Class k's
         step scalars are those of a solve that starts at the global step counter start_steps[k]; the counter itself is left
         as it was (the caller decides what the classes' solves count as).  copy_dropout uses the object's frozen mask.
-        tv_guide: the image's RGB [H,W,3], or its edge weights (wy, wx) [H,W], shared by the K classes."""
+        tv_guide: the image's RGB [H,W,3], or its edge weights (wy, wx) [H,W], shared by the K classes.
+        df_weights: the weights of the data term, [N,h,w] shared by the K classes (or [K,N,h,w])."""
         self._check_tv_guide(tv_guide)
+        self._check_df_weights(df_weights)
         if self.optimizer is None:
             raise Exception("You must provide an instance of the Optimizer class to compute the augmented SR")
         k = copies.shape[0]
@@ -229,9 +276,10 @@ class Superresolution:
             state.iterations = saved
         a = np.repeat(np.asarray(angles, dtype=np.float32)[None], k, axis=0)
         s = np.repeat(np.asarray(shifts, dtype=np.float32)[None], k, axis=0)
-        return self._solve_batch(copies, a, s, lambda b: np.stack(columns, axis=1).reshape(self.num_iter, b), tv_guide)
+        return self._solve_batch(copies, a, s, lambda b: np.stack(columns, axis=1).reshape(self.num_iter, b), tv_guide,
+                                 df_weights)
 
-    def _solve_batch(self, copies, angles, shifts, make_alphas, tv_guide=None):
+    def _solve_batch(self, copies, angles, shifts, make_alphas, tv_guide=None, df_weights=None):
         """The batched solve; make_alphas(B) -> float32 [num_iter, B] step scalars."""
         if self.optimizer is None:
             raise Exception("You must provide an instance of the Optimizer class to compute the augmented SR")
@@ -241,12 +289,14 @@ class Superresolution:
             raise ValueError(f"copies are {h}x{w} but feature_size is {self.feature_size}")
         x = ops.sr_init_target(copies, self.output_size)          # from copy 0 of the FULL stack (superresolution.py:112-114)
         n_drop = int(self.num_aug * self.copy_dropout)
+        mask = None
         if n_drop != 0:
             if n != self.num_aug:
                 raise ValueError(f"copy_dropout needs num_aug={self.num_aug} copies per image, got {n}")
             mask = self._drop_mask(n_drop)
             copies = copies[:, torch.as_tensor(mask, device=dev)].contiguous()
             angles, shifts = np.asarray(angles)[:, mask], np.asarray(shifts)[:, mask]
+        wts = self._masked_weights(df_weights, mask, dev)      # copy_dropout masks the weights with the copies
         rot, tr = self._transforms(angles, shifts, dev)
         irot, itr = self._transforms(angles, shifts, dev, inverse=True)
         alphas = make_alphas(b)                                                                # [iter, B]
@@ -257,6 +307,8 @@ class Superresolution:
         kw = dict(want_loss=True, cfg=state.config(use_btv=self.use_BTV), slot_init=state.slot_init)
         if tv_guide is not None:
             kw["tv_weights"] = self._tv_weights(tv_guide, b, dev)
+        if self._data_term() is not None or wts is not None:
+            kw.update(data_term=self._data_term(), weights=wts)
         if not self.verbose:
             return ops.sr_solve(x, copies, rot, tr, irot, itr, alphas_dev, self._lambdas, **kw)
         # superresolution.py:130-131 prints the loss of iteration i (evaluated before that iteration's update) for
@@ -273,15 +325,16 @@ class Superresolution:
                     print(f"{tag}{i + 1}/{self.num_iter} -- loss = {self._loss_from_terms(t)}")
         return x, terms
 
-    def augmented_superresolution(self, augmented_copies, angles, shifts, tv_guide=None):
+    def augmented_superresolution(self, augmented_copies, angles, shifts, tv_guide=None, df_weights=None):
         self._check_tv_guide(tv_guide)
+        self._check_df_weights(df_weights)
         if self.optimizer is None:
             raise Exception(
                 "You must provide an instance of the Optimizer class to compute the augmented SR")
         dev = _lib.require_gpu()
         y = _stack_copies(augmented_copies, dev)[None]
         a, s = self._batchify(angles, shifts)
-        x, terms = self.augmented_superresolution_batch(y, a, s, tv_guide=tv_guide)
+        x, terms = self.augmented_superresolution_batch(y, a, s, tv_guide=tv_guide, df_weights=df_weights)
         loss = self._loss_from_terms(terms.cpu().numpy()[0]) if isinstance(terms, torch.Tensor) else None
         return x[0].cpu().numpy()[..., None], loss
 

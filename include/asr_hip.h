@@ -221,6 +221,66 @@ int asr_sr_solve_wtv_f32(float* x, const float* y, const float* rot_tf, const fl
                          int h, int w, float lambda_df, float lambda_tv, float lambda_l2, float lambda_l1,
                          const asr_sr_config* cfg, const float* wy, const float* wx, int w_shared, asr_stream_t stream);
 
+/* --- data term: L1, Huber and per-measurement weights -----------------------------------------------------------
+ * The solver's data term above is sum (D(T(R(x))) - y)^2: every low-resolution pixel of every copy counts the same and a
+ * copy on which the network failed pulls with the square of its error.  The *_dt entry points minimise sum w * rho(r)
+ * instead (the reference carries the L1 form commented out, superresolution.py:73).  The rule, for the residual
+ * r = D(T(R(x))) - y in float32, exactly what asr_sr_forward_residual_f32 writes:
+ *
+ *   loss                          rho(r)                                          psi(r) = rho'(r) / 2
+ *   ASR_DF_L2                     r*r                                             r
+ *   ASR_DF_L1                     |r|                                             r > 0 ? 0.5f : (r < 0 ? -0.5f : +0.0f)
+ *   ASR_DF_HUBER, delta in (0,inf) |r| <= delta ? r*r : delta*(2|r| - delta)      r < -delta ? -delta : (r > delta ? delta : r)
+ *
+ *   q = w * psi(r), ONE float32 multiply, left out entirely without weights (w = 1 gives the same bits).  The forward kernel
+ *   writes q where it wrote r, and every backward kernel reads that buffer as before, as (2*lambda_df * q) * 0.25f: no backward
+ *   kernel knows about the data term, and one explicit step feeds q to asr_sr_backward_cfg_f32 / _wtv_f32 as `resid`.  Under L1
+ *   the data gradient is that of lambda_df * |r| (2*lambda_df and 0.5 are exact in float32): TF's own gradient of the
+ *   commented-out line.  Huber with delta >= max |r| is L2 bit for bit; so is a weight plane of all ones; a copy whose weights
+ *   are all zero adds +-0 to every sum it enters.  A NaN residual stays NaN under L2 and Huber and gives psi = +0 under L1.
+ *   Weights: any finite values >= 0 (not checked), [batch, n, h, w], or [n, h, w] shared by the batch (weights_shared != 0: the
+ *   K classes of one image); NULL: unweighted.
+ *   terms[b][0] = sum w * rho(r) over the RAW residual: each term in float32, one operation per statement as written above
+ *   (then the weight), the accumulation in float64.  The other three terms do not change.
+ *   wy, wx: both NULL for the plain TV or bilateral-TV prior of cfg, or the edge weights of the *_wtv calls (tv_shared as
+ *   their w_shared).  Refusals, before any launch, outputs untouched: every refusal of the *_cfg / *_wtv twin; dt NULL, an
+ *   unknown loss, Huber with delta not finite or <= 0, one of wy / wx NULL, weights with n, h or w <= 0 -> ASR_ERR_INVALID_ARG. */
+#define ASR_DF_L2 0
+#define ASR_DF_L1 1
+#define ASR_DF_HUBER 2
+
+typedef struct asr_sr_data_term {
+    int loss;              /* ASR_DF_* */
+    float delta;           /* Huber's threshold, in the units of y; read under ASR_DF_HUBER only */
+    const float* weights;  /* device; NULL = unweighted */
+    int weights_shared;    /* != 0: weights are [n, h, w], the same for every image of the batch */
+    const float* wy;       /* edge-weighted TV planes (device), or both NULL */
+    const float* wx;
+    int tv_shared;         /* != 0: wy, wx are [H, W], shared by the batch */
+} asr_sr_data_term;
+
+/* asr_sr_forward_residual_f32 under a data term: q_out = w * psi(r) and, with r_out != NULL, the raw r as well. */
+int asr_sr_forward_residual_dt_f32(const float* x, const float* y, const float* rot_tf, const float* trans_tf, float* q_out,
+                                   float* r_out, int batch, int n, int H, int W, int h, int w, const asr_sr_data_term* dt,
+                                   asr_stream_t stream);
+
+/* asr_sr_loss_terms_cfg_f64 / _wtv_f64 with terms[b][0] = sum w * rho(r); r is the RAW residual (r_out above), not q. */
+int asr_sr_loss_terms_dt_f64(const float* x, const float* r, double* terms, int batch, int n, int H, int W, int h, int w,
+                             const asr_sr_config* cfg, const asr_sr_data_term* dt, asr_stream_t stream);
+
+/* Workspace of asr_sr_solve_dt_f32: that of asr_sr_solve_workspace_bytes_cfg plus one more [batch, n, h, w] buffer (the raw
+ * residual of the last iteration, for last_loss_terms). */
+size_t asr_sr_solve_workspace_bytes_dt(int batch, int n, int H, int W, int h, int w, const asr_sr_config* cfg);
+
+/* asr_sr_solve_cfg_f32 / _wtv_f32 under a data term.  The same launches per iteration: the forward kernel's data-term
+ * instantiation in place of the plain one, the raw residual a second output of the last iteration's launch when
+ * last_loss_terms is asked for.  {ASR_DF_L2, no weights} gives asr_sr_solve_cfg_f32's results bit for bit. */
+int asr_sr_solve_dt_f32(float* x, const float* y, const float* rot_tf, const float* trans_tf, const float* inv_rot_tf,
+                        const float* inv_trans_tf, float* m, float* v, float* vhat, const float* alphas, int num_iter,
+                        double* last_loss_terms, void* workspace, size_t workspace_bytes, int batch, int n, int H, int W,
+                        int h, int w, float lambda_df, float lambda_tv, float lambda_l2, float lambda_l1,
+                        const asr_sr_config* cfg, const asr_sr_data_term* dt, asr_stream_t stream);
+
 /* out[b] = max / mean over copies of rotate(translate(resize(y[b,i], (H,W)), trans_tf), rot_tf)
  * -- max_superresolution / mean_superresolution, superresolution.py:139-161 (trans_tf built
  * from -shifts, rot_tf from -angles).  out [batch,H,W]; (H, W) need not be a multiple of (h, w).  The maximum runs
@@ -327,6 +387,17 @@ int asr_minmax_f32(const float* x, float* out_minmax, int64_t per_segment, int s
  * out may alias logits. */
 int asr_class_activation_f32(const float* logits, float* out, int64_t pixels, int classes, int kind,
                              asr_stream_t stream);
+
+/* The network's confidence per pixel from the logits rows [pixels, classes] -> out [pixels]: the weights of the SR solver's
+ * data term (asr_sr_data_term).  With max = the row's largest logit and sum = the float32 sum, in class order, of
+ * expf(z_c - max):
+ *   ASR_CONF_MAXPROB  1.0f / sum: the largest entry of asr_class_activation_f32's softmax, bit for bit;
+ *   ASR_CONF_MARGIN   that value minus expf(z_second - max) / sum, z_second the second largest logit counted with multiplicity:
+ *                     the difference of the two largest softmax entries; a tie for the maximum gives 0, one class gives 1.
+ * Refusals before any launch: null pointers, pixels or classes <= 0, an unknown kind -> ASR_ERR_INVALID_ARG. */
+#define ASR_CONF_MAXPROB 1
+#define ASR_CONF_MARGIN 2
+int asr_opm_confidence_f32(const float* logits, float* out, int64_t pixels, int classes, int kind, asr_stream_t stream);
 
 /* create_mask: argmax over the class axis, first maximum wins (utils.py:115-119). */
 int asr_argmax_i32(const float* logits, int32_t* out, int64_t pixels, int classes, asr_stream_t stream);

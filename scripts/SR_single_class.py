@@ -33,7 +33,14 @@ def main():
     ap.add_argument("--cover", choices=["frame", "validity"], default="frame", help="what the covered fusions count as "
                     "seen: the output frame only, or also the part of each copy that came from inside the image")
     ap.add_argument("--trim", type=float, default=0.1, help="fraction of the copies the trimmed mean drops at each end")
+    ap.add_argument("--df_loss", choices=["l2", "l1", "huber"], default="l2", help="data term of the iterative solve: l2 (the reference's), l1, or huber with threshold --df_delta")
+    ap.add_argument("--df_delta", type=float, default=0.1, help="Huber threshold, in units of the stacks (normalised to [0, 1]); finite, > 0")
     args = ap.parse_args()
+    from asr_amd.ops import check_data_term
+    try:
+        check_data_term(args.df_loss, args.df_delta, "--df_loss/--df_delta")
+    except ValueError as e:
+        ap.error(str(e))
     extra = tuple(t for t in args.extra_sr_types.split(",") if t)
     out_dir = args.out or os.path.join(ROOT, "data", "superres_root", "superres_output")
 
@@ -51,7 +58,7 @@ def main():
     sr = Superresolution(lambda_df=HYPER["lambda_df"], lambda_tv=HYPER["lambda_tv"], lambda_L2=HYPER["lambda_L2"],
                          lambda_L1=HYPER["lambda_L1"], num_iter=HYPER["num_iter"], num_aug=args.num_aug,
                          optimizer=optimizer_obj, feature_size=(args.feature_size, args.feature_size), trim=args.trim,
-                         cover=args.cover)
+                         cover=args.cover, df_loss=args.df_loss, df_delta=args.df_delta)
     paths = interchange_files(args.data)[:args.num_samples]
     res = evaluate_precomputed(sr, paths, args.gt, args.standard, num_aug=args.num_aug, class_id=args.class_id,
                                th_factor=args.th_factor, img_size=IMG_SIZE, out_dir=out_dir, rank=rank, world=world,

@@ -35,6 +35,8 @@ parser.add_argument("--backbone", type=str, choices=["mobilenet", "xception"], d
 parser.add_argument("--weights", default=None, help="local Keras .h5 checkpoint or .npz of Keras weights")
 parser.add_argument("--th_factor", type=float, default=0.65)
 parser.add_argument("--num_iter", type=int, default=300)
+parser.add_argument("--df_loss", choices=["l2", "l1", "huber"], default="l2", help="data term of the iterative solve: l2 (the reference's), l1, or huber with threshold --df_delta")
+parser.add_argument("--df_delta", type=float, default=0.1, help="Huber threshold, in units of the stacks (normalised to [0, 1]); finite, > 0")
 parser.add_argument("--class_ids", type=int, nargs="+", default=list(range(1, 21)),
                     help="classes to evaluate (0 and 255 never count)")
 parser.add_argument("--out", default=os.path.join(ROOT, "data", "superres_root", "class_validation.csv"),
@@ -43,6 +45,11 @@ parser.add_argument("--out", default=os.path.join(ROOT, "data", "superres_root",
 
 def main():
     args = parser.parse_args()
+    from asr_amd.ops import check_data_term
+    try:
+        check_data_term(args.df_loss, args.df_delta, "--df_loss/--df_delta")
+    except ValueError as e:
+        parser.error(str(e))
     import torch
     from asr_amd import distributed as D
     from asr_amd.evaluation import class_rows, evaluate_classes, write_class_csv
@@ -64,7 +71,7 @@ def main():
                     lr_scheduler=HYPER["lr_scheduler"], decay_steps=HYPER["decay_steps"], decay_rate=HYPER["decay_rate"])
     sr = Superresolution(lambda_df=HYPER["lambda_df"], lambda_tv=HYPER["lambda_tv"], lambda_L2=HYPER["lambda_L2"],
                          lambda_L1=HYPER["lambda_L1"], num_iter=args.num_iter, num_aug=args.num_aug, optimizer=opt,
-                         feature_size=(feat, feat), output_size=IMG_SIZE)
+                         feature_size=(feat, feat), output_size=IMG_SIZE, df_loss=args.df_loss, df_delta=args.df_delta)
     path = HotPath(model, sr, mode=args.mode, th_factor=args.th_factor, batch_size=BATCH_SIZE)
     table, presence = evaluate_classes(path, paths, gts, class_ids, num_aug=args.num_aug, angle_max=args.angle_max,
                                        shift_max=args.shift_max, img_size=IMG_SIZE, rank=rank, world=world, seed=SEED)

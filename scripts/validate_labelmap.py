@@ -113,6 +113,10 @@ parser.add_argument("--guide_radius", type=int, default=None,
 parser.add_argument("--guide_eps", type=float, default=None, help="the guided filter's regulariser (default 1e-3)")
 parser.add_argument("--tv_guide_beta", type=float, default=None,
                     help="weight the solver's TV prior by the image's edges with this beta (finite, >= 0; e.g. 100)")
+parser.add_argument("--df_loss", choices=["l2", "l1", "huber"], default="l2", help="data term of the iterative solve: l2 (the reference's), l1, or huber with threshold --df_delta")
+parser.add_argument("--df_delta", type=float, default=0.1, help="Huber threshold, in units of the stacks (normalised to [0, 1]); finite, > 0")
+parser.add_argument("--df_weights", choices=["maxprob", "margin"], default=None,
+                    help="weight every measurement of the solve's data term by the network's confidence there")
 parser.add_argument("--crf_iters", type=int, default=None,
                     help="decide the SR label maps with the windowed CRF of this many mean-field iterations (0..32)")
 parser.add_argument("--crf_radius", type=int, default=None, help="the CRF's window radius (1..7, default 3)")
@@ -148,7 +152,7 @@ def main():
                                     write_confusion_csv, write_confusion_metrics_csv, write_labelmap_csv,
                                     write_coverage_csv, write_labelmap_threshold_csv, write_regions_csv, write_segments_csv,
                                     write_trimap_csv)
-    from asr_amd.ops import check_coverages, check_crf, check_min_region, check_segments, check_tv_beta
+    from asr_amd.ops import check_coverages, check_crf, check_data_term, check_min_region, check_segments, check_tv_beta
     from asr_amd.model import DeeplabV3Plus
     from asr_amd.pipeline import HotPath
     from asr_amd.superresolution_scripts.optimizer import Optimizer
@@ -209,6 +213,10 @@ def main():
             check_tv_beta(args.tv_guide_beta, "--tv_guide_beta")
         except ValueError as e:
             parser.error(str(e))
+    try:
+        check_data_term(args.df_loss, args.df_delta, "--df_loss/--df_delta")
+    except ValueError as e:
+        parser.error(str(e))
     crf_flags = {"radius": args.crf_radius, "dilation": args.crf_dilation, "w_app": args.crf_w_app, "w_smooth": args.crf_w_smooth,
                  "theta_pos": args.crf_theta_pos, "theta_rgb": args.crf_theta_rgb, "theta_smooth": args.crf_theta_smooth,
                  "tau": args.crf_tau, "standard_conf": args.crf_standard_conf}
@@ -254,7 +262,7 @@ def main():
                     lr_scheduler=HYPER["lr_scheduler"], decay_steps=HYPER["decay_steps"], decay_rate=HYPER["decay_rate"])
     sr = Superresolution(lambda_df=HYPER["lambda_df"], lambda_tv=HYPER["lambda_tv"], lambda_L2=HYPER["lambda_L2"],
                          lambda_L1=HYPER["lambda_L1"], num_iter=args.num_iter, num_aug=args.num_aug, optimizer=opt,
-                         feature_size=(feat, feat), output_size=IMG_SIZE)
+                         feature_size=(feat, feat), output_size=IMG_SIZE, df_loss=args.df_loss, df_delta=args.df_delta)
     path = HotPath(model, sr, mode=args.mode, th_factor=args.th_factor, batch_size=BATCH_SIZE)
     out = evaluate_labelmaps(path, paths, gts, class_ids, num_aug=args.num_aug, angle_max=args.angle_max,
                              shift_max=args.shift_max, img_size=IMG_SIZE, rank=rank, world=world, seed=SEED,
@@ -263,6 +271,7 @@ def main():
                              **(dict(th_factors=factors) if factors is not None else {}),
                              **(dict(guide=guide) if guide is not None else {}),
                              **(dict(tv_guide=args.tv_guide_beta) if args.tv_guide_beta is not None else {}),
+                             **(dict(df_weights=args.df_weights) if args.df_weights is not None else {}),
                              **(dict(crf=crf) if crf is not None else {}),
                              **(dict(coverages=covs, uncertainty_dir=args.uncertainty_dir) if covs is not None else {}),
                              **(dict(min_region=min_region) if min_region is not None else {}),
