@@ -64,6 +64,12 @@ class SrDataTerm(C.Structure):
                 ("wy", C.c_void_p), ("wx", C.c_void_p), ("tv_shared", C.c_int)]
 
 
+class SrMonitor(C.Structure):
+    """struct asr_sr_monitor (include/asr_hip.h): evaluation stride, stop rule and outputs of asr_sr_solve_mon_f32."""
+    _fields_ = [("every", C.c_int), ("rel_tol", C.c_double), ("patience", C.c_int), ("min_iter", C.c_int),
+                ("history", C.c_void_p), ("iters_done", C.c_void_p)]
+
+
 class CrfConfig(C.Structure):
     """struct asr_crf_config (include/asr_hip.h): window, iterations and kernels of asr_crf_refine_f32."""
     _fields_ = [("radius", C.c_int), ("dilation", C.c_int), ("iterations", C.c_int), ("w_app", C.c_float),
@@ -74,6 +80,7 @@ MAX_CRF_RADIUS, MAX_CRF_HALO, MAX_CRF_ITERATIONS, MAX_CRF_LABELS = 7, 16, 32, 32
 _cfg = C.POINTER(SrConfig)
 _crf = C.POINTER(CrfConfig)
 _dt = C.POINTER(SrDataTerm)
+_mon = C.POINTER(SrMonitor)
 ABI_VERSION = 3          # ASR_ABI_VERSION of include/asr_hip.h this table mirrors
 
 # name -> (restype, argtypes).  Order and types mirror include/asr_hip.h exactly.
@@ -102,6 +109,8 @@ SIGNATURES = {
     "asr_sr_loss_terms_dt_f64": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _cfg, _dt, _vp]),
     "asr_sr_solve_workspace_bytes_dt": (_sz, [_i] * 6 + [_cfg]),
     "asr_sr_solve_dt_f32": (_i, [_vp] * 10 + [_i, _vp, _vp, _sz] + [_i] * 6 + [_fl] * 4 + [_cfg, _dt, _vp]),
+    "asr_sr_solve_workspace_bytes_mon": (_sz, [_i] * 6 + [_cfg]),
+    "asr_sr_solve_mon_f32": (_i, [_vp] * 10 + [_i, _vp, _vp, _sz] + [_i] * 6 + [_fl] * 4 + [_cfg, _dt, _mon, _vp]),
     "asr_realign_max_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "asr_realign_mean_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "asr_realign_max_mean_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),

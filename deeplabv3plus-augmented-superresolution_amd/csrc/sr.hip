@@ -160,10 +160,20 @@ __device__ __forceinline__ float sr_dt_psi(float r, int loss, float delta) {
     return r;
 }
 
-template <bool BORDERED, bool DT = false>
+// MON: the monitored solve (asr_sr_solve_mon_f32; include/asr_hip.h, "convergence monitor").  The MON = false instantiations
+// take an empty argument and are the kernels they always were; in the MON = true ones the workgroups of an image whose
+// stop flag is set return at once (the flag is uniform over a workgroup: one scalar load and branch).
+template <bool MON>
+struct SrMonArg {};
+template <>
+struct SrMonArg<true> {
+    const int* stopped;       // [batch]: != 0 once the stop rule has frozen the image (sr_mon_decide_kernel)
+};
+
+template <bool BORDERED, bool DT = false, bool MON = false>
 __global__ __launch_bounds__(256) ASR_KFWD_ATTR void sr_forward_residual_kernel(
     const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ rot_tf,
-    const float* __restrict__ trans_tf, float* __restrict__ resid, SrDims d, SrDtArg<DT> dt) {
+    const float* __restrict__ trans_tf, float* __restrict__ resid, SrDims d, SrDtArg<DT> dt, SrMonArg<MON> mon) {
 #ifdef ASR_DIAG_KFWD_TOP_VGPR
     ASR_DIAG_TOUCH_VGPR(ASR_DIAG_KFWD_TOP_VGPR);
 #endif
@@ -172,6 +182,9 @@ __global__ __launch_bounds__(256) ASR_KFWD_ATTR void sr_forward_residual_kernel(
     const int bn = blockIdx.z;  // b * n + copy
     if (j >= d.w || i >= d.h) return;
     const int b = bn / d.n;
+    if constexpr (MON) {
+        if (mon.stopped[b]) return;
+    }
     const int H = d.H, W = d.W, WP = W + 2 * kGrPadX;
     const float* img = BORDERED ? x + (size_t)b * sr_gr_plane_elems(H, W) : x + (int64_t)b * H * W;
     const AsrTf8 tr = asr_load_tf(rot_tf + (int64_t)bn * 8);
@@ -505,13 +518,16 @@ constexpr int kGrRows = 16;   // HR rows per wave of sr_grad_translate_kernel
 // are computed by lanes 0..kGrRows-1 in ONE pass and fetched per row with v_readlane (they are wave-uniform: scalar row
 // pointers, scalar validity branches).  The x blend of an LR row, h(L) = wl * G(L, l0) + wh * G(L, l1), serves the up
 // to 4 HR rows that tap L: a two-entry cache keyed by the (uniform) LR row index keeps the last two.
-template <int LOG2F>
+template <int LOG2F, bool MON = false>
 __global__ __launch_bounds__(256) void sr_grad_translate_kernel(const float* __restrict__ resid,
                                                                 const float* __restrict__ inv_trans_tf,
                                                                 float* __restrict__ gr_out, SrDims d, float two_lambda_df,
-                                                                int n0, int cn) {
+                                                                int n0, int cn, SrMonArg<MON> mon) {
     // blockIdx.z = b * cn + local: copy n0 + local of image b, written to plane slot blockIdx.z of the chunk's planes
     const int slot = blockIdx.z;
+    if constexpr (MON) {
+        if (mon.stopped[slot / cn]) return;      // a frozen image: its planes are never read again
+    }
     const int bn = (slot / cn) * d.n + n0 + (slot % cn);
     const int lane = threadIdx.x;
     const int cx = blockIdx.x * 64 + lane;
@@ -740,18 +756,29 @@ __global__ __launch_bounds__(64) void sr_affine_flags_kernel(const float* __rest
 // it): the running sum of the data-term gradient crosses the launches through `acc` [batch, H, W] as a float32 -- the same
 // sequence of float32 additions, in copy order, as one pass over all copies, so the result does not depend on the chunking.
 // The last chunk adds the priors and applies the update.
-template <bool WTV>
+// MON: a frozen image's workgroups carry x over to the other ping-pong buffer (in the chunk that would have applied the update)
+// and touch nothing else -- not m, v, vhat, the bordered copy (it already holds this x) or acc.
+template <bool WTV, bool MON = false>
 __global__ __launch_bounds__(256) void sr_backward_gather_kernel(
     const float* __restrict__ x, float* __restrict__ x_new, const float* __restrict__ gr_planes,
     const float* __restrict__ inv_rot_tf, float* __restrict__ m, float* __restrict__ v, float* __restrict__ vhat,
     const float* __restrict__ alphas, float* __restrict__ grad_out, SrDims d, float lambda_tv, float two_lambda_l2,
     float lambda_l1, SrStep st, float* __restrict__ x_bordered_out, float* __restrict__ acc, int n0, int cn,
-    const int* __restrict__ affine_flags, SrTvW tw) {
+    const int* __restrict__ affine_flags, SrTvW tw, SrMonArg<MON> mon) {
     const int X = blockIdx.x * 64 + threadIdx.x;
     const int Y = blockIdx.y * 4 + threadIdx.y;
     const int b = blockIdx.z;
     const int H = d.H, W = d.W, WP = W + 2 * kGrPadX;
     if (X >= W || Y >= H) return;
+    if constexpr (MON) {
+        if (mon.stopped[b]) {
+            if (n0 + cn >= d.n) {
+                const int64_t oo = ((int64_t)b * H + Y) * W + X;
+                x_new[oo] = x[oo];
+            }
+            return;
+        }
+    }
     const size_t plane = sr_gr_plane_elems(H, W);
     const float* const planes = gr_planes + (size_t)b * cn * plane;
     const float* const tfs = inv_rot_tf + ((int64_t)b * d.n + n0) * 8;
@@ -785,13 +812,22 @@ SrBwdKernel sr_backward_kernel_of(int f) {
 }
 SrBwdKernel sr_backward_kernel_for(int f, bool wtv) { return wtv ? sr_backward_kernel_of<true>(f) : sr_backward_kernel_of<false>(f); }
 
-typedef void (*SrGradTranslateKernel)(const float*, const float*, float*, SrDims, float, int, int);
+typedef void (*SrGradTranslateKernel)(const float*, const float*, float*, SrDims, float, int, int, SrMonArg<false>);
 SrGradTranslateKernel sr_grad_translate_kernel_for(int f) {
     switch (f) {
         case 2: return sr_grad_translate_kernel<1>;
         case 4: return sr_grad_translate_kernel<2>;
         case 8: return sr_grad_translate_kernel<3>;
         default: return sr_grad_translate_kernel<0>;
+    }
+}
+typedef void (*SrGradTranslateMonKernel)(const float*, const float*, float*, SrDims, float, int, int, SrMonArg<true>);
+SrGradTranslateMonKernel sr_grad_translate_mon_kernel_for(int f) {
+    switch (f) {
+        case 2: return sr_grad_translate_kernel<1, true>;
+        case 4: return sr_grad_translate_kernel<2, true>;
+        case 8: return sr_grad_translate_kernel<3, true>;
+        default: return sr_grad_translate_kernel<0, true>;
     }
 }
 
@@ -1347,7 +1383,7 @@ extern "C" int asr_sr_forward_residual_f32(const float* x, const float* y, const
     int rc = check_dims("asr_sr_forward_residual_f32", batch, n, H, W, h, w, &d);
     if (rc != ASR_OK) return rc;
     hipLaunchKernelGGL(sr_forward_residual_kernel<false>, lr_grid(d), kBlock, 0, asr_stream(stream), x, y, rot_tf, trans_tf,
-                       resid, d, SrDtArg<false>{});
+                       resid, d, SrDtArg<false>{}, SrMonArg<false>{});
     ASR_LAUNCH_CHECK();
     return ASR_OK;
 }
@@ -1385,7 +1421,7 @@ extern "C" int asr_sr_forward_residual_dt_f32(const float* x, const float* y, co
     if (rc != ASR_OK) return rc;
     a.r_out = r_out;
     hipLaunchKernelGGL((sr_forward_residual_kernel<false, true>), lr_grid(d), kBlock, 0, asr_stream(stream), x, y, rot_tf,
-                       trans_tf, q_out, d, a);
+                       trans_tf, q_out, d, a, SrMonArg<false>{});
     ASR_LAUNCH_CHECK();
     return ASR_OK;
 }
@@ -1568,11 +1604,179 @@ extern "C" size_t asr_sr_solve_workspace_bytes_cfg(int batch, int n, int H, int 
 // step (device array, prepared by the host wrapper so that the schedule and the persistent step
 // counter follow optimizer.py exactly).
 namespace {
+// ---- convergence monitor (asr_sr_solve_mon_f32; include/asr_hip.h: the rule) ---------------------------------------
+// The loss terms of the monitor, reproducible to the bit: no floating-point atomics, and every order of addition fixed by
+// the image's own index space.  Image b's elements p = 0 .. P-1 (the n*h*w residuals, or the H*W pixels) are dealt to
+// kMonParts workgroups of 256 threads: thread t of workgroup g adds, in float64 and in rising p, the summands of
+// p = g*256 + t + k*(kMonParts*256), k = 0, 1, ...; a wave adds its 64 sums with the shuffle tree of asr_wave_sum (offsets 32,
+// 16, .. 1), the workgroup its four waves as ((w0 + w1) + w2) + w3: partial g.  sr_mon_decide_kernel adds the kMonParts partials
+// of a term in index order, one lane per term.  Nothing depends on the batch, on plane_chunk or on what ran before.
+// The summands are those of sr_loss_df_dt_kernel and sr_loss_prior_kernel, statement for statement.
+constexpr int kMonParts = 256;
+
+__device__ __forceinline__ double sr_mon_block_sum(double acc, double* sh) {
+    acc = asr_wave_sum(acc);
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    const double r = ((sh[0] + sh[1]) + sh[2]) + sh[3];
+    __syncthreads();
+    return r;
+}
+
+__global__ __launch_bounds__(256) SR_NO_PK_F32 void sr_mon_loss_df_kernel(const float* __restrict__ resid, double* __restrict__ parts,
+                                                                          int64_t per_image, SrDt dt,
+                                                                          const int* __restrict__ stopped) {
+    __shared__ double sh[4];
+    const int b = blockIdx.y;
+    if (stopped[b]) return;
+    const float* r = resid + (int64_t)b * per_image;
+    const float* wgt = dt.w ? dt.w + (int64_t)b * dt.w_stride : nullptr;
+    double acc = 0.0;
+#pragma unroll 4                               // four loads in flight; the additions stay one chain, in rising p
+    for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < per_image; p += (int64_t)kMonParts * 256) {
+        const float t = r[p];
+        const float a = fabsf(t);
+        float rho;
+        if (dt.loss == ASR_DF_L1) {
+            rho = a;
+        } else if (dt.loss == ASR_DF_HUBER && !(a <= dt.delta)) {
+            const float lin = 2.0f * a - dt.delta;      // 2|r| is exact
+            rho = dt.delta * lin;
+        } else {
+            rho = t * t;
+        }
+        if (wgt) rho = wgt[p] * rho;
+        acc += (double)rho;
+    }
+    acc = sr_mon_block_sum(acc, sh);
+    if (threadIdx.x == 0) parts[((int64_t)b * kMonParts + blockIdx.x) * 4 + 0] = acc;
+}
+
+template <bool WTV>
+__global__ __launch_bounds__(256) SR_NO_PK_F32 void sr_mon_loss_prior_kernel(const float* __restrict__ x, double* __restrict__ parts,
+                                                                             int H, int W, SrStep st, SrTvW tw,
+                                                                             const int* __restrict__ stopped) {
+    __shared__ double sh[4];
+    const int b = blockIdx.y;
+    if (stopped[b]) return;
+    const float* img = x + (int64_t)b * H * W;
+    double tv = 0.0, l2 = 0.0, l1 = 0.0;
+    const int64_t total = (int64_t)H * W;
+    for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < total; p += (int64_t)kMonParts * 256) {
+        const int X = (int)(p % W), Y = (int)(p / W);
+        const float xc = img[p];
+        if (st.prior == ASR_PRIOR_BTV) {
+            for (int hh = -st.btv_shift; hh <= st.btv_shift; ++hh)
+                for (int vv = 0; vv <= st.btv_shift; ++vv) {
+                    const int xs = X - hh, ys = Y - vv;
+                    const float sv = (xs >= 0 && xs < W && ys >= 0 && ys < H) ? img[(int64_t)ys * W + xs] : 0.0f;
+                    tv += (double)st.btv_w[abs(hh) + vv] * (double)fabsf(xc - sv);     // two float32 factors: exact in float64
+                }
+        } else if (WTV) {
+            const float dy = (Y < H - 1) ? img[p + W] - xc : 0.0f;
+            const float dx = (X < W - 1) ? img[p + 1] - xc : 0.0f;
+            const int64_t q = (int64_t)b * tw.stride + p;      // the last row / column: weight read, times |0|
+            tv += (double)(tw.wy[q] * fabsf(dy) + tw.wx[q] * fabsf(dx));
+        } else {
+            const float dy = (Y < H - 1) ? img[p + W] - xc : 0.0f;
+            const float dx = (X < W - 1) ? img[p + 1] - xc : 0.0f;
+            tv += (double)(fabsf(dy) + fabsf(dx));
+        }
+        l2 += (double)(xc * xc);
+        l1 += (double)fabsf(xc);
+    }
+    tv = sr_mon_block_sum(tv, sh);
+    l2 = sr_mon_block_sum(l2, sh);
+    l1 = sr_mon_block_sum(l1, sh);
+    if (threadIdx.x == 0) {
+        double* o = parts + ((int64_t)b * kMonParts + blockIdx.x) * 4;
+        o[1] = tv;
+        o[2] = l2;
+        o[3] = l1;
+    }
+}
+
+// Per-image state of the stop rule, in the workspace.  One launch per solve.
+struct SrMonState {
+    double* parts;     // [batch, kMonParts, 4]
+    double* best;      // [batch]
+    int* stall;        // [batch]
+    int* stopped;      // [batch]
+};
+
+__global__ __launch_bounds__(64) SR_NO_PK_F32 void sr_mon_init_kernel(SrMonState s, int* __restrict__ iters_done, int batch,
+                                                                      int num_iter) {
+    for (int b = threadIdx.x; b < batch; b += 64) {
+        s.best[b] = __builtin_inf();
+        s.stall[b] = 0;
+        s.stopped[b] = 0;
+        iters_done[b] = num_iter;
+    }
+}
+
+// One evaluation.  rule == 0: only the terms (the last iteration's, for last_loss_terms, when it is no evaluation).
+struct SrMonEval {
+    int rule, it, row;                 // row: the evaluation's index = it / every
+    int patience, min_iter;
+    double rel_tol;
+    double l_df, l_tv, l_l2, l_l1;     // the float32 lambdas widened
+};
+
+// One workgroup of one wave per image: lanes 0..3 add the partials of their term in index order, lane 0 applies the rule.
+__global__ __launch_bounds__(64) SR_NO_PK_F32 void sr_mon_decide_kernel(SrMonState s, int* __restrict__ iters_done,
+                                                                        double* __restrict__ history,
+                                                                        double* __restrict__ last_terms, int batch, SrMonEval e) {
+    __shared__ double t[4];
+    __shared__ double part[kMonParts * 4];
+    const int b = blockIdx.x;
+    if (s.stopped[b]) return;
+    // the image's kMonParts x 4 partials through LDS (one coalesced read instead of a chain of dependent global loads)
+    for (int i = threadIdx.x; i < kMonParts * 4; i += 64) part[i] = s.parts[(int64_t)b * kMonParts * 4 + i];
+    __syncthreads();
+    if (threadIdx.x < 4) {
+        double sum = 0.0;
+        for (int g = 0; g < kMonParts; ++g) sum += part[g * 4 + threadIdx.x];
+        t[threadIdx.x] = sum;
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    if (last_terms)
+        for (int k = 0; k < 4; ++k) last_terms[(int64_t)b * 4 + k] = t[k];
+    if (!e.rule) return;
+    if (history)
+        for (int k = 0; k < 4; ++k) history[((int64_t)e.row * batch + b) * 4 + k] = t[k];
+    double loss = (e.l_df * t[0] + e.l_tv * t[1]) + e.l_l2 * t[2];
+    if (e.l_l1 > 0.0) loss = loss + e.l_l1 * t[3];
+    const double best = s.best[b];
+    // best = +inf (no evaluation yet): the threshold is +inf itself, not inf - tol * inf = NaN; a NaN loss never improves
+    const double bar = (best == __builtin_inf()) ? best : best - e.rel_tol * fabs(best);
+    int stall = s.stall[b];
+    if (loss < bar) {
+        s.best[b] = loss;
+        stall = 0;
+    } else {
+        stall += 1;
+    }
+    s.stall[b] = stall;
+    if (e.patience >= 1 && stall >= e.patience && e.it >= e.min_iter) {
+        s.stopped[b] = 1;
+        iters_done[b] = e.it;
+    }
+}
+
+size_t sr_mon_workspace_extra(int batch) {
+    // 8 bytes of slack to align the doubles + partials + best + {stall, stopped}
+    return 8 + sizeof(double) * ((size_t)batch * kMonParts * 4 + (size_t)batch) + sizeof(int) * 2 * (size_t)batch;
+}
+
 int sr_solve_impl(const char* fn, float* x, const float* y, const float* rot_tf, const float* trans_tf, const float* inv_rot_tf,
                   const float* inv_trans_tf, float* m, float* v, float* vhat, const float* alphas, int num_iter,
                   double* last_loss_terms, void* workspace, size_t workspace_bytes, int batch, int n, int H, int W, int h, int w,
                   float lambda_df, float lambda_tv, float lambda_l2, float lambda_l1, const asr_sr_config* cfg,
-                  const SrTvWArg& wa, asr_stream_t stream, const SrDt* dt = nullptr) {
+                  const SrTvWArg& wa, asr_stream_t stream, const SrDt* dt = nullptr, const asr_sr_monitor* mon = nullptr) {
+    // mon (asr_sr_solve_mon_f32, always with dt): the MON instantiations of the three per-iteration kernels and, at every
+    // evaluation, the two partial-sum kernels and the decision kernel between K_fwd and K_gt.  Everything is enqueued; the host
+    // never learns during the solve which image has stopped.
     // dt (asr_sr_solve_dt_f32): K_fwd writes q = w * psi(r) where the other entry points write r; everything after reads that
     // buffer as it always did.  The workspace then ends with a second [batch*n, h, w] buffer: the raw r of the last iteration,
     // a second output of that one K_fwd launch, for the loss terms.
@@ -1591,7 +1795,7 @@ int sr_solve_impl(const char* fn, float* x, const float* y, const float* rot_tf,
     const int chunk = sr_plane_chunk(batch, n, H, W, cfg->plane_chunk);
     ASR_REQUIRE((int64_t)batch * chunk <= 65535, "%s: batch*chunk=%lld exceeds 65535 (grid.z)", fn, (long long)batch * chunk);
     const size_t base = sr_workspace_bytes(batch, n, H, W, h, w, chunk);
-    const size_t need = base + (dt ? sr_dt_workspace_extra(batch, n, h, w) : 0);
+    const size_t need = base + (dt ? sr_dt_workspace_extra(batch, n, h, w) : 0) + (mon ? sr_mon_workspace_extra(batch) : 0);
     if (workspace_bytes < need) {
         asr_set_error("%s: workspace %zu < required %zu bytes", fn, workspace_bytes, need);
         return ASR_ERR_WORKSPACE;
@@ -1607,6 +1811,23 @@ int sr_solve_impl(const char* fn, float* x, const float* y, const float* rot_tf,
     float* const xb = gr + (size_t)batch * chunk * sr_gr_plane_elems(H, W);   // bordered copy of the current x
     int* const affine_flags = reinterpret_cast<int*>(xb + (size_t)batch * sr_gr_plane_elems(H, W));
     float* const raw = reinterpret_cast<float*>(static_cast<char*>(workspace) + base);   // dt only
+    SrMonState ms = {nullptr, nullptr, nullptr, nullptr};
+    SrMonArg<true> marg = {nullptr};
+    int mon_rows = 0;
+    if (mon) {
+        uintptr_t p = reinterpret_cast<uintptr_t>(raw) + sr_dt_workspace_extra(batch, n, h, w);
+        p = (p + 7) & ~(uintptr_t)7;
+        ms.parts = reinterpret_cast<double*>(p);
+        ms.best = ms.parts + (size_t)batch * kMonParts * 4;
+        ms.stall = reinterpret_cast<int*>(ms.best + batch);
+        ms.stopped = ms.stall + batch;
+        marg.stopped = ms.stopped;
+        mon_rows = (num_iter + mon->every - 1) / mon->every;
+        hipLaunchKernelGGL(sr_mon_init_kernel, dim3(1), dim3(64), 0, s, ms, mon->iters_done, batch, num_iter);
+        ASR_LAUNCH_CHECK();
+        if (mon->history && mon_rows > 0)     // NaN: the rows an image does not reach
+            ASR_HIP_CHECK(hipMemsetAsync(mon->history, 0xFF, sizeof(double) * 4 * (size_t)mon_rows * batch, s));
+    }
     if (num_iter > 0) {
         hipLaunchKernelGGL(sr_affine_flags_kernel, dim3((unsigned)batch), dim3(64), 0, s, inv_rot_tf, affine_flags, n);
         ASR_LAUNCH_CHECK();
@@ -1622,13 +1843,56 @@ int sr_solve_impl(const char* fn, float* x, const float* y, const float* rot_tf,
     }
     for (int it = 0; it < num_iter; ++it) {
         const bool want_terms = last_loss_terms && it == num_iter - 1;
+        if (mon) {
+            // an evaluation (it % every == 0) or, for last_loss_terms, the last iteration: the terms of the current x, then the rule
+            const bool is_eval = it % mon->every == 0;
+            SrDt a = *dt;
+            a.r_out = (is_eval || want_terms) ? raw : nullptr;
+            hipLaunchKernelGGL((sr_forward_residual_kernel<true, true, true>), lr_grid(d), kBlock, 0, s, xb, y, rot_tf, trans_tf, resid,
+                               d, a, marg);
+            ASR_LAUNCH_CHECK();
+            if (is_eval || want_terms) {
+                hipLaunchKernelGGL(sr_mon_loss_df_kernel, dim3(kMonParts, batch), dim3(256), 0, s, raw, ms.parts,
+                                   (int64_t)n * h * w, *dt, ms.stopped);
+                ASR_LAUNCH_CHECK();
+                if (wa.weighted)
+                    hipLaunchKernelGGL(sr_mon_loss_prior_kernel<true>, dim3(kMonParts, batch), dim3(256), 0, s, cur, ms.parts, H, W, st,
+                                       tw, ms.stopped);
+                else
+                    hipLaunchKernelGGL(sr_mon_loss_prior_kernel<false>, dim3(kMonParts, batch), dim3(256), 0, s, cur, ms.parts, H, W, st,
+                                       tw, ms.stopped);
+                ASR_LAUNCH_CHECK();
+                SrMonEval e;
+                e.rule = is_eval ? 1 : 0; e.it = it; e.row = it / mon->every;
+                e.patience = mon->patience; e.min_iter = mon->min_iter; e.rel_tol = mon->rel_tol;
+                e.l_df = (double)lambda_df; e.l_tv = (double)lambda_tv; e.l_l2 = (double)lambda_l2; e.l_l1 = (double)lambda_l1;
+                hipLaunchKernelGGL(sr_mon_decide_kernel, dim3((unsigned)batch), dim3(64), 0, s, ms, mon->iters_done, mon->history,
+                                   last_loss_terms, batch, e);
+                ASR_LAUNCH_CHECK();
+            }
+            const SrGradTranslateMonKernel gr_mon = sr_grad_translate_mon_kernel_for(d.f);
+            for (int n0 = 0; n0 < n; n0 += chunk) {
+                const int cn = n - n0 < chunk ? n - n0 : chunk;
+                hipLaunchKernelGGL(gr_mon, gr_grid(d, cn), dim3(64, 4), 0, s, resid, inv_trans_tf, gr, d, 2.0f * lambda_df, n0, cn,
+                                   marg);
+                ASR_LAUNCH_CHECK();
+                const auto bwd_kernel = wa.weighted ? sr_backward_gather_kernel<true, true> : sr_backward_gather_kernel<false, true>;
+                hipLaunchKernelGGL(bwd_kernel, gather_grid(d), dim3(64, 4), 0, s, cur, nxt, gr, inv_rot_tf, m, v, vhat,
+                                   alphas + (size_t)it * batch, (float*)nullptr, d, lambda_tv, 2.0f * lambda_l2, lambda_l1, st, xb,
+                                   acc, n0, cn, affine_flags, tw, marg);
+                ASR_LAUNCH_CHECK();
+            }
+            float* t = cur; cur = nxt; nxt = t;
+            continue;
+        }
         if (dt) {
             SrDt a = *dt;
             a.r_out = want_terms ? raw : nullptr;
-            hipLaunchKernelGGL((sr_forward_residual_kernel<true, true>), lr_grid(d), kBlock, 0, s, xb, y, rot_tf, trans_tf, resid, d, a);
+            hipLaunchKernelGGL((sr_forward_residual_kernel<true, true>), lr_grid(d), kBlock, 0, s, xb, y, rot_tf, trans_tf, resid, d, a,
+                               SrMonArg<false>{});
         } else {
             hipLaunchKernelGGL(sr_forward_residual_kernel<true>, lr_grid(d), kBlock, 0, s, xb, y, rot_tf, trans_tf, resid, d,
-                               SrDtArg<false>{});
+                               SrDtArg<false>{}, SrMonArg<false>{});
         }
         ASR_LAUNCH_CHECK();
         if (want_terms) {
@@ -1637,12 +1901,13 @@ int sr_solve_impl(const char* fn, float* x, const float* y, const float* rot_tf,
         }
         for (int n0 = 0; n0 < n; n0 += chunk) {
             const int cn = n - n0 < chunk ? n - n0 : chunk;
-            hipLaunchKernelGGL(gr_kernel, gr_grid(d, cn), dim3(64, 4), 0, s, resid, inv_trans_tf, gr, d, 2.0f * lambda_df, n0, cn);
+            hipLaunchKernelGGL(gr_kernel, gr_grid(d, cn), dim3(64, 4), 0, s, resid, inv_trans_tf, gr, d, 2.0f * lambda_df, n0, cn,
+                               SrMonArg<false>{});
             ASR_LAUNCH_CHECK();
             const auto bwd_kernel = wa.weighted ? sr_backward_gather_kernel<true> : sr_backward_gather_kernel<false>;
             hipLaunchKernelGGL(bwd_kernel, gather_grid(d), dim3(64, 4), 0, s, cur, nxt, gr, inv_rot_tf, m, v, vhat,
                                alphas + (size_t)it * batch, (float*)nullptr, d, lambda_tv, 2.0f * lambda_l2, lambda_l1, st, xb,
-                               acc, n0, cn, affine_flags, tw);
+                               acc, n0, cn, affine_flags, tw, SrMonArg<false>{});
             ASR_LAUNCH_CHECK();
         }
         float* t = cur; cur = nxt; nxt = t;
@@ -1732,6 +1997,33 @@ extern "C" int asr_sr_solve_dt_f32(float* x, const float* y, const float* rot_tf
     return sr_solve_impl("asr_sr_solve_dt_f32", x, y, rot_tf, trans_tf, inv_rot_tf, inv_trans_tf, m, v, vhat, alphas, num_iter,
                          last_loss_terms, workspace, workspace_bytes, batch, n, H, W, h, w, lambda_df, lambda_tv, lambda_l2,
                          lambda_l1, cfg, wa, stream, &a);
+}
+
+extern "C" size_t asr_sr_solve_workspace_bytes_mon(int batch, int n, int H, int W, int h, int w, const asr_sr_config* cfg) {
+    return asr_sr_solve_workspace_bytes_dt(batch, n, H, W, h, w, cfg) + sr_mon_workspace_extra(batch > 0 ? batch : 0);
+}
+
+extern "C" int asr_sr_solve_mon_f32(float* x, const float* y, const float* rot_tf, const float* trans_tf,
+                                    const float* inv_rot_tf, const float* inv_trans_tf, float* m, float* v, float* vhat,
+                                    const float* alphas, int num_iter, double* last_loss_terms, void* workspace,
+                                    size_t workspace_bytes, int batch, int n, int H, int W, int h, int w, float lambda_df,
+                                    float lambda_tv, float lambda_l2, float lambda_l1, const asr_sr_config* cfg,
+                                    const asr_sr_data_term* dt, const asr_sr_monitor* mon, asr_stream_t stream) {
+    const char* fn = "asr_sr_solve_mon_f32";
+    SrDt a;
+    const int rc = make_data_term(fn, dt, n, h, w, &a);
+    if (rc != ASR_OK) return rc;
+    ASR_REQUIRE(mon, "%s: null monitor", fn);
+    ASR_REQUIRE(mon->every >= 1, "%s: monitor every=%d must be >= 1", fn, mon->every);
+    ASR_REQUIRE(mon->rel_tol >= 0.0 && mon->rel_tol < __builtin_inf(), "%s: monitor rel_tol=%g must be finite and >= 0", fn,
+                mon->rel_tol);
+    ASR_REQUIRE(mon->patience >= 0, "%s: monitor patience=%d must be >= 0", fn, mon->patience);
+    ASR_REQUIRE(mon->min_iter >= 0, "%s: monitor min_iter=%d must be >= 0", fn, mon->min_iter);
+    ASR_REQUIRE(mon->iters_done, "%s: null pointer (monitor iters_done)", fn);
+    const SrTvWArg wa = {dt->wy, dt->wx, dt->tv_shared, dt->wy != nullptr};
+    return sr_solve_impl(fn, x, y, rot_tf, trans_tf, inv_rot_tf, inv_trans_tf, m, v, vhat, alphas, num_iter, last_loss_terms,
+                         workspace, workspace_bytes, batch, n, H, W, h, w, lambda_df, lambda_tv, lambda_l2, lambda_l1, cfg, wa,
+                         stream, &a, mon);
 }
 
 extern "C" int asr_sr_solve_f32(float* x, const float* y, const float* rot_tf, const float* trans_tf,

@@ -219,6 +219,29 @@ def write_class_csv(path, rows):
             wr.writerow([name] + [repr(v) for v in means] + [str(count)])
 
 
+SR_ITERS_CSV_COLUMNS = ("image", "class", "iterations")
+
+
+def write_sr_iters_csv(path, rows):
+    """rows of (image, class, iterations) -- evaluate_labelmaps' sr_iters -- as a CSV, every field quoted."""
+    import csv
+    with open(path, "w", newline="") as fh:
+        wr = csv.writer(fh, quoting=csv.QUOTE_ALL, lineterminator="\n")
+        wr.writerow(SR_ITERS_CSV_COLUMNS)
+        for image, cls, iterations in rows:
+            wr.writerow([str(image), str(cls), str(int(iterations))])
+
+
+def read_sr_iters_csv(path):
+    """write_sr_iters_csv's file -> [(image, class, iterations)], image and class as strings."""
+    import csv
+    with open(path, newline="") as fh:
+        rows = list(csv.reader(fh))
+    if not rows or tuple(rows[0]) != SR_ITERS_CSV_COLUMNS:
+        raise ValueError(f"{path}: not an SR-iterations CSV (header {rows[:1]})")
+    return [(r[0], r[1], int(r[2])) for r in rows[1:]]
+
+
 # ---- label maps: one fused label map per image and SR type, scored with the multi-class Mean_IOU ------------------------
 LABELMAP_KEYS = ("standard", "aug", "max", "mean")
 LABELMAP_CSV_COLUMNS = ("standard_iou", "aug_iou", "max_iou", "mean_iou")
@@ -286,8 +309,8 @@ def dataset_miou(counts):
 def evaluate_labelmaps(path, image_paths, gt_paths, class_ids=tuple(range(1, 21)), num_aug=100, angle_max=0.3, shift_max=30,
                        img_size=(512, 512), rank=0, world=1, seed=1234, sr_types=("aug", "max", "mean"), prune=True,
                        save_dir=None, band_widths=None, band_ignore_label=255, confusion_labels=None, th_factors=None,
-                       guide=None, df_weights=None, tv_guide=None, crf=None, min_region=None, segments=None, coverages=None,
-                       uncertainty_dir=None):
+                       guide=None, df_weights=None, sr_stop=None, sr_iters=None, tv_guide=None, crf=None, min_region=None,
+                       segments=None, coverages=None, uncertainty_dir=None):
     """One fused label map per image and SR type (HotPath.run_image_labels) and its score.  Returns on every rank a
     LabelmapScores, the tuple (rows, counts) plus what the options below append, every entry also an attribute by the name
     given here: rows [images, 4] per-image Mean_IOU in LABELMAP_KEYS order (the reference's per-image-then-mean convention;
@@ -348,7 +371,13 @@ def evaluate_labelmaps(path, image_paths, gt_paths, class_ids=tuple(range(1, 21)
     (utils.metrics_from_segments, write_segments_csv), all zero for a label map that was not asked for; with min_region
     another follows, raw_segments, the same of the maps before the clean-up.  They travel in the same float64 all-gather:
     exact while a Q sum stays below 2^53, that is 2^23 (about 8 million) matched segments per label map and label, each
-    adding at most 2^30."""
+    adding at most 2^30.
+
+    sr_stop (run_image_labels' sr_stop: rel_tol, patience, every, min_iter): every image's "aug" solves stop class by class
+    once their loss has stalled.  The return value keeps its form; sr_iters (a list) receives one row (image stem, class id,
+    iterations) per image of THIS rank and solved class (write_sr_iters_csv; in slice_max a second row per class, the class
+    written "<id>_max", for its max map's solve).  The Adam bookkeeping does not change."""
+    stop_kw = {} if path.check_sr_stop(sr_stop) is None else {"sr_stop": dict(sr_stop)}
     if uncertainty_dir and coverages is None:
         raise ValueError("uncertainty_dir needs coverages: the uncertainty map is only built for the risk-coverage curve")
     opts = path.label_options(tuple(img_size) + (3,), True, band_widths, band_ignore_label, confusion_labels, th_factors,
@@ -379,7 +408,12 @@ def evaluate_labelmaps(path, image_paths, gt_paths, class_ids=tuple(range(1, 21)
                                     band_widths=opts.bands, band_ignore_label=band_ignore_label,
                                     confusion_labels=opts.n_conf or None, th_factors=opts.factors, guide=opts.guide,
                                     coverages=opts.covs, keep_uncertainty=bool(uncertainty_dir), min_region=opts.min_region,
-                                    segments=opts.segments, **tv_kw)
+                                    segments=opts.segments, **tv_kw, **stop_kw)
+        if stop_kw and sr_iters is not None:
+            stem = os.path.splitext(os.path.basename(image_paths[g]))[0]
+            for solve, its in sorted(res["sr_iters"].items()):
+                tag = "_max" if solve == "aug_max" else ""
+                sr_iters.extend((stem, f"{c}{tag}", int(k)) for c, k in zip(res["solved_ids"], its))
         for f, (mious, counts) in local.items():        # a label map that was not produced: NaN Mean_IOU, zero counts
             if f.scored:
                 mious.append([res[f.prefix + "Mean_IOU"].get(key, np.full(f.shape[:-2], np.nan)) for key in f.keys])

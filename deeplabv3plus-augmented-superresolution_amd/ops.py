@@ -118,17 +118,18 @@ def check_data_term(loss, delta=0.1, name="data term"):
     return code, float(delta)
 
 
-def _data_term(data_term, weights, y, tvw, name):
+def _data_term(data_term, weights, y, tvw, name, always=False):
     """data_term (None, a loss name, or a pair (loss, delta)) + weights ([N,h,w] shared by the batch or [B,N,h,w], on the device
     of y) + the checked tv_weights -> the asr_sr_data_term of a *_dt call, or None when the call that ran before data terms
-    existed computes the same thing (L2, no weights).  The struct keeps its tensors alive."""
+    existed computes the same thing (L2, no weights; always=True: the struct then too, for the monitored solve, which has
+    the *_dt form only).  The struct keeps its tensors alive."""
     if isinstance(data_term, (tuple, list)):
         if len(data_term) != 2:
             raise ValueError(f"{name}: data_term must be a loss name or a pair (loss, delta), got {data_term!r}")
         code, delta = check_data_term(data_term[0], data_term[1], name)
     else:
         code, delta = check_data_term(data_term, name=name)
-    if weights is None and code == _lib.DF_L2:
+    if weights is None and code == _lib.DF_L2 and not always:
         return None
     shared = 0
     if weights is not None:
@@ -293,19 +294,78 @@ def sr_loss_terms(x, resid, cfg=None, tv_weights=None, data_term=None, weights=N
     return terms
 
 
+SR_MONITOR_DEFAULTS = dict(every=1, rel_tol=1e-4, patience=3, min_iter=0, history=True)
+
+
+def check_sr_monitor(params, name="sr monitor"):
+    """The monitor of a solve (include/asr_hip.h: asr_sr_monitor) as a complete dict: a mapping with any of the keys every
+    (int >= 1), rel_tol (finite number >= 0), patience (int >= 0; 0 = never stop), min_iter (int >= 0) and history (bool),
+    the others from SR_MONITOR_DEFAULTS.  Host only; ValueError on anything else."""
+    import numbers
+    if not isinstance(params, dict):
+        raise ValueError(f"{name}: a dict with keys among {sorted(SR_MONITOR_DEFAULTS)} expected, got {params!r}")
+    unknown = sorted(set(params) - set(SR_MONITOR_DEFAULTS))
+    if unknown:
+        raise ValueError(f"{name}: unknown keys {unknown} (known: {sorted(SR_MONITOR_DEFAULTS)})")
+    p = dict(SR_MONITOR_DEFAULTS, **params)
+    for key, low in (("every", 1), ("patience", 0), ("min_iter", 0)):
+        v = p[key]
+        if not isinstance(v, numbers.Integral) or isinstance(v, bool) or not low <= int(v) < 2 ** 31:
+            raise ValueError(f"{name}: {key} must be an integer >= {low}, got {v!r}")
+        p[key] = int(v)
+    t = p["rel_tol"]
+    if not isinstance(t, numbers.Real) or isinstance(t, bool) or not np.isfinite(float(t)) or float(t) < 0.0:
+        raise ValueError(f"{name}: rel_tol must be a finite number >= 0, got {t!r}")
+    p["rel_tol"] = float(t)
+    if not isinstance(p["history"], (bool, np.bool_)):
+        raise ValueError(f"{name}: history must be True or False, got {p['history']!r}")
+    p["history"] = bool(p["history"])
+    return p
+
+
+def sr_loss_from_terms(terms, lambdas):
+    """The scalar loss of the monitor from its four terms [..., 4], in float64: ((l_df*t0 + l_tv*t1) + l_L2*t2), then
+    + l_L1*t3 only when l_L1 > 0, the lambdas the float32 arguments widened, every operation rounding by itself."""
+    t = np.asarray(terms, dtype=np.float64)
+    l = [np.float64(np.float32(v)) for v in lambdas]
+    loss = (l[0] * t[..., 0] + l[1] * t[..., 1]) + l[2] * t[..., 2]
+    if l[3] > 0.0:
+        loss = loss + l[3] * t[..., 3]
+    return loss
+
+
+class SrTrace:
+    """What a monitored solve leaves behind.  history: device float64 [E, B, 4], the four loss terms of every image at
+    every evaluation (NaN after the image stopped), or None; eval_iters: the E iterations that were evaluations;
+    iters_done: device int32 [B], the updates applied to each image.  Reading either tensor on the host synchronises."""
+
+    def __init__(self, history, eval_iters, iters_done):
+        self.history, self.eval_iters, self.iters_done = history, list(eval_iters), iters_done
+
+    def losses(self, lambdas):
+        """numpy float64 [E, B]: the scalar loss the stop rule saw at every evaluation (sr_loss_from_terms)."""
+        if self.history is None:
+            raise AsrError("SrTrace.losses: the solve kept no history (monitor history=False)")
+        return sr_loss_from_terms(self.history.cpu().numpy(), lambdas)
+
+
 def sr_solve(x, y, rot_tf, trans_tf, inv_rot_tf, inv_trans_tf, alphas, lambdas, one_minus_beta1=None, one_minus_beta2=None,
              epsilon=None, amsgrad=False, want_loss=True, cfg=None, slot_init=None, state=None, tv_weights=None,
-             data_term=None, weights=None):
+             data_term=None, weights=None, monitor=None):
     """Runs alphas.shape[0] iterations in place on x.  alphas [num_iter, B] (device).  Either the Adam
     hyper-parameters (asr_sr_solve_f32) or cfg (+ slot_init = {"m"/"v"/"vhat": initial value}) for
     asr_sr_solve_cfg_f32.  state: a dict that carries the optimiser slots and the workspace from one call to the next --
     a solve cut into several calls (the verbose loss print-outs) then performs exactly the updates of a single call.
     tv_weights = (wy, wx): the edge-weighted TV prior; with the Adam hyper-parameters instead of cfg the call goes through
     the equivalent {Adam, TV} config.  data_term, weights: the data term sum weights * rho(r) (sr_forward_residual; combines
-    freely with tv_weights); with L2 / None and no weights the calls above are made, unchanged."""
+    freely with tv_weights); with L2 / None and no weights the calls above are made, unchanged.
+    monitor (check_sr_monitor's dict): the solve goes through asr_sr_solve_mon_f32 -- the loss terms of every `every`-th
+    iteration, each image stopped by itself when its loss stalls (include/asr_hip.h: the rule) -- and the return value is
+    (x, terms, SrTrace); nothing is read back here.  Without it: the calls and the pair above, unchanged."""
     b, n, H, W, h, w = _sr_dims(x, y)
+    mon = check_sr_monitor(monitor, "sr_solve: monitor") if monitor is not None else None
     tvw = _tv_weights(tv_weights, x, "sr_solve") if tv_weights is not None else None
-    dt = _data_term(data_term, weights, y, tvw, "sr_solve")
+    dt = _data_term(data_term, weights, y, tvw, "sr_solve", always=mon is not None)
     if (tvw is not None or dt is not None) and cfg is None:
         cfg = _adam_config(one_minus_beta1, one_minus_beta2, epsilon, amsgrad)
     for t, name in ((rot_tf, "rot_tf"), (trans_tf, "trans_tf"), (inv_rot_tf, "inv_rot_tf"), (inv_trans_tf, "inv_trans_tf")):
@@ -314,7 +374,8 @@ def sr_solve(x, y, rot_tf, trans_tf, inv_rot_tf, inv_trans_tf, alphas, lambdas, 
         raise AsrError(f"alphas must be [num_iter,{b}]")
     num_iter = alphas.shape[0]
     lib = _lib.load()
-    ws_bytes = (lib.asr_sr_solve_workspace_bytes(b, n, H, W, h, w) if cfg is None else
+    ws_bytes = (lib.asr_sr_solve_workspace_bytes_mon(b, n, H, W, h, w, C.byref(cfg)) if mon is not None else
+                lib.asr_sr_solve_workspace_bytes(b, n, H, W, h, w) if cfg is None else
                 lib.asr_sr_solve_workspace_bytes_dt(b, n, H, W, h, w, C.byref(cfg)) if dt is not None else
                 lib.asr_sr_solve_workspace_bytes_cfg(b, n, H, W, h, w, C.byref(cfg)))
     if state is not None and "ws" in state:
@@ -332,6 +393,17 @@ def sr_solve(x, y, rot_tf, trans_tf, inv_rot_tf, inv_trans_tf, alphas, lambdas, 
         if state is not None:
             state.update(ws=ws, m=m, v=v, vhat=vhat)
     terms = torch.zeros((b, 4), dtype=torch.float64, device=x.device) if want_loss else None
+    if mon is not None:
+        eval_iters = list(range(0, num_iter, mon["every"]))
+        history = (torch.empty((len(eval_iters), b, 4), dtype=torch.float64, device=x.device) if mon["history"] else None)
+        iters_done = torch.empty((b,), dtype=torch.int32, device=x.device)
+        ms = _lib.SrMonitor(mon["every"], mon["rel_tol"], mon["patience"], mon["min_iter"],
+                            history.data_ptr() if history is not None and history.numel() else None, ptr(iters_done, torch.int32))
+        call("asr_sr_solve_mon_f32", ptr(x), ptr(y), ptr(rot_tf), ptr(trans_tf), ptr(inv_rot_tf), ptr(inv_trans_tf), ptr(m),
+             ptr(v), ptr(vhat), ptr(alphas), num_iter, ptr(terms, torch.float64, allow_none=True), ptr(ws),
+             C.c_size_t(ws_bytes), b, n, H, W, h, w, float(lambdas[0]), float(lambdas[1]), float(lambdas[2]),
+             float(lambdas[3]), C.byref(cfg), C.byref(dt), C.byref(ms), stream_ptr())
+        return x, terms, SrTrace(history, eval_iters, iters_done)
     if dt is not None:
         call("asr_sr_solve_dt_f32", ptr(x), ptr(y), ptr(rot_tf), ptr(trans_tf), ptr(inv_rot_tf), ptr(inv_trans_tf), ptr(m),
              ptr(v), ptr(vhat), ptr(alphas), num_iter, ptr(terms, torch.float64, allow_none=True), ptr(ws),

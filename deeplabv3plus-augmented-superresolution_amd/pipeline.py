@@ -231,17 +231,41 @@ class HotPath:
             return [it0 + j * self._solves * sr.num_iter for j in range(len(ids))]
         return [int(adam_starts[c]) for c in ids]
 
-    def _classes_scores(self, y, ymax, angles, fshifts, starts, sr_types, tv_weights=None, df_weights=None):
+    def _classes_scores(self, y, ymax, angles, fshifts, starts, sr_types, tv_weights=None, df_weights=None, stop=None,
+                        iters=None):
         """_sr_scores of a class set: class k's solve starts at the Adam step starts[k], its max map's num_iter later; the
         counter itself is left as it was.  tv_weights: the image's edge weights (wy, wx), shared by every solve; df_weights:
-        the copies' confidence stack [N, h, w], the weights of every solve's data term."""
+        the copies' confidence stack [N, h, w], the weights of every solve's data term.  stop (a checked monitor dict): the
+        solves run under it, and iters (a dict) receives the device int32 [K] iterations of each: "aug", "aug_max"."""
         sr = self.sr
         kw = {} if tv_weights is None else {"tv_guide": tv_weights}
         if df_weights is not None:
             kw["df_weights"] = df_weights
         solve = lambda stack, a, s, second: sr.augmented_superresolution_classes(
             stack, a[0], s[0], [st + second * sr.num_iter for st in starts], **kw)[0]
+        if stop is not None:
+            plain = solve
+
+            def solve(stack, a, s, second):
+                saved, sr.monitor, sr.last_trace = sr.monitor, stop, None
+                try:
+                    x = plain(stack, a, s, second)
+                finally:
+                    sr.monitor = saved
+                if sr.last_trace is not None:              # (num_iter = 0: no solve, no trace)
+                    iters["aug_max" if second else "aug"] = sr.last_trace.iters_done
+                return x
         return self._sr_scores(y, ymax, angles, fshifts, sr_types, solve)
+
+    @staticmethod
+    def check_sr_stop(sr_stop):
+        """run_image_labels' sr_stop, checked on the host before any launch: None, or a dict with any of rel_tol (default
+        1e-4), patience (3), every (1), min_iter (0) -> None or the monitor dict of the solver (no history is kept)."""
+        if sr_stop is None:
+            return None
+        if not isinstance(sr_stop, dict) or set(sr_stop) - {"rel_tol", "patience", "every", "min_iter"}:
+            raise ValueError(f"sr_stop must be a dict with keys among rel_tol, patience, every, min_iter, got {sr_stop!r}")
+        return ops.check_sr_monitor(dict(sr_stop, history=False), "sr_stop")
 
     def _advance_past(self, starts, adam_starts, sr_types):
         """adam_starts None: the classes counted as consecutive solves, the counter moves past the last of them."""
@@ -303,8 +327,8 @@ class HotPath:
     def run_image_labels(self, image_dev, angles, shifts, class_ids=range(1, 21), gt_dev=None, adam_starts=None,
                          sr_types=("aug", "max", "mean"), want_standard=True, prune=True, profile=None, keep_scores=False,
                          band_widths=None, band_ignore_label=255, confusion_labels=None, th_factors=None, guide=None,
-                         coverages=None, keep_uncertainty=False, min_region=None, df_weights=None, tv_guide=None, crf=None,
-                         segments=None):
+                         coverages=None, keep_uncertainty=False, min_region=None, df_weights=None, sr_stop=None, tv_guide=None,
+                         crf=None, segments=None):
         """One label map per SR type from one forward pass: stage 1 and the solves are run_image_classes's; stage 2 ends in the
         fusion kernel (ops.fuse_labels) instead of K thresholds.  class_ids: K <= 32 distinct ids, none 0 (the label of "no
         class").  At each pixel the label is the class whose single-class mask is set there and whose SR output is greatest
@@ -415,8 +439,16 @@ class HotPath:
         solve and, in slice_max, by the max maps' solve, and it is neither pruned nor normalised (copy_dropout drops its
         copies with the stacks').  The kernel always reads logits: from a model with a last_activation the batch's raw logits
         are taken, not the probabilities it returns (with final_upsample as well there are none at the stacks' size: refused).  With df_weights=None, or without "aug" in sr_types, nothing else is launched and every
-        result is what it was."""
+        result is what it was.
+
+        sr_stop ({"rel_tol": .., "patience": .., "every": .., "min_iter": ..}, any subset; check_sr_stop): the "aug" solves go
+        through the solver's convergence monitor (include/asr_hip.h), each class stopping by itself once its loss has stalled.
+        The result gains "sr_iters": {"aug": int32 [K'] numpy, the updates applied to each class of solved_ids} and in
+        slice_max also {"aug_max": the same of the max maps' solves}; they are read back with the other results, after the
+        whole image is enqueued.  The Adam bookkeeping does not change: every solve counts as num_iter steps, stopped or not.
+        With sr_stop=None nothing else is launched and the result is what it was."""
         ids = [int(c) for c in class_ids]
+        stop = self.check_sr_stop(sr_stop)
         self.check_df_weights(df_weights)
         tv_beta = self.check_tv_guide(tv_guide, None if image_dev is None else tuple(image_dev.shape))
         crf_opts = self.check_crf(crf, None if image_dev is None else tuple(image_dev.shape), th_factors, len(ids))
@@ -464,6 +496,7 @@ class HotPath:
         if kept:
             y, ymax = self._normalise(y, ymax)
         scores = {}
+        sr_iters = {}                      # sr_stop: device int32 [K'] per solve, read back at the end
         fshifts = self._sr_frame(image_dev, shifts)
         with self._sr_stage_timed(profile):
             gt = self._gt_int32(gt_dev) if gt_dev is not None else None
@@ -485,8 +518,9 @@ class HotPath:
             if tv_beta is not None and kept and "aug" in sr_types:
                 tv_weights = ops.tv_edge_weights(image_dev.to(torch.float32).contiguous(), tv_beta)
             if kept:
+                stop_kw = {} if stop is None else {"stop": stop, "iters": sr_iters}
                 for t, tgt, tmax in self._classes_scores(y, ymax, angles, fshifts, [starts[k] for k in kept], sr_types,
-                                                         tv_weights, conf[0] if conf else None):
+                                                         tv_weights, conf[0] if conf else None, **stop_kw):
                     j = keys.index(t)
                     if g_state is not None:
                         ops.guided_apply(g_state, g_image, tgt, out=tgt)
@@ -528,6 +562,8 @@ class HotPath:
             res["regions"] = {key: host[j] for j, key in enumerate(keys)}
         if keep_scores:
             res["scores"] = scores
+        if stop is not None:
+            res["sr_iters"] = {k: v.cpu().numpy() for k, v in sr_iters.items()}
         if keep_uncertainty:
             res["uncertainty"] = u_map
             res["uncertainty_stacks"] = y if kept else None

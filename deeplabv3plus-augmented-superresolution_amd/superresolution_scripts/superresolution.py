@@ -80,8 +80,18 @@ class Superresolution:
     def __init__(self, lambda_df, lambda_tv, lambda_L2, lambda_L1, num_iter=200, num_aug=100,
                  optimizer: Optimizer = None, feature_size=(64, 64), output_size=(512, 512), use_BTV=False,
                  verbose=False, copy_dropout=0.0, trim=0.1, cover="frame", cov_min=0.5, valid_min=0.5, tv_beta=100.0,
-                 df_loss="l2", df_delta=0.1):
+                 df_loss="l2", df_delta=0.1, stop_rel_tol=None, stop_patience=3, stop_every=1, stop_min_iter=0,
+                 keep_history=False):
         self.tv_beta = ops.check_tv_beta(tv_beta, "Superresolution: tv_beta")
+        # the convergence monitor (include/asr_hip.h): with stop_rel_tol each image of a solve stops by itself once its loss
+        # has not improved by that relative amount for stop_patience evaluations in a row (one every stop_every iterations,
+        # none before stop_min_iter); keep_history alone records the loss terms and never stops.  Neither: the solves and
+        # their launches are what they always were.  self.last_trace: the ops.SrTrace of the last monitored solve.
+        self.monitor = self.check_stop(stop_rel_tol, stop_patience, stop_every, stop_min_iter, keep_history)
+        if self.monitor is not None and verbose:
+            raise ValueError("Superresolution: verbose prints by cutting the solve into calls and cannot be combined with "
+                             "stop_rel_tol / keep_history (read last_trace instead)")
+        self.last_trace = None
         # the data term sum w * rho(r): "l2" (the reference's), "l1" or "huber" with threshold df_delta, in the units of the
         # stacks (the path normalises them to [0, 1]); the weights w come per solve (df_weights=)
         ops.check_data_term(df_loss, df_delta, "Superresolution: df_loss")
@@ -115,6 +125,23 @@ class Superresolution:
         self._drop_masks = {}        # n_drop -> bool [num_aug], frozen at first use (tf.function trace time)
 
     # -- parameter preparation ----------------------------------------------------------------
+    @staticmethod
+    def check_stop(stop_rel_tol=None, stop_patience=3, stop_every=1, stop_min_iter=0, keep_history=False):
+        """The stop_* / keep_history keywords -> None (no monitor) or the monitor dict of ops.sr_solve; ValueError on a bad
+        value, on the host.  With a tolerance the patience must be >= 1 (patience 0 never stops: say keep_history)."""
+        if not isinstance(keep_history, (bool, np.bool_)):
+            raise ValueError(f"keep_history must be True or False, got {keep_history!r}")
+        if stop_rel_tol is None:
+            mon = ops.check_sr_monitor(dict(every=stop_every, rel_tol=0.0, patience=0, min_iter=stop_min_iter, history=True),
+                                       "Superresolution: stop")
+            ops.check_sr_monitor(dict(patience=stop_patience), "Superresolution: stop")
+            return mon if keep_history else None
+        mon = ops.check_sr_monitor(dict(every=stop_every, rel_tol=stop_rel_tol, patience=stop_patience, min_iter=stop_min_iter,
+                                        history=bool(keep_history)), "Superresolution: stop")
+        if mon["patience"] < 1:
+            raise ValueError(f"Superresolution: stop_patience must be >= 1 with stop_rel_tol, got {stop_patience!r}")
+        return mon
+
     @property
     def _lambdas(self):
         return (self.lambda_df, self.lambda_tv, self.lambda_L2, self.lambda_L1)
@@ -309,6 +336,12 @@ class Superresolution:
             kw["tv_weights"] = self._tv_weights(tv_guide, b, dev)
         if self._data_term() is not None or wts is not None:
             kw.update(data_term=self._data_term(), weights=wts)
+        if self.monitor is not None:
+            # the schedule above covers all num_iter iterations whether an image stops or not: the optimiser's step counter
+            # never depends on a device result
+            x, terms, self.last_trace = ops.sr_solve(x, copies, rot, tr, irot, itr, alphas_dev, self._lambdas,
+                                                     monitor=self.monitor, **kw)
+            return x, terms
         if not self.verbose:
             return ops.sr_solve(x, copies, rot, tr, irot, itr, alphas_dev, self._lambdas, **kw)
         # superresolution.py:130-131 prints the loss of iteration i (evaluated before that iteration's update) for

@@ -281,6 +281,61 @@ int asr_sr_solve_dt_f32(float* x, const float* y, const float* rot_tf, const flo
                         int h, int w, float lambda_df, float lambda_tv, float lambda_l2, float lambda_l1,
                         const asr_sr_config* cfg, const asr_sr_data_term* dt, asr_stream_t stream);
 
+/* --- convergence monitor: a reproducible loss trace and a per-image stop rule --------------------------------------
+ * asr_sr_solve_mon_f32 is asr_sr_solve_dt_f32 (dt may be {ASR_DF_L2, no weights}: every combination of the solver is
+ * reachable) that evaluates the loss every `every` iterations, records it, and freezes each image of the batch by itself
+ * once its loss has stalled.  The whole loop is enqueued as before: the rule runs on the device, the host never waits.
+ *
+ *   Loss terms.  The four terms of asr_sr_loss_terms_dt_f64 for the current x, before the iteration's update: the same
+ *     float32 summands, statement for statement (bilateral TV: the float64 product of its two float32 factors, which is
+ *     exact), accumulated in float64 -- but WITHOUT floating-point atomics and in one fixed order:
+ *       image b's P elements (its n*h*w residuals for term 0, its H*W pixels for terms 1..3), p = 0 .. P-1, are dealt to
+ *       256 workgroups of 256 threads; thread t of workgroup g adds the summands of p = g*256 + t + k*65536, k = 0, 1, ...,
+ *       in rising p; a wave adds its 64 lanes by the tree s[l] += s[l + o] for o = 32, 16, 8, 4, 2, 1; a workgroup adds its
+ *       four waves as ((w0 + w1) + w2) + w3: partial g, written to the workspace; one lane adds the 256 partials of a term
+ *       in index order, from 0.
+ *     The terms of image b depend on image b's data alone: the same bits from call to call, alone or inside any batch,
+ *     for any plane_chunk.
+ *   Scalar loss, in float64, each operation rounding by itself (no contraction), the lambdas the float32 arguments widened:
+ *       L = ((lambda_df*t0 + lambda_tv*t1) + lambda_l2*t2),  then  L = L + lambda_l1*t3  only when lambda_l1 > 0.
+ *   Stop rule, per image (Keras' EarlyStopping with a relative min_delta).  best = +inf, stall = 0 on entry.  Iteration
+ *     it (0-based) is an evaluation when it % every == 0; its loss L is that of the x before update `it`.
+ *       bar = (best == +inf) ? +inf : best - rel_tol*|best|          (float64; inf - tol*inf would be NaN)
+ *       if (L < bar) { best = L; stall = 0; } else stall += 1;        (false for a NaN L, and for L = +inf)
+ *       the image stops at the first evaluation with patience >= 1, stall >= patience and it >= min_iter:
+ *       iters_done[b] = it, and no update from `it` on is applied to it.  An image that never stops: iters_done[b] = num_iter.
+ *     A stopped image is frozen: its workgroups in the forward and gradient-plane kernels return at once, those of the
+ *     update kernel carry x over and touch nothing else (not m, v, vhat).  Hence, bit for bit: x, m, v, vhat of image b equal
+ *     image b of the same batch through asr_sr_solve_dt_f32 with num_iter = iters_done[b] and the first iters_done[b] rows of
+ *     alphas; with patience = 0 that is the unmonitored solve itself.
+ *   Outputs.  history (optional) [ceil(num_iter / every), batch, 4] float64: row e holds the terms of every image still
+ *     running at evaluation e; the call first fills it with 0xFF bytes, so the rows after an image's stop read NaN.
+ *     last_loss_terms (optional): the terms of the stopping evaluation for a stopped image -- the loss of the x that is
+ *     returned --, the terms of the last iteration for the others, from the same reproducible sums.
+ *   Optimiser counter.  alphas is prepared by the host before the solve, for all num_iter iterations; a stopped image leaves
+ *     its remaining rows unused.  The caller's persistent step counter therefore advances by num_iter per solve, stop or no
+ *     stop: it must not come to depend on a device result.
+ *   Refusals, before any launch, outputs untouched: every refusal of asr_sr_solve_dt_f32; mon NULL, every < 1, rel_tol
+ *     negative or not finite, patience < 0, min_iter < 0, iters_done NULL -> ASR_ERR_INVALID_ARG. */
+typedef struct asr_sr_monitor {
+    int every;            /* >= 1: iteration it (0-based) is an evaluation when it % every == 0 */
+    double rel_tol;       /* >= 0, finite; 0 with patience 0 = trace only, never stop */
+    int patience;         /* >= 1 to stop; 0 = never stop */
+    int min_iter;         /* >= 0: no stop before this iteration */
+    double* history;      /* device [ceil(num_iter/every), batch, 4] or NULL */
+    int32_t* iters_done;  /* device [batch]: updates applied to each image */
+} asr_sr_monitor;
+
+/* Workspace of asr_sr_solve_mon_f32: that of asr_sr_solve_workspace_bytes_dt plus the partial sums and the rule's state. */
+size_t asr_sr_solve_workspace_bytes_mon(int batch, int n, int H, int W, int h, int w, const asr_sr_config* cfg);
+
+int asr_sr_solve_mon_f32(float* x, const float* y, const float* rot_tf, const float* trans_tf, const float* inv_rot_tf,
+                         const float* inv_trans_tf, float* m, float* v, float* vhat, const float* alphas, int num_iter,
+                         double* last_loss_terms, void* workspace, size_t workspace_bytes, int batch, int n, int H, int W,
+                         int h, int w, float lambda_df, float lambda_tv, float lambda_l2, float lambda_l1,
+                         const asr_sr_config* cfg, const asr_sr_data_term* dt, const asr_sr_monitor* mon,
+                         asr_stream_t stream);
+
 /* out[b] = max / mean over copies of rotate(translate(resize(y[b,i], (H,W)), trans_tf), rot_tf)
  * -- max_superresolution / mean_superresolution, superresolution.py:139-161 (trans_tf built
  * from -shifts, rot_tf from -angles).  out [batch,H,W]; (H, W) need not be a multiple of (h, w).  The maximum runs

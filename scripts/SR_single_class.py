@@ -35,12 +35,29 @@ def main():
     ap.add_argument("--trim", type=float, default=0.1, help="fraction of the copies the trimmed mean drops at each end")
     ap.add_argument("--df_loss", choices=["l2", "l1", "huber"], default="l2", help="data term of the iterative solve: l2 (the reference's), l1, or huber with threshold --df_delta")
     ap.add_argument("--df_delta", type=float, default=0.1, help="Huber threshold, in units of the stacks (normalised to [0, 1]); finite, > 0")
+    ap.add_argument("--sr_stop_tol", type=float, default=None,
+                    help="stop each image's iterative solve once its loss has not improved by this relative amount (finite, >= 0; e.g. 1e-4)")
+    ap.add_argument("--sr_stop_patience", type=int, default=None, help="evaluations in a row without that improvement before a solve stops (default 3)")
+    ap.add_argument("--sr_stop_every", type=int, default=None, help="evaluate the loss every this many iterations (default 1)")
+    ap.add_argument("--sr_stop_min_iter", type=int, default=None, help="no solve stops before this iteration (default 0)")
     args = ap.parse_args()
     from asr_amd.ops import check_data_term
+    from asr_amd.superresolution_scripts.superresolution import Superresolution as _Sr
     try:
         check_data_term(args.df_loss, args.df_delta, "--df_loss/--df_delta")
     except ValueError as e:
         ap.error(str(e))
+    stop_kw = {k: v for k, v in (("stop_patience", args.sr_stop_patience), ("stop_every", args.sr_stop_every),
+                                 ("stop_min_iter", args.sr_stop_min_iter)) if v is not None}
+    if args.sr_stop_tol is None:
+        if stop_kw:
+            ap.error("--sr_stop_patience, --sr_stop_every and --sr_stop_min_iter need --sr_stop_tol")
+    else:
+        stop_kw["stop_rel_tol"] = args.sr_stop_tol
+        try:
+            _Sr.check_stop(**stop_kw)
+        except ValueError as e:
+            ap.error(f"--sr_stop_*: {e}")
     extra = tuple(t for t in args.extra_sr_types.split(",") if t)
     out_dir = args.out or os.path.join(ROOT, "data", "superres_root", "superres_output")
 
@@ -58,7 +75,7 @@ def main():
     sr = Superresolution(lambda_df=HYPER["lambda_df"], lambda_tv=HYPER["lambda_tv"], lambda_L2=HYPER["lambda_L2"],
                          lambda_L1=HYPER["lambda_L1"], num_iter=HYPER["num_iter"], num_aug=args.num_aug,
                          optimizer=optimizer_obj, feature_size=(args.feature_size, args.feature_size), trim=args.trim,
-                         cover=args.cover, df_loss=args.df_loss, df_delta=args.df_delta)
+                         cover=args.cover, df_loss=args.df_loss, df_delta=args.df_delta, **stop_kw)
     paths = interchange_files(args.data)[:args.num_samples]
     res = evaluate_precomputed(sr, paths, args.gt, args.standard, num_aug=args.num_aug, class_id=args.class_id,
                                th_factor=args.th_factor, img_size=IMG_SIZE, out_dir=out_dir, rank=rank, world=world,

@@ -117,6 +117,12 @@ parser.add_argument("--df_loss", choices=["l2", "l1", "huber"], default="l2", he
 parser.add_argument("--df_delta", type=float, default=0.1, help="Huber threshold, in units of the stacks (normalised to [0, 1]); finite, > 0")
 parser.add_argument("--df_weights", choices=["maxprob", "margin"], default=None,
                     help="weight every measurement of the solve's data term by the network's confidence there")
+parser.add_argument("--sr_stop_tol", type=float, default=None,
+                    help="stop each class's iterative solve once its loss has not improved by this relative amount (finite, >= 0; e.g. 1e-4)")
+parser.add_argument("--sr_stop_patience", type=int, default=None, help="evaluations in a row without that improvement before a solve stops (default 3)")
+parser.add_argument("--sr_stop_every", type=int, default=None, help="evaluate the loss every this many iterations (default 1)")
+parser.add_argument("--sr_stop_min_iter", type=int, default=None, help="no solve stops before this iteration (default 0)")
+parser.add_argument("--sr_iters_out", default=None, help="CSV file (image, class, iterations) of the iterations each solve ran; needs --sr_stop_tol")
 parser.add_argument("--crf_iters", type=int, default=None,
                     help="decide the SR label maps with the windowed CRF of this many mean-field iterations (0..32)")
 parser.add_argument("--crf_radius", type=int, default=None, help="the CRF's window radius (1..7, default 3)")
@@ -151,7 +157,7 @@ def main():
     from asr_amd.evaluation import (LABELMAP_KEYS, best_threshold_factors, dataset_miou, evaluate_labelmaps,
                                     write_confusion_csv, write_confusion_metrics_csv, write_labelmap_csv,
                                     write_coverage_csv, write_labelmap_threshold_csv, write_regions_csv, write_segments_csv,
-                                    write_trimap_csv)
+                                    write_sr_iters_csv, write_trimap_csv)
     from asr_amd.ops import check_coverages, check_crf, check_data_term, check_min_region, check_segments, check_tv_beta
     from asr_amd.model import DeeplabV3Plus
     from asr_amd.pipeline import HotPath
@@ -217,6 +223,18 @@ def main():
         check_data_term(args.df_loss, args.df_delta, "--df_loss/--df_delta")
     except ValueError as e:
         parser.error(str(e))
+    stop_flags = {"patience": args.sr_stop_patience, "every": args.sr_stop_every, "min_iter": args.sr_stop_min_iter}
+    sr_stop = None
+    if args.sr_stop_tol is None:
+        if args.sr_iters_out or any(v is not None for v in stop_flags.values()):
+            parser.error("--sr_stop_patience, --sr_stop_every, --sr_stop_min_iter and --sr_iters_out need --sr_stop_tol")
+    else:
+        sr_stop = dict({k: v for k, v in stop_flags.items() if v is not None}, rel_tol=args.sr_stop_tol)
+        try:
+            if HotPath.check_sr_stop(sr_stop)["patience"] < 1:
+                raise ValueError("--sr_stop_patience must be >= 1")
+        except ValueError as e:
+            parser.error(f"--sr_stop_*: {e}")
     crf_flags = {"radius": args.crf_radius, "dilation": args.crf_dilation, "w_app": args.crf_w_app, "w_smooth": args.crf_w_smooth,
                  "theta_pos": args.crf_theta_pos, "theta_rgb": args.crf_theta_rgb, "theta_smooth": args.crf_theta_smooth,
                  "tau": args.crf_tau, "standard_conf": args.crf_standard_conf}
@@ -264,6 +282,7 @@ def main():
                          lambda_L1=HYPER["lambda_L1"], num_iter=args.num_iter, num_aug=args.num_aug, optimizer=opt,
                          feature_size=(feat, feat), output_size=IMG_SIZE, df_loss=args.df_loss, df_delta=args.df_delta)
     path = HotPath(model, sr, mode=args.mode, th_factor=args.th_factor, batch_size=BATCH_SIZE)
+    sr_iters = []
     out = evaluate_labelmaps(path, paths, gts, class_ids, num_aug=args.num_aug, angle_max=args.angle_max,
                              shift_max=args.shift_max, img_size=IMG_SIZE, rank=rank, world=world, seed=SEED,
                              prune=not args.no_prune, save_dir=args.save_dir, band_widths=bands,
@@ -275,8 +294,15 @@ def main():
                              **(dict(crf=crf) if crf is not None else {}),
                              **(dict(coverages=covs, uncertainty_dir=args.uncertainty_dir) if covs is not None else {}),
                              **(dict(min_region=min_region) if min_region is not None else {}),
-                             **(dict(segments=segments) if segments is not None else {}))
+                             **(dict(segments=segments) if segments is not None else {}),
+                             **(dict(sr_stop=sr_stop, sr_iters=sr_iters) if sr_stop is not None else {}))
     rows, counts = out.rows, out.counts
+    if args.sr_iters_out:             # every rank holds the solves of its own images
+        stem, ext = os.path.splitext(args.sr_iters_out)
+        iters_path = args.sr_iters_out if world == 1 else f"{stem}.rank{rank}{ext}"
+        os.makedirs(os.path.dirname(os.path.abspath(iters_path)), exist_ok=True)
+        write_sr_iters_csv(iters_path, sr_iters)
+        print(f"Wrote {iters_path}")
     if rank == 0:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         write_labelmap_csv(args.out, counts, rows)
