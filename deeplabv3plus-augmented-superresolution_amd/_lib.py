@@ -44,6 +44,8 @@ MAX_SEGMENT_LABELS, SEGMENTS_IOU_ONE = 64, 1 << 30               # ASR_SEGMENTS_
 OPM_MODES = {"argmax": 0, "slice": 1, "slice_max": 2}     # ASR_OPM_*
 
 OPT_ADAM, OPT_SGD, OPT_ADAGRAD, OPT_ADADELTA, OPT_ADAMAX = 0, 1, 2, 3, 4
+OPT_PRIMAL_DUAL = 5            # ASR_OPT_PRIMAL_DUAL: the solves only (include/asr_hip.h, "primal-dual")
+MAX_BOUND_ITERS = 64           # asr_sr_data_bound_f32: iters in 1..64
 PRIOR_TV, PRIOR_BTV = 0, 1
 
 
@@ -111,6 +113,8 @@ SIGNATURES = {
     "asr_sr_solve_dt_f32": (_i, [_vp] * 10 + [_i, _vp, _vp, _sz] + [_i] * 6 + [_fl] * 4 + [_cfg, _dt, _vp]),
     "asr_sr_solve_workspace_bytes_mon": (_sz, [_i] * 6 + [_cfg]),
     "asr_sr_solve_mon_f32": (_i, [_vp] * 10 + [_i, _vp, _vp, _sz] + [_i] * 6 + [_fl] * 4 + [_cfg, _dt, _mon, _vp]),
+    "asr_sr_data_bound_workspace_bytes": (_sz, [_i] * 6 + [_cfg]),
+    "asr_sr_data_bound_f32": (_i, [_vp] * 6 + [_i, _i, _vp, _sz] + [_i] * 6 + [_fl, _cfg, _vp]),
     "asr_realign_max_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "asr_realign_mean_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "asr_realign_max_mean_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),

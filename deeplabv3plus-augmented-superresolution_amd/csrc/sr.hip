@@ -752,6 +752,125 @@ __global__ __launch_bounds__(64) void sr_affine_flags_kernel(const float* __rest
     if (threadIdx.x == 0) flags[b] = all ? 1 : 0;
 }
 
+// The data-term gradient of HR pixel (X, Y) of image b after the copies [n0, n0 + cn) of a chunk: the running sum of the chunks
+// before (acc; +0 for the first) plus this chunk's rotation taps, in copy order: the gather of sr_backward_gather_kernel below,
+// statement for statement, for the primal-dual kernel (that kernel keeps its own text: factored out, its machine code moved).
+__device__ __forceinline__ float sr_gather_copies(const float* __restrict__ gr_planes, const float* __restrict__ inv_rot_tf,
+                                                  const float* __restrict__ acc, const int* __restrict__ affine_flags,
+                                                  const SrDims& d, int b, int X, int Y, int64_t o, int n0, int cn) {
+    const int H = d.H, W = d.W, WP = W + 2 * kGrPadX;
+    const size_t plane = sr_gr_plane_elems(H, W);
+    const float* const planes = gr_planes + (size_t)b * cn * plane;
+    const float* const tfs = inv_rot_tf + ((int64_t)b * d.n + n0) * 8;
+    const float fx = (float)X, fy = (float)Y;
+    float g_df = (n0 == 0) ? 0.0f : acc[o];
+    int n = 0;
+    if (affine_flags[b]) {       // the copies K at a time, branch-free: 2 K loads in flight, only the final adds are a chain
+        for (; n + 8 <= cn; n += 8) g_df = sr_gather_chunk<8, true>(g_df, tfs + n * 8, planes + n * plane, plane, WP, H, W, fx, fy);
+        if (n + 4 <= cn) { g_df = sr_gather_chunk<4, true>(g_df, tfs + n * 8, planes + n * plane, plane, WP, H, W, fx, fy); n += 4; }
+        for (; n < cn; ++n) g_df = sr_gather_chunk<1, true>(g_df, tfs + n * 8, planes + n * plane, plane, WP, H, W, fx, fy);
+    } else {
+        for (; n < cn; ++n) g_df = sr_gather_chunk<1, false>(g_df, tfs + n * 8, planes + n * plane, plane, WP, H, W, fx, fy);
+    }
+    return g_df;
+}
+
+// ---- primal-dual update (ASR_OPT_PRIMAL_DUAL; include/asr_hip.h, "primal-dual": the rule, statement for statement) --------
+// py / px: the dual planes before the iteration, py_new / px_new: after it -- other buffers, because a pixel rebuilds the new
+// duals of its upper and left neighbours from their OLD values (a Jacobi step: nothing read here is written in this launch).
+struct SrPd {
+    const float* py;          // [batch, H, W]: the dual of the jump (Y,X) -> (Y+1,X)
+    const float* px;          //                the dual of the jump (Y,X) -> (Y,X+1)
+    float* py_new;
+    float* px_new;
+    float dual_ratio;         // cfg->c0: sigma = dual_ratio / tau
+};
+
+template <bool WTV>
+__device__ __forceinline__ void sr_pd_update(const float* __restrict__ x, float* __restrict__ x_new, const SrPd& pd,
+                                             const float* __restrict__ alphas, const SrDims& d, int b, int X, int Y, float g_df,
+                                             float lambda_tv, float two_lambda_l2, float lambda_l1, const SrTvW& tw,
+                                             float* __restrict__ x_bordered_out) {
+    const int H = d.H, W = d.W;
+    const int64_t img_o = (int64_t)b * H * W;
+    const float* img = x + img_o;
+    const float* pyo = pd.py + img_o;
+    const float* pxo = pd.px + img_o;
+    const int p = Y * W + X;
+    const float xc = img[p];
+    const float tau = alphas[b];
+    const float sigma = pd.dual_ratio / tau;
+    // the box of each dual: lambda_tv, or (lambda_tv * w) of the edge it belongs to
+    float by = lambda_tv, bx = lambda_tv, by_up = lambda_tv, bx_left = lambda_tv;
+    if (WTV) {
+        const float* wyp = tw.wy + (int64_t)b * tw.stride;
+        const float* wxp = tw.wx + (int64_t)b * tw.stride;
+        by = lambda_tv * wyp[p];
+        bx = lambda_tv * wxp[p];
+        if (Y > 0) by_up = lambda_tv * wyp[p - W];
+        if (X > 0) bx_left = lambda_tv * wxp[p - 1];
+    }
+    const float dY = (Y < H - 1) ? img[p + W] - xc : 0.0f;
+    const float dX = (X < W - 1) ? img[p + 1] - xc : 0.0f;
+    const float py0 = pyo[p], px0 = pxo[p];
+    const float py1 = fminf(fmaxf(py0 + sigma * dY, -by), by);
+    const float px1 = fminf(fmaxf(px0 + sigma * dX, -bx), bx);
+    const float qy = 2.0f * py1 - py0;
+    const float qx = 2.0f * px1 - px0;
+    float div = -qy - qx;
+    if (Y > 0) {                                   // the upper neighbour's new dual, from its old one
+        const float pu0 = pyo[p - W];
+        const float pu1 = fminf(fmaxf(pu0 + sigma * (xc - img[p - W]), -by_up), by_up);
+        div += 2.0f * pu1 - pu0;
+    }
+    if (X > 0) {                                   // the left neighbour's
+        const float pl0 = pxo[p - 1];
+        const float pl1 = fminf(fmaxf(pl0 + sigma * (xc - img[p - 1]), -bx_left), bx_left);
+        div += 2.0f * pl1 - pl0;
+    }
+    const float g = g_df + div + two_lambda_l2 * xc;
+    const float u = xc - g * tau;
+    float xn = u;
+    if (lambda_l1 > 0.0f) {
+        const float t = tau * lambda_l1;
+        xn = (u > t) ? u - t : ((u < -t) ? u + t : 0.0f);
+    }
+    const int64_t o = img_o + p;
+    pd.py_new[o] = py1;
+    pd.px_new[o] = px1;
+    x_new[o] = xn;
+    x_bordered_out[(size_t)b * sr_gr_plane_elems(H, W) + (size_t)(Y + kGrPadY) * (W + 2 * kGrPadX) + (X + kGrPadX)] = xn;
+}
+
+// sr_backward_gather_kernel with the primal-dual update in the last chunk.  MON: a frozen image's workgroups carry x AND both
+// dual planes over to the other buffers, and touch nothing else.
+template <bool WTV, bool MON = false>
+__global__ __launch_bounds__(256) void sr_backward_gather_pd_kernel(
+    const float* __restrict__ x, float* __restrict__ x_new, const float* __restrict__ gr_planes,
+    const float* __restrict__ inv_rot_tf, SrPd pd, const float* __restrict__ alphas, SrDims d, float lambda_tv,
+    float two_lambda_l2, float lambda_l1, float* __restrict__ x_bordered_out, float* __restrict__ acc, int n0, int cn,
+    const int* __restrict__ affine_flags, SrTvW tw, SrMonArg<MON> mon) {
+    const int X = blockIdx.x * 64 + threadIdx.x;
+    const int Y = blockIdx.y * 4 + threadIdx.y;
+    const int b = blockIdx.z;
+    const int H = d.H, W = d.W;
+    if (X >= W || Y >= H) return;
+    const int64_t o = ((int64_t)b * H + Y) * W + X;
+    if constexpr (MON) {
+        if (mon.stopped[b]) {
+            if (n0 + cn >= d.n) {
+                x_new[o] = x[o];
+                pd.py_new[o] = pd.py[o];
+                pd.px_new[o] = pd.px[o];
+            }
+            return;
+        }
+    }
+    const float g_df = sr_gather_copies(gr_planes, inv_rot_tf, acc, affine_flags, d, b, X, Y, o, n0, cn);
+    if (n0 + cn < d.n) { acc[o] = g_df; return; }
+    sr_pd_update<WTV>(x, x_new, pd, alphas, d, b, X, Y, g_df, lambda_tv, two_lambda_l2, lambda_l1, tw, x_bordered_out);
+}
+
 // The copies are taken in chunks [n0, n0 + cn) (one launch per chunk, the chunk's planes written by the K_gt launch before
 // it): the running sum of the data-term gradient crosses the launches through `acc` [batch, H, W] as a float32 -- the same
 // sequence of float32 additions, in copy order, as one pass over all copies, so the result does not depend on the chunking.
@@ -1429,11 +1548,20 @@ extern "C" int asr_sr_forward_residual_dt_f32(const float* x, const float* y, co
 namespace {
 
 // asr_sr_config -> kernel argument; validates the host-side choices
+// pd: what the caller does with ASR_OPT_PRIMAL_DUAL -- kPdUnknown (the explicit one-step entry points: the rule does not exist
+// for them, they answer what they always answered to optimizer 5), kPdPriorOnly (the loss terms: only the prior is read) or
+// kPdSolve (the solves: the rule's own refusals apply).
+enum SrPdUse { kPdUnknown, kPdPriorOnly, kPdSolve };
 int make_step(const char* fn, const asr_sr_config* cfg, bool need_update, const float* m, const float* v, const float* vhat,
-              SrStep* st) {
+              SrStep* st, SrPdUse pd = kPdUnknown) {
     ASR_REQUIRE(cfg, "%s: null config", fn);
-    ASR_REQUIRE(cfg->optimizer >= ASR_OPT_ADAM && cfg->optimizer <= ASR_OPT_ADAMAX, "%s: unknown optimizer %d", fn, cfg->optimizer);
+    const int last = (pd == kPdUnknown) ? ASR_OPT_ADAMAX : ASR_OPT_PRIMAL_DUAL;
+    ASR_REQUIRE(cfg->optimizer >= ASR_OPT_ADAM && cfg->optimizer <= last, "%s: unknown optimizer %d", fn, cfg->optimizer);
     ASR_REQUIRE(cfg->prior == ASR_PRIOR_TV || cfg->prior == ASR_PRIOR_BTV, "%s: unknown prior %d", fn, cfg->prior);
+    if (cfg->optimizer == ASR_OPT_PRIMAL_DUAL && pd == kPdSolve) {
+        ASR_UNSUPPORTED(cfg->prior == ASR_PRIOR_BTV, "%s: the primal-dual rule needs ASR_PRIOR_TV (bilateral TV has no dual form here)", fn);
+        ASR_REQUIRE(cfg->c0 > 0.0f && cfg->c0 <= 0.0625f, "%s: primal-dual dual ratio c0=%g must be in (0, 1/16]", fn, (double)cfg->c0);
+    }
     st->optimizer = cfg->optimizer; st->flag = cfg->flag; st->c0 = cfg->c0; st->c1 = cfg->c1; st->c2 = cfg->c2;
     st->prior = cfg->prior; st->btv_shift = 0;
     for (int k = 0; k < 9; ++k) st->btv_w[k] = 0.0f;
@@ -1513,7 +1641,7 @@ int sr_loss_terms_impl(const char* fn, const float* x, const float* resid, doubl
     ASR_REQUIRE(x && resid && terms, "%s: null pointer", fn);
     ASR_REQUIRE(batch > 0 && batch <= 65535, "%s: bad batch %d", fn, batch);
     SrStep st;
-    int rc = make_step(fn, cfg, false, nullptr, nullptr, nullptr, &st);
+    int rc = make_step(fn, cfg, false, nullptr, nullptr, nullptr, &st, kPdPriorOnly);
     if (rc != ASR_OK) return rc;
     SrTvW tw;
     rc = make_tv_weights(fn, cfg, wa, H, W, &tw);
@@ -1594,8 +1722,17 @@ extern "C" size_t asr_sr_solve_workspace_bytes(int batch, int n, int H, int W, i
     return sr_workspace_bytes(batch, n, H, W, h, w, sr_plane_chunk(batch, n, H, W, 0));
 }
 
+namespace {
+// ASR_OPT_PRIMAL_DUAL only: the second pair of dual planes [batch, H, W] (the Jacobi step's ping-pong), at the workspace's end
+size_t sr_pd_workspace_extra(const asr_sr_config* cfg, int batch, int H, int W) {
+    if (!cfg || cfg->optimizer != ASR_OPT_PRIMAL_DUAL || batch <= 0 || H <= 0 || W <= 0) return 0;
+    return sizeof(float) * 2 * (size_t)batch * H * W;
+}
+}  // namespace
+
 extern "C" size_t asr_sr_solve_workspace_bytes_cfg(int batch, int n, int H, int W, int h, int w, const asr_sr_config* cfg) {
-    return sr_workspace_bytes(batch, n, H, W, h, w, sr_plane_chunk(batch, n, H, W, cfg ? cfg->plane_chunk : 0));
+    return sr_workspace_bytes(batch, n, H, W, h, w, sr_plane_chunk(batch, n, H, W, cfg ? cfg->plane_chunk : 0)) +
+           sr_pd_workspace_extra(cfg, batch, H, W);
 }
 
 // The whole optimisation loop of augmented_superresolution (superresolution.py:120-135) as one
@@ -1786,16 +1923,19 @@ int sr_solve_impl(const char* fn, float* x, const float* y, const float* rot_tf,
     int rc = check_dims(fn, batch, n, H, W, h, w, &d);
     if (rc != ASR_OK) return rc;
     SrStep st;
-    rc = make_step(fn, cfg, true, m, v, vhat, &st);
+    rc = make_step(fn, cfg, true, m, v, vhat, &st, kPdSolve);
     if (rc != ASR_OK) return rc;
     SrTvW tw;
     rc = make_tv_weights(fn, cfg, wa, H, W, &tw);
     if (rc != ASR_OK) return rc;
+    const bool pd = cfg->optimizer == ASR_OPT_PRIMAL_DUAL;
+    ASR_UNSUPPORTED(pd && dt && dt->loss == ASR_DF_L1, "%s: the primal-dual rule needs a smooth data term (ASR_DF_L2 or ASR_DF_HUBER)", fn);
     ASR_REQUIRE(cfg->plane_chunk >= 0, "%s: plane_chunk %d < 0", fn, cfg->plane_chunk);
     const int chunk = sr_plane_chunk(batch, n, H, W, cfg->plane_chunk);
     ASR_REQUIRE((int64_t)batch * chunk <= 65535, "%s: batch*chunk=%lld exceeds 65535 (grid.z)", fn, (long long)batch * chunk);
     const size_t base = sr_workspace_bytes(batch, n, H, W, h, w, chunk);
-    const size_t need = base + (dt ? sr_dt_workspace_extra(batch, n, h, w) : 0) + (mon ? sr_mon_workspace_extra(batch) : 0);
+    const size_t pd_at = base + (dt ? sr_dt_workspace_extra(batch, n, h, w) : 0) + (mon ? sr_mon_workspace_extra(batch) : 0);
+    const size_t need = pd_at + sr_pd_workspace_extra(cfg, batch, H, W);
     if (workspace_bytes < need) {
         asr_set_error("%s: workspace %zu < required %zu bytes", fn, workspace_bytes, need);
         return ASR_ERR_WORKSPACE;
@@ -1841,6 +1981,16 @@ int sr_solve_impl(const char* fn, float* x, const float* y, const float* rot_tf,
                                            (size_t)W * sizeof(float), (size_t)W * sizeof(float), (size_t)H,
                                            hipMemcpyDeviceToDevice, s));
     }
+    // primal-dual: the duals ping-pong with x -- they sit in the caller's m (p_y) and v (p_x) whenever x sits in the caller's buffer
+    float* const p_alt = reinterpret_cast<float*>(static_cast<char*>(workspace) + pd_at);
+    SrPd duals = {m, v, p_alt, p_alt + (size_t)batch * H * W, cfg->c0};
+    auto swap_duals = [&]() {
+        if (!pd) return;
+        float* const a = const_cast<float*>(duals.py);
+        float* const c = const_cast<float*>(duals.px);
+        duals.py = duals.py_new; duals.px = duals.px_new;
+        duals.py_new = a; duals.px_new = c;
+    };
     for (int it = 0; it < num_iter; ++it) {
         const bool want_terms = last_loss_terms && it == num_iter - 1;
         if (mon) {
@@ -1876,6 +2026,14 @@ int sr_solve_impl(const char* fn, float* x, const float* y, const float* rot_tf,
                 hipLaunchKernelGGL(gr_mon, gr_grid(d, cn), dim3(64, 4), 0, s, resid, inv_trans_tf, gr, d, 2.0f * lambda_df, n0, cn,
                                    marg);
                 ASR_LAUNCH_CHECK();
+                if (pd) {
+                    const auto pd_kernel = wa.weighted ? sr_backward_gather_pd_kernel<true, true> : sr_backward_gather_pd_kernel<false, true>;
+                    hipLaunchKernelGGL(pd_kernel, gather_grid(d), dim3(64, 4), 0, s, cur, nxt, gr, inv_rot_tf, duals,
+                                       alphas + (size_t)it * batch, d, lambda_tv, 2.0f * lambda_l2, lambda_l1, xb, acc, n0, cn,
+                                       affine_flags, tw, marg);
+                    ASR_LAUNCH_CHECK();
+                    continue;
+                }
                 const auto bwd_kernel = wa.weighted ? sr_backward_gather_kernel<true, true> : sr_backward_gather_kernel<false, true>;
                 hipLaunchKernelGGL(bwd_kernel, gather_grid(d), dim3(64, 4), 0, s, cur, nxt, gr, inv_rot_tf, m, v, vhat,
                                    alphas + (size_t)it * batch, (float*)nullptr, d, lambda_tv, 2.0f * lambda_l2, lambda_l1, st, xb,
@@ -1883,6 +2041,7 @@ int sr_solve_impl(const char* fn, float* x, const float* y, const float* rot_tf,
                 ASR_LAUNCH_CHECK();
             }
             float* t = cur; cur = nxt; nxt = t;
+            swap_duals();
             continue;
         }
         if (dt) {
@@ -1904,6 +2063,14 @@ int sr_solve_impl(const char* fn, float* x, const float* y, const float* rot_tf,
             hipLaunchKernelGGL(gr_kernel, gr_grid(d, cn), dim3(64, 4), 0, s, resid, inv_trans_tf, gr, d, 2.0f * lambda_df, n0, cn,
                                SrMonArg<false>{});
             ASR_LAUNCH_CHECK();
+            if (pd) {
+                const auto pd_kernel = wa.weighted ? sr_backward_gather_pd_kernel<true> : sr_backward_gather_pd_kernel<false>;
+                hipLaunchKernelGGL(pd_kernel, gather_grid(d), dim3(64, 4), 0, s, cur, nxt, gr, inv_rot_tf, duals,
+                                   alphas + (size_t)it * batch, d, lambda_tv, 2.0f * lambda_l2, lambda_l1, xb, acc, n0, cn,
+                                   affine_flags, tw, SrMonArg<false>{});
+                ASR_LAUNCH_CHECK();
+                continue;
+            }
             const auto bwd_kernel = wa.weighted ? sr_backward_gather_kernel<true> : sr_backward_gather_kernel<false>;
             hipLaunchKernelGGL(bwd_kernel, gather_grid(d), dim3(64, 4), 0, s, cur, nxt, gr, inv_rot_tf, m, v, vhat,
                                alphas + (size_t)it * batch, (float*)nullptr, d, lambda_tv, 2.0f * lambda_l2, lambda_l1, st, xb,
@@ -1911,8 +2078,16 @@ int sr_solve_impl(const char* fn, float* x, const float* y, const float* rot_tf,
             ASR_LAUNCH_CHECK();
         }
         float* t = cur; cur = nxt; nxt = t;
+        swap_duals();
     }
-    if (cur != x) ASR_HIP_CHECK(hipMemcpyAsync(x, cur, sizeof(float) * (size_t)batch * H * W, hipMemcpyDeviceToDevice, s));
+    if (cur != x) {
+        const size_t bytes = sizeof(float) * (size_t)batch * H * W;
+        ASR_HIP_CHECK(hipMemcpyAsync(x, cur, bytes, hipMemcpyDeviceToDevice, s));
+        if (pd) {    // the duals moved with x: back into the caller's slots
+            ASR_HIP_CHECK(hipMemcpyAsync(m, duals.py, bytes, hipMemcpyDeviceToDevice, s));
+            ASR_HIP_CHECK(hipMemcpyAsync(v, duals.px, bytes, hipMemcpyDeviceToDevice, s));
+        }
+    }
     return ASR_OK;
 }
 
@@ -2024,6 +2199,139 @@ extern "C" int asr_sr_solve_mon_f32(float* x, const float* y, const float* rot_t
     return sr_solve_impl(fn, x, y, rot_tf, trans_tf, inv_rot_tf, inv_trans_tf, m, v, vhat, alphas, num_iter, last_loss_terms,
                          workspace, workspace_bytes, batch, n, H, W, h, w, lambda_df, lambda_tv, lambda_l2, lambda_l1, cfg, wa,
                          stream, &a, mon);
+}
+
+// ---- the step bound of the primal-dual rule (asr_sr_data_bound_f32; include/asr_hip.h, "primal-dual": the rule) -------------
+// One repetition is one solver iteration on v with measurements of zero -- K_fwd, K_gt and the gather kernel as they are, the
+// gather's gradient output (no prior: every lambda but lambda_df is 0) taken as w = M v -- then the two maxima and v = w / s.
+namespace {
+constexpr int kBoundMaxIters = 64, kBoundParts = 64;
+
+// maxima[b] = {max over v > 0 of w / v, max w} as the bits of floats >= 0 (their order as unsigned integers is their order as
+// floats), zeroed before the launch: integer maxima, the same bits in any order of arrival.
+__global__ __launch_bounds__(256) SR_NO_PK_F32 void sr_bound_maxima_kernel(const float* __restrict__ wv, const float* __restrict__ v,
+                                                                           unsigned* __restrict__ maxima, int64_t per_image) {
+    const int b = blockIdx.y;
+    const float* wp = wv + (int64_t)b * per_image;
+    const float* vp = v + (int64_t)b * per_image;
+    float ratio = 0.0f, top = 0.0f;
+    for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < per_image; p += (int64_t)kBoundParts * 256) {
+        const float wi = wp[p], vi = vp[p];
+        if (vi > 0.0f) ratio = fmaxf(ratio, wi / vi);
+        top = fmaxf(top, wi);
+    }
+    ratio = asr_wave_max(ratio);
+    top = asr_wave_max(top);
+    if ((threadIdx.x & 63) == 0) {
+        if (ratio > 0.0f) atomicMax(maxima + (int64_t)b * 2 + 0, __float_as_uint(ratio));
+        if (top > 0.0f) atomicMax(maxima + (int64_t)b * 2 + 1, __float_as_uint(top));
+    }
+}
+
+// v for the next repetition, plain and zero-bordered: 1 everywhere to begin with (maxima == nullptr), then w / s while s > 0
+// (s == 0: w is 0 everywhere, v stays and every later repetition finds the same maxima, the bound of the last one done)
+__global__ __launch_bounds__(256) SR_NO_PK_F32 void sr_bound_next_v_kernel(const float* __restrict__ wv, float* __restrict__ v,
+                                                                           float* __restrict__ v_bordered,
+                                                                           const unsigned* __restrict__ maxima, int H, int W) {
+    const int X = blockIdx.x * kTileX + threadIdx.x;
+    const int Y = blockIdx.y * kTileY + threadIdx.y;
+    const int b = blockIdx.z;
+    if (X >= W || Y >= H) return;
+    const int64_t o = ((int64_t)b * H + Y) * W + X;
+    float nv = 1.0f;
+    if (maxima) {
+        const float s = __uint_as_float(maxima[(int64_t)b * 2 + 1]);
+        if (!(s > 0.0f)) return;
+        nv = wv[o] / s;
+    }
+    v[o] = nv;
+    v_bordered[(size_t)b * sr_gr_plane_elems(H, W) + (size_t)(Y + kGrPadY) * (W + 2 * kGrPadX) + (X + kGrPadX)] = nv;
+}
+
+__global__ __launch_bounds__(64) void sr_bound_out_kernel(const unsigned* __restrict__ maxima, float* __restrict__ bound, int batch) {
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b < batch) bound[b] = __uint_as_float(maxima[(int64_t)b * 2]);
+}
+
+// measurements of zero + residuals + v, w, the running sum + the planes of a chunk and of v + the affine flags + the maxima
+size_t sr_bound_workspace_bytes(int batch, int n, int H, int W, int h, int w, int chunk) {
+    return sizeof(float) * (2 * (size_t)batch * n * h * w + 3 * (size_t)batch * H * W +
+                            ((size_t)batch * chunk + batch) * sr_gr_plane_elems(H, W)) +
+           sizeof(int) * (size_t)batch + sizeof(unsigned) * 2 * (size_t)kBoundMaxIters * batch;
+}
+}  // namespace
+
+extern "C" size_t asr_sr_data_bound_workspace_bytes(int batch, int n, int H, int W, int h, int w, const asr_sr_config* cfg) {
+    if (batch <= 0 || n <= 0 || H <= 0 || W <= 0 || h <= 0 || w <= 0) return 0;
+    return sr_bound_workspace_bytes(batch, n, H, W, h, w, sr_plane_chunk(batch, n, H, W, cfg ? cfg->plane_chunk : 0));
+}
+
+extern "C" int asr_sr_data_bound_f32(float* bound, const float* rot_tf, const float* trans_tf, const float* inv_rot_tf,
+                                     const float* inv_trans_tf, const float* weights, int weights_shared, int iters,
+                                     void* workspace, size_t workspace_bytes, int batch, int n, int H, int W, int h, int w,
+                                     float lambda_df, const asr_sr_config* cfg, asr_stream_t stream) {
+    const char* fn = "asr_sr_data_bound_f32";
+    ASR_REQUIRE(bound && rot_tf && trans_tf && inv_rot_tf && inv_trans_tf && workspace, "%s: null pointer", fn);
+    ASR_REQUIRE(iters >= 1 && iters <= kBoundMaxIters, "%s: iters=%d outside [1, %d]", fn, iters, kBoundMaxIters);
+    ASR_REQUIRE(lambda_df >= 0.0f && lambda_df < __builtin_inff(), "%s: lambda_df=%g must be finite and >= 0", fn, (double)lambda_df);
+    SrDims d;
+    int rc = check_dims(fn, batch, n, H, W, h, w, &d);
+    if (rc != ASR_OK) return rc;
+    const int requested = cfg ? cfg->plane_chunk : 0;
+    ASR_REQUIRE(requested >= 0, "%s: plane_chunk %d < 0", fn, requested);
+    const int chunk = sr_plane_chunk(batch, n, H, W, requested);
+    ASR_REQUIRE((int64_t)batch * chunk <= 65535, "%s: batch*chunk=%lld exceeds 65535 (grid.z)", fn, (long long)batch * chunk);
+    const size_t need = sr_bound_workspace_bytes(batch, n, H, W, h, w, chunk);
+    if (workspace_bytes < need) {
+        asr_set_error("%s: workspace %zu < required %zu bytes", fn, workspace_bytes, need);
+        return ASR_ERR_WORKSPACE;
+    }
+    hipStream_t s = asr_stream(stream);
+    const size_t lr = (size_t)batch * n * h * w, hr = (size_t)batch * H * W, pe = sr_gr_plane_elems(H, W);
+    float* const zero_y = static_cast<float*>(workspace);
+    float* const resid = zero_y + lr;
+    float* const vcur = resid + lr;
+    float* const wv = vcur + hr;
+    float* const acc = wv + hr;
+    float* const gr = acc + hr;
+    float* const vb = gr + (size_t)batch * chunk * pe;
+    int* const affine_flags = reinterpret_cast<int*>(vb + (size_t)batch * pe);
+    unsigned* const maxima = reinterpret_cast<unsigned*>(affine_flags + batch);
+    ASR_HIP_CHECK(hipMemsetAsync(zero_y, 0, sizeof(float) * lr, s));
+    ASR_HIP_CHECK(hipMemsetAsync(gr, 0, sizeof(float) * ((size_t)batch * chunk + batch) * pe, s));
+    ASR_HIP_CHECK(hipMemsetAsync(maxima, 0, sizeof(unsigned) * 2 * (size_t)iters * batch, s));
+    hipLaunchKernelGGL(sr_affine_flags_kernel, dim3((unsigned)batch), dim3(64), 0, s, inv_rot_tf, affine_flags, n);
+    ASR_LAUNCH_CHECK();
+    SrDt dt;
+    dt.loss = ASR_DF_L2; dt.delta = 0.0f; dt.w = weights; dt.w_stride = weights_shared ? 0 : (int64_t)n * h * w; dt.r_out = nullptr;
+    SrStep st = {};
+    st.optimizer = ASR_OPT_ADAM; st.prior = ASR_PRIOR_TV;
+    const SrTvW tw = {nullptr, nullptr, 0};
+    const SrGradTranslateKernel gr_kernel = sr_grad_translate_kernel_for(d.f);
+    for (int k = 0; k < iters; ++k) {
+        unsigned* const mk = maxima + (size_t)k * 2 * batch;
+        hipLaunchKernelGGL(sr_bound_next_v_kernel, hr_grid(d), kBlock, 0, s, wv, vcur, vb, k ? mk - 2 * batch : nullptr, H, W);
+        ASR_LAUNCH_CHECK();
+        hipLaunchKernelGGL((sr_forward_residual_kernel<true, true>), lr_grid(d), kBlock, 0, s, vb, zero_y, rot_tf, trans_tf, resid, d, dt,
+                           SrMonArg<false>{});
+        ASR_LAUNCH_CHECK();
+        for (int n0 = 0; n0 < n; n0 += chunk) {
+            const int cn = n - n0 < chunk ? n - n0 : chunk;
+            hipLaunchKernelGGL(gr_kernel, gr_grid(d, cn), dim3(64, 4), 0, s, resid, inv_trans_tf, gr, d, 2.0f * lambda_df, n0, cn,
+                               SrMonArg<false>{});
+            ASR_LAUNCH_CHECK();
+            hipLaunchKernelGGL(sr_backward_gather_kernel<false>, gather_grid(d), dim3(64, 4), 0, s, vcur, (float*)nullptr, gr, inv_rot_tf,
+                               (float*)nullptr, (float*)nullptr, (float*)nullptr, (const float*)nullptr, wv, d, 0.0f, 0.0f, 0.0f, st,
+                               (float*)nullptr, acc, n0, cn, affine_flags, tw, SrMonArg<false>{});
+            ASR_LAUNCH_CHECK();
+        }
+        hipLaunchKernelGGL(sr_bound_maxima_kernel, dim3(kBoundParts, batch), dim3(256), 0, s, wv, vcur, mk, (int64_t)H * W);
+        ASR_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(sr_bound_out_kernel, dim3((unsigned)asr_cdiv(batch, 64)), dim3(64), 0, s, maxima + (size_t)(iters - 1) * 2 * batch,
+                       bound, batch);
+    ASR_LAUNCH_CHECK();
+    return ASR_OK;
 }
 
 extern "C" int asr_sr_solve_f32(float* x, const float* y, const float* rot_tf, const float* trans_tf,

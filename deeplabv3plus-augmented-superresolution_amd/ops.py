@@ -176,6 +176,60 @@ def _adam_config(one_minus_beta1, one_minus_beta2, epsilon, amsgrad):
     return sr_config(_lib.OPT_ADAM, amsgrad, one_minus_beta1, one_minus_beta2, epsilon)
 
 
+PD_DUAL_RATIO = 1.0 / 16.0          # the largest dual ratio of ASR_OPT_PRIMAL_DUAL, and the one its step rule is derived for
+
+
+def check_pd(bound_iters=6, dual_ratio=PD_DUAL_RATIO, name="primal-dual"):
+    """The two parameters of the primal-dual rule -> (int, float): bound_iters an integer in 1..64, dual_ratio a finite number
+    in (0, 1/16].  Host check, before any launch (include/asr_hip.h: the rule)."""
+    import numbers
+    if not isinstance(bound_iters, numbers.Integral) or isinstance(bound_iters, bool) or not 1 <= int(bound_iters) <= _lib.MAX_BOUND_ITERS:
+        raise ValueError(f"{name}: bound iterations must be an integer in 1..{_lib.MAX_BOUND_ITERS}, got {bound_iters!r}")
+    ok = isinstance(dual_ratio, numbers.Real) and not isinstance(dual_ratio, bool) and np.isfinite(float(dual_ratio)) \
+        and 0.0 < float(np.float32(dual_ratio)) <= PD_DUAL_RATIO
+    if not ok:
+        raise ValueError(f"{name}: dual ratio must be a finite number in (0, 1/16], got {dual_ratio!r}")
+    return int(bound_iters), float(dual_ratio)
+
+
+def sr_data_bound(rot_tf, trans_tf, inv_rot_tf, inv_trans_tf, out_hw, lr_hw, lambda_df, weights=None, iters=6, cfg=None):
+    """device [B]: an upper bound on the spectral radius of the data term's gradient map, the step bound of the primal-dual
+    rule (include/asr_hip.h, "primal-dual").  The transforms [B,N,8] of the solve, out_hw = (H, W), lr_hw = (h, w); weights:
+    the data term's, [N,h,w] shared or [B,N,h,w]; cfg: its plane_chunk alone is read.  Nothing is read back."""
+    iters, _ = check_pd(iters, name="sr_data_bound")
+    if rot_tf.dim() != 3 or rot_tf.shape[-1] != 8:
+        raise AsrError(f"sr_data_bound: transforms must be [B,N,8], got {tuple(rot_tf.shape)}")
+    b, n = rot_tf.shape[:2]
+    for t, name in ((rot_tf, "rot_tf"), (trans_tf, "trans_tf"), (inv_rot_tf, "inv_rot_tf"), (inv_trans_tf, "inv_trans_tf")):
+        _check_tf(t, b, n, name)
+    (H, W), (h, w) = (int(v) for v in out_hw), (int(v) for v in lr_hw)
+    shared = 0
+    if weights is not None:
+        if not isinstance(weights, torch.Tensor) or weights.dtype != f32 or not weights.is_contiguous() or weights.device != rot_tf.device:
+            raise AsrError("sr_data_bound: weights must be a contiguous float32 tensor on the device of the transforms")
+        if tuple(weights.shape) not in ((n, h, w), (b, n, h, w)):
+            raise AsrError(f"sr_data_bound: weights must be [{n},{h},{w}] (shared) or [{b},{n},{h},{w}], got {tuple(weights.shape)}")
+        shared = int(weights.dim() == 3)
+    cfg = cfg if cfg is not None else sr_config()
+    ws_bytes = _lib.load().asr_sr_data_bound_workspace_bytes(b, n, H, W, h, w, C.byref(cfg))
+    ws = torch.empty((ws_bytes + 3) // 4, dtype=f32, device=rot_tf.device)
+    bound = torch.empty((b,), dtype=f32, device=rot_tf.device)
+    call("asr_sr_data_bound_f32", ptr(bound), ptr(rot_tf), ptr(trans_tf), ptr(inv_rot_tf), ptr(inv_trans_tf),
+         ptr(weights, allow_none=True), shared, iters, ptr(ws), C.c_size_t(ws_bytes), b, n, H, W, h, w, float(lambda_df),
+         C.byref(cfg), stream_ptr())
+    return bound
+
+
+def pd_steps(bound, lambda_l2, num_iter):
+    """device [num_iter, B]: the alphas of a primal-dual solve, tau = 1 / (bound + 2 lambda_l2) in float32 for every iteration,
+    0 where that denominator is 0.  Built on the device of bound; nothing is read back."""
+    if not isinstance(bound, torch.Tensor) or bound.dtype != f32 or bound.dim() != 1:
+        raise AsrError("pd_steps: bound must be a float32 tensor [B]")
+    den = bound + float(np.float32(2.0) * np.float32(lambda_l2))
+    tau = torch.where(den != 0, 1.0 / den, torch.zeros_like(den))
+    return tau[None].expand(int(num_iter), -1).contiguous()
+
+
 def check_tv_beta(beta, name="tv_edge_weights"):
     """beta of the edge weights: a finite number >= 0 (host check, before any launch)."""
     import numbers
@@ -361,7 +415,9 @@ def sr_solve(x, y, rot_tf, trans_tf, inv_rot_tf, inv_trans_tf, alphas, lambdas, 
     freely with tv_weights); with L2 / None and no weights the calls above are made, unchanged.
     monitor (check_sr_monitor's dict): the solve goes through asr_sr_solve_mon_f32 -- the loss terms of every `every`-th
     iteration, each image stopped by itself when its loss stalls (include/asr_hip.h: the rule) -- and the return value is
-    (x, terms, SrTrace); nothing is read back here.  Without it: the calls and the pair above, unchanged."""
+    (x, terms, SrTrace); nothing is read back here.  Without it: the calls and the pair above, unchanged.
+    cfg with _lib.OPT_PRIMAL_DUAL (sr_config(optimizer=_lib.OPT_PRIMAL_DUAL, c0=1/16)): alphas are the steps tau of pd_steps,
+    the slots m and v come back as the dual planes p_y and p_x (include/asr_hip.h, "primal-dual")."""
     b, n, H, W, h, w = _sr_dims(x, y)
     mon = check_sr_monitor(monitor, "sr_solve: monitor") if monitor is not None else None
     tvw = _tv_weights(tv_weights, x, "sr_solve") if tv_weights is not None else None

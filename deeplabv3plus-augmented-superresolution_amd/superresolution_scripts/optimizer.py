@@ -110,11 +110,34 @@ class AdamaxState(_State):
         return ops.sr_config(self.kind, False, _f32(1.0) - self.beta_1, self.beta_2, self.epsilon, use_btv)
 
 
+class PrimalDualState(_State):
+    """The primal-dual rule (not in the reference; include/asr_hip.h, "primal-dual"): no learning rate and no schedule.  The
+    step of a solve is computed on the device from that solve's own transforms and weights (ops.sr_data_bound with
+    bound_iters repetitions, then ops.pd_steps) by Superresolution._solve_batch; this object carries the two parameters and
+    the step counter, which advances by num_iter per solve like every other rule's."""
+    kind = _lib.OPT_PRIMAL_DUAL
+
+    def __init__(self, bound_iters=6, dual_ratio=ops.PD_DUAL_RATIO):
+        super().__init__(0.0)
+        self.bound_iters, dual_ratio = ops.check_pd(bound_iters, dual_ratio, "Optimizer: primal_dual")
+        self.dual_ratio = _f32(dual_ratio)
+
+    def step_size(self):
+        return _f32(0.0)             # never used: the solve builds its own steps on the device
+
+    def config(self, use_btv=False):
+        if use_btv:
+            raise ValueError("Optimizer: primal_dual needs the TV prior (use_BTV=True has no dual form here)")
+        return ops.sr_config(self.kind, False, self.dual_ratio, 0.0, 0.0, False)
+
+
 class Optimizer:
     def __init__(self, optimizer="adam", learning_rate=1e-3,
                  epsilon=1e-7, beta_1=.9, beta_2=.999, amsgrad=False,
                  initial_accumulator_value=.1, momentum=.0, nesterov=False,
-                 lr_scheduler=False, decay_steps=.5, decay_rate=100) -> None:
+                 lr_scheduler=False, decay_steps=.5, decay_rate=100, pd_bound_iters=6, pd_dual_ratio=ops.PD_DUAL_RATIO) -> None:
+        if optimizer == "primal_dual" and lr_scheduler:
+            raise ValueError("Optimizer: primal_dual has no learning rate to schedule (lr_scheduler=True)")
         self.learning_rate = learning_rate
         self.epsilon = epsilon
         self.beta_1 = beta_1
@@ -133,6 +156,8 @@ class Optimizer:
             self.optimizer = AdamaxState(learning_rate, beta_1, beta_2, epsilon)
         elif optimizer == "sgd":
             self.optimizer = SGDState(learning_rate, momentum, nesterov)
+        elif optimizer == "primal_dual":     # learning_rate is unused
+            self.optimizer = PrimalDualState(pd_bound_iters, pd_dual_ratio)
         else:   # like the reference, any other string falls through to Adam (optimizer.py:36-41)
             self.optimizer = AdamState(learning_rate, beta_1, beta_2, epsilon, amsgrad)
         self.lr_scheduler = bool(lr_scheduler)
@@ -140,6 +165,24 @@ class Optimizer:
     def lr_decay(self, iteration):
         self.optimizer.learning_rate = T.exponential_decay_lr(self.learning_rate, self.decay_steps,
                                                               self.decay_rate, iteration)
+
+    SR_OPTIMIZER_FLAGS = ("primal_dual",)      # choices of the scripts' --sr_optimizer
+
+    @classmethod
+    def from_flags(cls, hyper, sr_optimizer=None, pd_bound_iters=None, df_loss="l2"):
+        """The scripts' --sr_optimizer / --pd_bound_iters -> Optimizer.  Without --sr_optimizer: the script's own constants
+        (hyper: optimizer, learning_rate, amsgrad, lr_scheduler, decay_steps, decay_rate), as before the flag existed.
+        ValueError on a bad combination (--df_loss l1 is not smooth: the primal-dual rule refuses it), on the host."""
+        if sr_optimizer is not None and str(df_loss).lower() == "l1":
+            raise ValueError("--sr_optimizer primal_dual needs a smooth data term (--df_loss l2 or huber)")
+        if sr_optimizer is None:
+            if pd_bound_iters is not None:
+                raise ValueError("--pd_bound_iters needs --sr_optimizer primal_dual")
+            return cls(optimizer=hyper["optimizer"], learning_rate=hyper["learning_rate"], amsgrad=hyper["amsgrad"],
+                       lr_scheduler=hyper["lr_scheduler"], decay_steps=hyper["decay_steps"], decay_rate=hyper["decay_rate"])
+        if sr_optimizer not in cls.SR_OPTIMIZER_FLAGS:
+            raise ValueError(f"--sr_optimizer must be one of {cls.SR_OPTIMIZER_FLAGS}, got {sr_optimizer!r}")
+        return cls(optimizer="primal_dual", pd_bound_iters=6 if pd_bound_iters is None else pd_bound_iters)
 
     def schedule_alphas(self, num_iter):
         """float32 [num_iter] per-step scalars for one solve, advancing the global step counter exactly

@@ -20,6 +20,10 @@ of the solution is cheap across an image edge and costs full price elsewhere (in
 ``df_loss`` / ``df_delta`` (not in the reference, which carries the L1 line commented out) choose the data term sum w * rho(r):
 "l2", "l1" or "huber"; ``df_weights`` on the solves and ``loss_function`` are its per-measurement weights w, [N,h,w] or
 [B,N,h,w] on the device (include/asr_hip.h, "data term").  With "l2" and no weights the calls that ran before are made.
+
+``Optimizer("primal_dual")`` (not in the reference) swaps the update rule for the primal-dual iteration of include/asr_hip.h,
+"primal-dual": no learning rate; ``_solve_batch`` computes the step on the device from the transforms, weights and dropout
+mask it solves (ops.sr_data_bound, ops.pd_steps).  It refuses ``use_BTV`` and ``df_loss="l1"``.
 """
 from __future__ import annotations
 
@@ -330,7 +334,18 @@ class Superresolution:
         if self.num_iter == 0:
             return x, [None] * b
         state = self.optimizer.optimizer
-        alphas_dev = ops.to_device(alphas, device=dev)
+        if state.kind == _lib.OPT_PRIMAL_DUAL:
+            # no learning rate: the step comes from the transforms, weights and dropout mask actually solved, on the device
+            # (make_alphas above only advanced the step counter, by num_iter per image like every other rule)
+            if self.optimizer.lr_scheduler:
+                raise ValueError("Superresolution: primal_dual has no learning rate to schedule (lr_scheduler=True)")
+            if self.df_loss == "l1":
+                raise ValueError("Superresolution: primal_dual needs a smooth data term (df_loss 'l2' or 'huber')")
+            bound = ops.sr_data_bound(rot, tr, irot, itr, self.output_size, (h, w), self.lambda_df, weights=wts,
+                                      iters=state.bound_iters)
+            alphas_dev = ops.pd_steps(bound, self.lambda_L2, self.num_iter)
+        else:
+            alphas_dev = ops.to_device(alphas, device=dev)
         kw = dict(want_loss=True, cfg=state.config(use_btv=self.use_BTV), slot_init=state.slot_init)
         if tv_guide is not None:
             kw["tv_weights"] = self._tv_weights(tv_guide, b, dev)

@@ -134,12 +134,14 @@ int asr_sr_solve_f32(float* x, const float* y, const float* rot_tf, const float*
  *   ASR_OPT_ADAGRAD    v = accumulator (init initial_accumulator_value) -          -           epsilon   lr_t
  *   ASR_OPT_ADADELTA   v = accum, m = accum_update                     rho         1 - rho     epsilon   lr_t
  *   ASR_OPT_ADAMAX     m, v                                            1 - beta1   beta2       epsilon   lr_t / (1 - beta1^t)
+ *   ASR_OPT_PRIMAL_DUAL  m = p_y, v = p_x (the solves only; see "primal-dual" below)   dual ratio  -   -         tau
  */
 #define ASR_OPT_ADAM 0
 #define ASR_OPT_SGD 1
 #define ASR_OPT_ADAGRAD 2
 #define ASR_OPT_ADADELTA 3
 #define ASR_OPT_ADAMAX 4
+#define ASR_OPT_PRIMAL_DUAL 5
 #define ASR_PRIOR_TV 0
 #define ASR_PRIOR_BTV 1
 
@@ -335,6 +337,61 @@ int asr_sr_solve_mon_f32(float* x, const float* y, const float* rot_tf, const fl
                          int h, int w, float lambda_df, float lambda_tv, float lambda_l2, float lambda_l1,
                          const asr_sr_config* cfg, const asr_sr_data_term* dt, const asr_sr_monitor* mon,
                          asr_stream_t stream);
+
+/* --- primal-dual: a solver for "smooth term + TV" that needs no learning rate ------------------------------------------
+ * ASR_OPT_PRIMAL_DUAL is the iteration of Condat and Vu on the loss the other rules minimise by the sign subgradient: the TV
+ * term is handled through its dual variable (one plane per difference direction, each value in a box) instead of a sign, and
+ * the step comes from a bound on the data term's curvature (asr_sr_data_bound_f32) instead of a schedule.  It is accepted by
+ * asr_sr_solve_cfg_f32, _wtv_f32, _dt_f32 and _mon_f32; the launches per iteration are those of the other rules.  The rule:
+ *
+ *   Slots.  m holds p_y and v holds p_x, the dual planes [batch, H, W], zero for a fresh solve; vhat is not touched (may be NULL).
+ *   Scalars.  alphas[it,b] = tau;  c0 = the dual ratio, sigma = c0 / tau as ONE float32 division;  c1, c2 and flag are ignored.
+ *   Per pixel (Y,X), every operation rounding by itself, everything read from the x and p BEFORE the iteration (a Jacobi
+ *   step: the new duals of a pixel's neighbours are rebuilt from old values, never read from what the iteration writes):
+ *       dY  = (Y < H-1) ? x[Y+1,X] - x[Y,X] : 0            dX = (X < W-1) ? x[Y,X+1] - x[Y,X] : 0
+ *       by  = lambda_tv    (edge-weighted TV: lambda_tv * wy[Y,X], one multiply as in the weighted prior)     bx likewise
+ *       py' = fminf(fmaxf(py + sigma*dY, -by), by)         px' likewise
+ *       qy  = 2*py' - py                                   qx likewise
+ *       div = -qy[Y,X] - qx[Y,X];  if (Y > 0) div += qy[Y-1,X];  if (X > 0) div += qx[Y,X-1];
+ *       g   = g_df + div + two_lambda_l2 * x               (g_df: the data-term gradient every other rule receives)
+ *       u   = x - g * tau
+ *       x'  = lambda_l1 > 0 ? (u > t ? u - t : (u < -t ? u + t : 0)),  t = tau * lambda_l1   :   u
+ *     The solves have no grad_out; g is not returned.  The result does not depend on plane_chunk.
+ *   Workspace.  A second pair of dual planes: asr_sr_solve_workspace_bytes_cfg / _dt / _mon grow by 2 * batch * H * W floats
+ *     when cfg->optimizer is ASR_OPT_PRIMAL_DUAL, and only then.
+ *   Monitor.  A frozen image keeps x, p_y and p_x; the loss terms are those of x, as for every rule.
+ *   Refusals, before any launch, outputs untouched: the bilateral-TV prior and ASR_DF_L1 (not smooth) as data loss ->
+ *     ASR_ERR_UNSUPPORTED (Huber and weights are accepted); c0 not finite, <= 0 or > 1/16 -> ASR_ERR_INVALID_ARG.  The explicit
+ *     one-step entry points asr_sr_backward_cfg_f32 / _wtv_f32 do not know the rule (they update slots in place; a solve with
+ *     num_iter = 1 is the one-step form): optimizer 5 stays what it always was to them, "unknown optimizer 5",
+ *     ASR_ERR_INVALID_ARG.
+ *
+ *   Step bound.  Let M be the linear map v -> the data-term gradient at x = v for measurements y = 0 under ASR_DF_L2 with the
+ *     given weights (q = w * D(T(R(v))), then the gradient-plane and gather kernels with their 2*lambda_df and 0.25 factors).
+ *     Every entry of M is >= 0, so for any v > 0 the largest (Mv)_i / v_i bounds M's spectral radius from above
+ *     (Collatz-Wielandt), tighter with every application.  Per image, in float32:
+ *       v = 1 everywhere;  repeat `iters` times (1..64):
+ *           w = M v;   B = max over {i : v_i > 0} of w_i / v_i  (0 when the set is empty);   s = max_i w_i
+ *           if (s > 0) v = w / s, else stop
+ *       bound[b] = B of the last repetition done
+ *     Maxima are order-free (taken on the bits of floats >= 0, as integers: no floating-point atomics): the same bits from call
+ *     to call, alone or in any batch, for any plane_chunk.  A repetition costs one solver iteration; no y is needed.
+ *     With tau = 1 / (bound + 2*lambda_l2) and c0 = 1/16:  1/tau - 8*sigma = (bound + 2*lambda_l2) / 2, the Condat-Vu
+ *     condition for a smooth part with that Lipschitz constant and a difference operator of squared norm <= 8.  The
+ *     theorem assumes the data gradient is a true gradient (M symmetric); the registered gradient of the projective
+ *     transform is an inverse warp, not the adjoint, so the step is a heuristic and the monitor is the guard.
+ *     Refusals: null pointers (weights may be NULL), iters outside 1..64, lambda_df negative or not finite, plane_chunk < 0
+ *     -> ASR_ERR_INVALID_ARG; the shape refusals of the solves; a short workspace -> ASR_ERR_WORKSPACE. */
+
+/* Bytes of workspace asr_sr_data_bound_f32 needs (cfg: its plane_chunk, may be NULL); 0 for a size below 1. */
+size_t asr_sr_data_bound_workspace_bytes(int batch, int n, int H, int W, int h, int w, const asr_sr_config* cfg);
+
+/* bound [batch] (device): the step bound above.  weights: NULL, or [n, h, w] shared by the batch (weights_shared != 0) or
+ * [batch, n, h, w], the data term's per-measurement weights.  cfg: its plane_chunk alone is read (may be NULL). */
+int asr_sr_data_bound_f32(float* bound, const float* rot_tf, const float* trans_tf, const float* inv_rot_tf,
+                          const float* inv_trans_tf, const float* weights, int weights_shared, int iters, void* workspace,
+                          size_t workspace_bytes, int batch, int n, int H, int W, int h, int w, float lambda_df,
+                          const asr_sr_config* cfg, asr_stream_t stream);
 
 /* out[b] = max / mean over copies of rotate(translate(resize(y[b,i], (H,W)), trans_tf), rot_tf)
  * -- max_superresolution / mean_superresolution, superresolution.py:139-161 (trans_tf built

@@ -40,11 +40,16 @@ def main():
     ap.add_argument("--sr_stop_patience", type=int, default=None, help="evaluations in a row without that improvement before a solve stops (default 3)")
     ap.add_argument("--sr_stop_every", type=int, default=None, help="evaluate the loss every this many iterations (default 1)")
     ap.add_argument("--sr_stop_min_iter", type=int, default=None, help="no solve stops before this iteration (default 0)")
+    ap.add_argument("--sr_optimizer", choices=["primal_dual"], default=None,
+                    help="update rule of the iterative solve: primal_dual needs no learning rate (default: the reference's AMSGrad schedule)")
+    ap.add_argument("--pd_bound_iters", type=int, default=None, help="repetitions of the primal-dual step bound, 1..64 (default 6); needs --sr_optimizer primal_dual")
     args = ap.parse_args()
     from asr_amd.ops import check_data_term
+    from asr_amd.superresolution_scripts.optimizer import Optimizer
     from asr_amd.superresolution_scripts.superresolution import Superresolution as _Sr
     try:
         check_data_term(args.df_loss, args.df_delta, "--df_loss/--df_delta")
+        optimizer_obj = Optimizer.from_flags(HYPER, args.sr_optimizer, args.pd_bound_iters, args.df_loss)
     except ValueError as e:
         ap.error(str(e))
     stop_kw = {k: v for k, v in (("stop_patience", args.sr_stop_patience), ("stop_every", args.sr_stop_every),
@@ -64,15 +69,11 @@ def main():
     import torch
     from asr_amd import distributed as D
     from asr_amd.evaluation import evaluate_precomputed, interchange_files, mean_over_valid, valid_rows
-    from asr_amd.superresolution_scripts.optimizer import Optimizer
     from asr_amd.superresolution_scripts.superresolution import Superresolution
 
     rank, world, local_rank = D.init_from_env()
     torch.cuda.set_device(local_rank)
-    optimizer_obj = Optimizer(optimizer=HYPER["optimizer"], learning_rate=HYPER["learning_rate"], amsgrad=HYPER["amsgrad"],
-                              lr_scheduler=HYPER["lr_scheduler"], decay_steps=HYPER["decay_steps"],
-                              decay_rate=HYPER["decay_rate"])
-    sr = Superresolution(lambda_df=HYPER["lambda_df"], lambda_tv=HYPER["lambda_tv"], lambda_L2=HYPER["lambda_L2"],
+    sr =Superresolution(lambda_df=HYPER["lambda_df"], lambda_tv=HYPER["lambda_tv"], lambda_L2=HYPER["lambda_L2"],
                          lambda_L1=HYPER["lambda_L1"], num_iter=HYPER["num_iter"], num_aug=args.num_aug,
                          optimizer=optimizer_obj, feature_size=(args.feature_size, args.feature_size), trim=args.trim,
                          cover=args.cover, df_loss=args.df_loss, df_delta=args.df_delta, **stop_kw)

@@ -37,6 +37,9 @@ parser.add_argument("--th_factor", type=float, default=0.65)
 parser.add_argument("--num_iter", type=int, default=300)
 parser.add_argument("--df_loss", choices=["l2", "l1", "huber"], default="l2", help="data term of the iterative solve: l2 (the reference's), l1, or huber with threshold --df_delta")
 parser.add_argument("--df_delta", type=float, default=0.1, help="Huber threshold, in units of the stacks (normalised to [0, 1]); finite, > 0")
+parser.add_argument("--sr_optimizer", choices=["primal_dual"], default=None,
+                    help="update rule of the iterative solve: primal_dual needs no learning rate (default: the reference's AMSGrad schedule)")
+parser.add_argument("--pd_bound_iters", type=int, default=None, help="repetitions of the primal-dual step bound, 1..64 (default 6); needs --sr_optimizer primal_dual")
 parser.add_argument("--class_ids", type=int, nargs="+", default=list(range(1, 21)),
                     help="classes to evaluate (0 and 255 never count)")
 parser.add_argument("--out", default=os.path.join(ROOT, "data", "superres_root", "class_validation.csv"),
@@ -50,12 +53,16 @@ def main():
         check_data_term(args.df_loss, args.df_delta, "--df_loss/--df_delta")
     except ValueError as e:
         parser.error(str(e))
+    from asr_amd.superresolution_scripts.optimizer import Optimizer
+    try:
+        opt = Optimizer.from_flags(HYPER, args.sr_optimizer, args.pd_bound_iters, args.df_loss)
+    except ValueError as e:
+        parser.error(str(e))
     import torch
     from asr_amd import distributed as D
     from asr_amd.evaluation import class_rows, evaluate_classes, write_class_csv
     from asr_amd.model import DeeplabV3Plus
     from asr_amd.pipeline import HotPath
-    from asr_amd.superresolution_scripts.optimizer import Optimizer
     from asr_amd.superresolution_scripts.superresolution import Superresolution
     from generate_augmented_copies import list_images
 
@@ -67,8 +74,6 @@ def main():
     model = DeeplabV3Plus(input_shape=IMG_SIZE + (3,), classes=21, OS=16, last_activation=None, load_weights=True,
                           backbone=args.backbone, weights_path=args.weights).build_model(final_upsample=False)
     feat = IMG_SIZE[0] // (4 if args.backbone == "xception" else 8)
-    opt = Optimizer(optimizer=HYPER["optimizer"], learning_rate=HYPER["learning_rate"], amsgrad=HYPER["amsgrad"],
-                    lr_scheduler=HYPER["lr_scheduler"], decay_steps=HYPER["decay_steps"], decay_rate=HYPER["decay_rate"])
     sr = Superresolution(lambda_df=HYPER["lambda_df"], lambda_tv=HYPER["lambda_tv"], lambda_L2=HYPER["lambda_L2"],
                          lambda_L1=HYPER["lambda_L1"], num_iter=args.num_iter, num_aug=args.num_aug, optimizer=opt,
                          feature_size=(feat, feat), output_size=IMG_SIZE, df_loss=args.df_loss, df_delta=args.df_delta)

@@ -123,6 +123,9 @@ parser.add_argument("--sr_stop_patience", type=int, default=None, help="evaluati
 parser.add_argument("--sr_stop_every", type=int, default=None, help="evaluate the loss every this many iterations (default 1)")
 parser.add_argument("--sr_stop_min_iter", type=int, default=None, help="no solve stops before this iteration (default 0)")
 parser.add_argument("--sr_iters_out", default=None, help="CSV file (image, class, iterations) of the iterations each solve ran; needs --sr_stop_tol")
+parser.add_argument("--sr_optimizer", choices=["primal_dual"], default=None,
+                    help="update rule of the iterative solve: primal_dual needs no learning rate (default: the reference's AMSGrad schedule)")
+parser.add_argument("--pd_bound_iters", type=int, default=None, help="repetitions of the primal-dual step bound, 1..64 (default 6); needs --sr_optimizer primal_dual")
 parser.add_argument("--crf_iters", type=int, default=None,
                     help="decide the SR label maps with the windowed CRF of this many mean-field iterations (0..32)")
 parser.add_argument("--crf_radius", type=int, default=None, help="the CRF's window radius (1..7, default 3)")
@@ -221,6 +224,7 @@ def main():
             parser.error(str(e))
     try:
         check_data_term(args.df_loss, args.df_delta, "--df_loss/--df_delta")
+        opt = Optimizer.from_flags(HYPER, args.sr_optimizer, args.pd_bound_iters, args.df_loss)
     except ValueError as e:
         parser.error(str(e))
     stop_flags = {"patience": args.sr_stop_patience, "every": args.sr_stop_every, "min_iter": args.sr_stop_min_iter}
@@ -276,8 +280,6 @@ def main():
     model = DeeplabV3Plus(input_shape=IMG_SIZE + (3,), classes=21, OS=16, last_activation=None, load_weights=True,
                           backbone=args.backbone, weights_path=args.weights).build_model(final_upsample=False)
     feat = IMG_SIZE[0] // (4 if args.backbone == "xception" else 8)
-    opt = Optimizer(optimizer=HYPER["optimizer"], learning_rate=HYPER["learning_rate"], amsgrad=HYPER["amsgrad"],
-                    lr_scheduler=HYPER["lr_scheduler"], decay_steps=HYPER["decay_steps"], decay_rate=HYPER["decay_rate"])
     sr = Superresolution(lambda_df=HYPER["lambda_df"], lambda_tv=HYPER["lambda_tv"], lambda_L2=HYPER["lambda_L2"],
                          lambda_L1=HYPER["lambda_L1"], num_iter=args.num_iter, num_aug=args.num_aug, optimizer=opt,
                          feature_size=(feat, feat), output_size=IMG_SIZE, df_loss=args.df_loss, df_delta=args.df_delta)
