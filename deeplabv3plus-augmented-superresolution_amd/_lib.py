@@ -113,6 +113,9 @@ SIGNATURES = {
     "asr_sr_solve_dt_f32": (_i, [_vp] * 10 + [_i, _vp, _vp, _sz] + [_i] * 6 + [_fl] * 4 + [_cfg, _dt, _vp]),
     "asr_sr_solve_workspace_bytes_mon": (_sz, [_i] * 6 + [_cfg]),
     "asr_sr_solve_mon_f32": (_i, [_vp] * 10 + [_i, _vp, _vp, _sz] + [_i] * 6 + [_fl] * 4 + [_cfg, _dt, _mon, _vp]),
+    "asr_simplex_project_f32": (_i, [_vp, _i, _i, _i64, _vp]),
+    "asr_sr_solve_workspace_bytes_ml": (_sz, [_i] * 6 + [_cfg, _i]),
+    "asr_sr_solve_ml_f32": (_i, [_vp] * 10 + [_i, _vp, _vp, _sz] + [_i] * 6 + [_fl] * 4 + [_cfg, _dt, _mon, _i, _vp]),
     "asr_sr_data_bound_workspace_bytes": (_sz, [_i] * 6 + [_cfg]),
     "asr_sr_data_bound_f32": (_i, [_vp] * 6 + [_i, _i, _vp, _sz] + [_i] * 6 + [_fl, _cfg, _vp]),
     "asr_realign_max_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
@@ -141,6 +144,7 @@ SIGNATURES = {
     "asr_iou_counts_classes_i32": (_i, [_vp, _vp, _vp, _i64, _i, _i, _ip, _i, _vp]),
     "asr_standard_mask_classes_i32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _ip, _i, _vp]),
     "asr_fuse_labels_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _fl, _ip, _i, _vp]),
+    "asr_fuse_labels_simplex_f32": (_i, [_vp, _ip, _i, _vp, _i64, _vp]),
     "asr_fuse_labels_sweep_workspace_bytes": (_sz, [_i, _i]),
     "asr_fuse_labels_sweep_counts_f32": (_i, [_vp, _vp, _vp, _vp, _sz, _vp, _i64, _i, _i, _ip, _i, _vp]),
     "asr_standard_labels_i32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _ip, _i, _vp]),

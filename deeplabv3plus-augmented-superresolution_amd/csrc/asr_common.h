@@ -64,6 +64,13 @@ static inline hipStream_t asr_stream(asr_stream_t s) { return reinterpret_cast<h
 
 static inline int64_t asr_cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// The projection of the multi-label coupling (reduce.hip: sr_simplex_project_kernel; include/asr_hip.h: the rule), for
+// asr_simplex_project_f32 and the coupled solve of sr.hip: in place on x [groups * G, pixels]; xb (or NULL): a second destination
+// with pixel (Y, X) of plane b at xb[b * xb_plane + Y * xb_row + xb_first + X], rows of W pixels; stopped (or NULL): int [groups * G],
+// a group whose first flag is set is skipped.  The arguments are checked by the callers.  ASR_OK or ASR_ERR_HIP.
+int asr_simplex_project_launch(hipStream_t s, float* x, float* xb, int groups, int G, int64_t pixels, int W, int64_t xb_row,
+                               int64_t xb_first, int64_t xb_plane, const int* stopped);
+
 // ---- class sets of the *_classes entry points --------------------------------------------------
 // K distinct class ids, copied from the caller's host array into a kernel argument (wave-uniform, read with scalar loads).
 struct AsrClassSet {

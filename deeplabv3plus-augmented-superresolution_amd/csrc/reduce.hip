@@ -474,6 +474,102 @@ __global__ __launch_bounds__(256) void fuse_labels_kernel(const float* __restric
     }
 }
 
+// ---- multi-label coupling (include/asr_hip.h, "multi-label coupling": the projection rule, statement for statement) -------------
+// One thread per pixel of a group of G planes; plane j of the group is read and written at the same p by neighbouring lanes,
+// so every access is coalesced.  The pixel's G positive parts sit in an LDS column [G][256] (lane stride 1: no bank conflict),
+// touched by its own thread alone: no barrier.  Only a pixel with s > 1 sorts its column (insertion sort, at most G*(G-1)/2
+// moves) and reads its values once more for the result; the others write what the column holds.  Every loop is counted.
+// xb != NULL (the solve): the result also goes into the interior of the bordered copy the next forward launch reads -- pixel
+// (Y, X) of plane b at xb[b * xb_plane + Y * xb_row + xb_first + X].  The unit is built without packed f32 and without contraction.
+// stopped != NULL (the monitored solve): a stopped group -- the flag of its first member, they stop together -- is skipped.
+// A kernel of the SR solver outside the solver's unit: csrc/isa_guard.py lets any kernel named sr_* hold packed-f32 instructions
+// (sr.hip goes through the post-pass); this one must hold none, and what forbids them is THIS unit's flags (build.py: NO_PK_F32),
+// not the name.  Moved into a packed-f32 unit it would need __attribute__((target("no-packed-fp32-ops"))) as sr.hip's
+// SR_NO_PK_F32 kernels have.
+__global__ __launch_bounds__(256) void sr_simplex_project_kernel(float* __restrict__ x, float* __restrict__ xb, int groups, int G,
+                                                                 int64_t pixels, int W, int64_t xb_row, int64_t xb_first,
+                                                                 int64_t xb_plane, const int* __restrict__ stopped) {
+    extern __shared__ float sr_simplex_col[];
+    float* const col = sr_simplex_col + threadIdx.x;
+    for (int g = blockIdx.y; g < groups; g += gridDim.y) {
+        if (stopped && stopped[g * G]) continue;
+        float* const base = x + (int64_t)g * G * pixels;
+        for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < pixels; p += (int64_t)gridDim.x * 256) {
+            float s = 0.0f;                            // 0 + a_0 is a_0
+            for (int j = 0; j < G; ++j) {
+                const float v = base[(int64_t)j * pixels + p];
+                const float a = (v > 0.0f) ? v : 0.0f;
+                col[j * 256] = a;
+                s = s + a;
+            }
+            const bool over = s > 1.0f;
+            float theta = 0.0f;
+            if (over) {
+                for (int i = 1; i < G; ++i) {          // descending
+                    const float key = col[i * 256];
+                    int k = i;
+                    for (; k > 0; --k) {
+                        const float prev = col[(k - 1) * 256];
+                        if (!(prev < key)) break;
+                        col[k * 256] = prev;
+                    }
+                    col[k * 256] = key;
+                }
+                float c = 0.0f;
+                for (int k = 1; k <= G; ++k) {
+                    const float u = col[(k - 1) * 256];
+                    c = c + u;
+                    const float t = (c - 1.0f) / (float)k;
+                    if (u > t) theta = t;
+                }
+            }
+            size_t ob = 0;
+            if (xb) {
+                const int64_t Y = p / W;
+                ob = (size_t)((int64_t)g * G * xb_plane + Y * xb_row + xb_first + (p - Y * W));
+            }
+            for (int j = 0; j < G; ++j) {
+                float r;
+                if (over) {
+                    const float v = base[(int64_t)j * pixels + p];
+                    const float a = (v > 0.0f) ? v : 0.0f;
+                    r = (a > theta) ? a - theta : 0.0f;
+                } else {
+                    r = col[j * 256];
+                }
+                base[(int64_t)j * pixels + p] = r;
+                if (xb) xb[ob + (size_t)j * (size_t)xb_plane] = r;
+            }
+        }
+    }
+}
+
+// ---- label fusion of a coupled solve (asr_fuse_labels_simplex_f32; include/asr_hip.h: the rule) -----------------------------
+// The planes are shares of the pixel: s = ((S_0 + S_1) + ...) in index order, bg = 1 - s, the first k of greatest S_k wins when
+// its share exceeds the background's.  One thread per pixel, every plane read once, four classes' loads in flight.
+__global__ __launch_bounds__(256) void fuse_labels_simplex_kernel(const float* __restrict__ scores, int32_t* __restrict__ labels,
+                                                                  int64_t pixels, AsrClassSet set) {
+    const int K = set.n;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < pixels; i += (int64_t)gridDim.x * 256) {
+        float sum = 0.0f, best = 0.0f;
+        int lab = 0;
+        for (int k0 = 0; k0 < K; k0 += 4) {
+            float s[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) s[j] = (k0 + j < K) ? scores[(int64_t)(k0 + j) * pixels + i] : 0.0f;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (k0 + j < K) {
+                    sum = (k0 + j == 0) ? s[j] : sum + s[j];
+                    if (k0 + j == 0 || s[j] > best) { best = s[j]; lab = set.id[k0 + j]; }
+                }
+            }
+        }
+        const float bg = 1.0f - sum;
+        labels[i] = (best > bg) ? lab : 0;
+    }
+}
+
 // ---- label fusion swept over T threshold factors: counts only (asr_fuse_labels_sweep_counts_f32) --------------------------
 // counts[j] is what fuse_labels_kernel<false, true> leaves at th_factor = factors[j]: the same f32 product max_k * factors[j],
 // the same strict comparisons in the same order of k.  A predicted label is 0 or one of the K ids, so a workgroup counts in SLOTS
@@ -1092,6 +1188,29 @@ extern "C" int asr_fuse_labels_f32(const float* scores, const float* max_scores,
         if (truth) ASR_FUSE_LAUNCH(false, true); else ASR_FUSE_LAUNCH(false, false);
     }
 #undef ASR_FUSE_LAUNCH
+    ASR_LAUNCH_CHECK();
+    return ASR_OK;
+}
+
+int asr_simplex_project_launch(hipStream_t s, float* x, float* xb, int groups, int G, int64_t pixels, int W, int64_t xb_row,
+                               int64_t xb_first, int64_t xb_plane, const int* stopped) {
+    const int64_t blocks = asr_cdiv(pixels, 256);
+    const dim3 grid((unsigned)(blocks < 65536 ? blocks : 65536), (unsigned)(groups < 65535 ? groups : 65535));
+    hipLaunchKernelGGL(sr_simplex_project_kernel, grid, dim3(256), sizeof(float) * 256 * (size_t)G, s, x, xb, groups, G, pixels, W,
+                       xb_row, xb_first, xb_plane, stopped);
+    ASR_LAUNCH_CHECK();
+    return ASR_OK;
+}
+
+extern "C" int asr_fuse_labels_simplex_f32(const float* scores, const int* ids, int K, int32_t* labels, int64_t pixels,
+                                           asr_stream_t stream) {
+    AsrClassSet set;
+    const int rc = asr_label_set("asr_fuse_labels_simplex_f32", ids, K, 0, &set);
+    if (rc != ASR_OK) return rc;
+    ASR_REQUIRE(scores && labels, "asr_fuse_labels_simplex_f32: null pointer");
+    ASR_REQUIRE(pixels > 0, "asr_fuse_labels_simplex_f32: bad shape");
+    hipLaunchKernelGGL(fuse_labels_simplex_kernel, dim3(stream_grid(pixels)), dim3(256), 0, asr_stream(stream), scores, labels, pixels,
+                       set);
     ASR_LAUNCH_CHECK();
     return ASR_OK;
 }

@@ -1859,46 +1859,68 @@ struct SrMonEval {
     double l_df, l_tv, l_l2, l_l1;     // the float32 lambdas widened
 };
 
-// One workgroup of one wave per image: lanes 0..3 add the partials of their term in index order, lane 0 applies the rule.
+// One workgroup of one wave per group of `group` images (1 without coupling: per image): for each member in index order, lanes
+// 0..3 add the partials of their term in index order and lane 0 forms the member's loss; the group's loss is the members'
+// added in that order.  Lane 0 applies the rule to the group -- best and stall live at its first member -- and stops every
+// member together (include/asr_hip.h, "multi-label coupling": the monitor).  The branches below are uniform over the workgroup.
 __global__ __launch_bounds__(64) SR_NO_PK_F32 void sr_mon_decide_kernel(SrMonState s, int* __restrict__ iters_done,
                                                                         double* __restrict__ history,
-                                                                        double* __restrict__ last_terms, int batch, SrMonEval e) {
+                                                                        double* __restrict__ last_terms, int batch, SrMonEval e,
+                                                                        int group) {
     __shared__ double t[4];
     __shared__ double part[kMonParts * 4];
-    const int b = blockIdx.x;
-    if (s.stopped[b]) return;
-    // the image's kMonParts x 4 partials through LDS (one coalesced read instead of a chain of dependent global loads)
-    for (int i = threadIdx.x; i < kMonParts * 4; i += 64) part[i] = s.parts[(int64_t)b * kMonParts * 4 + i];
-    __syncthreads();
-    if (threadIdx.x < 4) {
-        double sum = 0.0;
-        for (int g = 0; g < kMonParts; ++g) sum += part[g * 4 + threadIdx.x];
-        t[threadIdx.x] = sum;
+    const int b0 = blockIdx.x * group;
+    if (s.stopped[b0]) return;
+    double loss = 0.0;
+    for (int j = 0; j < group; ++j) {
+        const int b = b0 + j;
+        // the image's kMonParts x 4 partials through LDS (one coalesced read instead of a chain of dependent global loads)
+        for (int i = threadIdx.x; i < kMonParts * 4; i += 64) part[i] = s.parts[(int64_t)b * kMonParts * 4 + i];
+        __syncthreads();
+        if (threadIdx.x < 4) {
+            double sum = 0.0;
+            for (int g = 0; g < kMonParts; ++g) sum += part[g * 4 + threadIdx.x];
+            t[threadIdx.x] = sum;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            if (last_terms)
+                for (int k = 0; k < 4; ++k) last_terms[(int64_t)b * 4 + k] = t[k];
+            if (e.rule && history)
+                for (int k = 0; k < 4; ++k) history[((int64_t)e.row * batch + b) * 4 + k] = t[k];
+            double lb = (e.l_df * t[0] + e.l_tv * t[1]) + e.l_l2 * t[2];
+            if (e.l_l1 > 0.0) lb = lb + e.l_l1 * t[3];
+            loss = (j == 0) ? lb : loss + lb;
+        }
+        __syncthreads();                               // part and t are rewritten for the next member
     }
-    __syncthreads();
-    if (threadIdx.x != 0) return;
-    if (last_terms)
-        for (int k = 0; k < 4; ++k) last_terms[(int64_t)b * 4 + k] = t[k];
-    if (!e.rule) return;
-    if (history)
-        for (int k = 0; k < 4; ++k) history[((int64_t)e.row * batch + b) * 4 + k] = t[k];
-    double loss = (e.l_df * t[0] + e.l_tv * t[1]) + e.l_l2 * t[2];
-    if (e.l_l1 > 0.0) loss = loss + e.l_l1 * t[3];
-    const double best = s.best[b];
+    if (threadIdx.x != 0 || !e.rule) return;
+    const double best = s.best[b0];
     // best = +inf (no evaluation yet): the threshold is +inf itself, not inf - tol * inf = NaN; a NaN loss never improves
     const double bar = (best == __builtin_inf()) ? best : best - e.rel_tol * fabs(best);
-    int stall = s.stall[b];
+    int stall = s.stall[b0];
     if (loss < bar) {
-        s.best[b] = loss;
+        s.best[b0] = loss;
         stall = 0;
     } else {
         stall += 1;
     }
-    s.stall[b] = stall;
+    s.stall[b0] = stall;
     if (e.patience >= 1 && stall >= e.patience && e.it >= e.min_iter) {
-        s.stopped[b] = 1;
-        iters_done[b] = e.it;
+        for (int j = 0; j < group; ++j) {
+            s.stopped[b0 + j] = 1;
+            iters_done[b0 + j] = e.it;
+        }
     }
+}
+
+// ---- multi-label coupling (include/asr_hip.h, "multi-label coupling") ------------------------------------------------------------
+// The projection kernel lives in reduce.hip with the other per-pixel kernels over class planes (asr_simplex_project_launch,
+// asr_common.h); here only the geometry of the bordered copy xb that it also writes inside a solve.
+int sr_simplex_project_launch(hipStream_t s, float* x, float* xb, int groups, int G, int H, int W, const int* stopped) {
+    const int64_t WP = W + 2 * kGrPadX;
+    return asr_simplex_project_launch(s, x, xb, groups, G, (int64_t)H * W, W, WP, (int64_t)kGrPadY * WP + kGrPadX,
+                                      (int64_t)sr_gr_plane_elems(H, W), stopped);
 }
 
 size_t sr_mon_workspace_extra(int batch) {
@@ -1910,7 +1932,10 @@ int sr_solve_impl(const char* fn, float* x, const float* y, const float* rot_tf,
                   const float* inv_trans_tf, float* m, float* v, float* vhat, const float* alphas, int num_iter,
                   double* last_loss_terms, void* workspace, size_t workspace_bytes, int batch, int n, int H, int W, int h, int w,
                   float lambda_df, float lambda_tv, float lambda_l2, float lambda_l1, const asr_sr_config* cfg,
-                  const SrTvWArg& wa, asr_stream_t stream, const SrDt* dt = nullptr, const asr_sr_monitor* mon = nullptr) {
+                  const SrTvWArg& wa, asr_stream_t stream, const SrDt* dt = nullptr, const asr_sr_monitor* mon = nullptr,
+                  int group = 0) {
+    // group >= 1 (asr_sr_solve_ml_f32): after the update launch of an iteration's last chunk, one projection launch over the
+    // batch's groups of `group` planes rewrites the new x and its bordered copy; the stop rule then decides per group.
     // mon (asr_sr_solve_mon_f32, always with dt): the MON instantiations of the three per-iteration kernels and, at every
     // evaluation, the two partial-sum kernels and the decision kernel between K_fwd and K_gt.  Everything is enqueued; the host
     // never learns during the solve which image has stopped.
@@ -1929,6 +1954,9 @@ int sr_solve_impl(const char* fn, float* x, const float* y, const float* rot_tf,
     rc = make_tv_weights(fn, cfg, wa, H, W, &tw);
     if (rc != ASR_OK) return rc;
     const bool pd = cfg->optimizer == ASR_OPT_PRIMAL_DUAL;
+    ASR_REQUIRE(group >= 0 && group <= ASR_MAX_CLASS_SET, "%s: group=%d outside 0..%d", fn, group, ASR_MAX_CLASS_SET);
+    ASR_REQUIRE(group == 0 || batch % group == 0, "%s: batch=%d is no multiple of group=%d", fn, batch, group);
+    ASR_UNSUPPORTED(group >= 1 && !pd, "%s: the multi-label coupling needs ASR_OPT_PRIMAL_DUAL (optimizer %d)", fn, cfg->optimizer);
     ASR_UNSUPPORTED(pd && dt && dt->loss == ASR_DF_L1, "%s: the primal-dual rule needs a smooth data term (ASR_DF_L2 or ASR_DF_HUBER)", fn);
     ASR_REQUIRE(cfg->plane_chunk >= 0, "%s: plane_chunk %d < 0", fn, cfg->plane_chunk);
     const int chunk = sr_plane_chunk(batch, n, H, W, cfg->plane_chunk);
@@ -2016,8 +2044,9 @@ int sr_solve_impl(const char* fn, float* x, const float* y, const float* rot_tf,
                 e.rule = is_eval ? 1 : 0; e.it = it; e.row = it / mon->every;
                 e.patience = mon->patience; e.min_iter = mon->min_iter; e.rel_tol = mon->rel_tol;
                 e.l_df = (double)lambda_df; e.l_tv = (double)lambda_tv; e.l_l2 = (double)lambda_l2; e.l_l1 = (double)lambda_l1;
-                hipLaunchKernelGGL(sr_mon_decide_kernel, dim3((unsigned)batch), dim3(64), 0, s, ms, mon->iters_done, mon->history,
-                                   last_loss_terms, batch, e);
+                const int members = group >= 1 ? group : 1;
+                hipLaunchKernelGGL(sr_mon_decide_kernel, dim3((unsigned)(batch / members)), dim3(64), 0, s, ms, mon->iters_done,
+                                   mon->history, last_loss_terms, batch, e, members);
                 ASR_LAUNCH_CHECK();
             }
             const SrGradTranslateMonKernel gr_mon = sr_grad_translate_mon_kernel_for(d.f);
@@ -2039,6 +2068,10 @@ int sr_solve_impl(const char* fn, float* x, const float* y, const float* rot_tf,
                                    alphas + (size_t)it * batch, (float*)nullptr, d, lambda_tv, 2.0f * lambda_l2, lambda_l1, st, xb,
                                    acc, n0, cn, affine_flags, tw, marg);
                 ASR_LAUNCH_CHECK();
+            }
+            if (group >= 1) {
+                rc = sr_simplex_project_launch(s, nxt, xb, batch / group, group, H, W, ms.stopped);
+                if (rc != ASR_OK) return rc;
             }
             float* t = cur; cur = nxt; nxt = t;
             swap_duals();
@@ -2076,6 +2109,10 @@ int sr_solve_impl(const char* fn, float* x, const float* y, const float* rot_tf,
                                alphas + (size_t)it * batch, (float*)nullptr, d, lambda_tv, 2.0f * lambda_l2, lambda_l1, st, xb,
                                acc, n0, cn, affine_flags, tw, SrMonArg<false>{});
             ASR_LAUNCH_CHECK();
+        }
+        if (group >= 1) {
+            rc = sr_simplex_project_launch(s, nxt, xb, batch / group, group, H, W, nullptr);
+            if (rc != ASR_OK) return rc;
         }
         float* t = cur; cur = nxt; nxt = t;
         swap_duals();
@@ -2159,19 +2196,41 @@ extern "C" size_t asr_sr_solve_workspace_bytes_dt(int batch, int n, int H, int W
     return asr_sr_solve_workspace_bytes_cfg(batch, n, H, W, h, w, cfg) + sr_dt_workspace_extra(batch, n, h, w);
 }
 
+namespace {
+// asr_sr_solve_dt_f32 (mon NULL) and asr_sr_solve_mon_f32 (mon given, checked here), with the group of asr_sr_solve_ml_f32
+int sr_solve_dt_entry(const char* fn, float* x, const float* y, const float* rot_tf, const float* trans_tf, const float* inv_rot_tf,
+                      const float* inv_trans_tf, float* m, float* v, float* vhat, const float* alphas, int num_iter,
+                      double* last_loss_terms, void* workspace, size_t workspace_bytes, int batch, int n, int H, int W, int h, int w,
+                      float lambda_df, float lambda_tv, float lambda_l2, float lambda_l1, const asr_sr_config* cfg,
+                      const asr_sr_data_term* dt, const asr_sr_monitor* mon, bool monitored, int group, asr_stream_t stream) {
+    SrDt a;
+    const int rc = make_data_term(fn, dt, n, h, w, &a);
+    if (rc != ASR_OK) return rc;
+    if (monitored) {
+        ASR_REQUIRE(mon, "%s: null monitor", fn);
+        ASR_REQUIRE(mon->every >= 1, "%s: monitor every=%d must be >= 1", fn, mon->every);
+        ASR_REQUIRE(mon->rel_tol >= 0.0 && mon->rel_tol < __builtin_inf(), "%s: monitor rel_tol=%g must be finite and >= 0", fn,
+                    mon->rel_tol);
+        ASR_REQUIRE(mon->patience >= 0, "%s: monitor patience=%d must be >= 0", fn, mon->patience);
+        ASR_REQUIRE(mon->min_iter >= 0, "%s: monitor min_iter=%d must be >= 0", fn, mon->min_iter);
+        ASR_REQUIRE(mon->iters_done, "%s: null pointer (monitor iters_done)", fn);
+    }
+    const SrTvWArg wa = {dt->wy, dt->wx, dt->tv_shared, dt->wy != nullptr};
+    return sr_solve_impl(fn, x, y, rot_tf, trans_tf, inv_rot_tf, inv_trans_tf, m, v, vhat, alphas, num_iter, last_loss_terms,
+                         workspace, workspace_bytes, batch, n, H, W, h, w, lambda_df, lambda_tv, lambda_l2, lambda_l1, cfg, wa,
+                         stream, &a, monitored ? mon : nullptr, group);
+}
+}  // namespace
+
 extern "C" int asr_sr_solve_dt_f32(float* x, const float* y, const float* rot_tf, const float* trans_tf,
                                    const float* inv_rot_tf, const float* inv_trans_tf, float* m, float* v, float* vhat,
                                    const float* alphas, int num_iter, double* last_loss_terms, void* workspace,
                                    size_t workspace_bytes, int batch, int n, int H, int W, int h, int w, float lambda_df,
                                    float lambda_tv, float lambda_l2, float lambda_l1, const asr_sr_config* cfg,
                                    const asr_sr_data_term* dt, asr_stream_t stream) {
-    SrDt a;
-    const int rc = make_data_term("asr_sr_solve_dt_f32", dt, n, h, w, &a);
-    if (rc != ASR_OK) return rc;
-    const SrTvWArg wa = {dt->wy, dt->wx, dt->tv_shared, dt->wy != nullptr};
-    return sr_solve_impl("asr_sr_solve_dt_f32", x, y, rot_tf, trans_tf, inv_rot_tf, inv_trans_tf, m, v, vhat, alphas, num_iter,
-                         last_loss_terms, workspace, workspace_bytes, batch, n, H, W, h, w, lambda_df, lambda_tv, lambda_l2,
-                         lambda_l1, cfg, wa, stream, &a);
+    return sr_solve_dt_entry("asr_sr_solve_dt_f32", x, y, rot_tf, trans_tf, inv_rot_tf, inv_trans_tf, m, v, vhat, alphas, num_iter,
+                             last_loss_terms, workspace, workspace_bytes, batch, n, H, W, h, w, lambda_df, lambda_tv, lambda_l2,
+                             lambda_l1, cfg, dt, nullptr, false, 0, stream);
 }
 
 extern "C" size_t asr_sr_solve_workspace_bytes_mon(int batch, int n, int H, int W, int h, int w, const asr_sr_config* cfg) {
@@ -2184,21 +2243,34 @@ extern "C" int asr_sr_solve_mon_f32(float* x, const float* y, const float* rot_t
                                     size_t workspace_bytes, int batch, int n, int H, int W, int h, int w, float lambda_df,
                                     float lambda_tv, float lambda_l2, float lambda_l1, const asr_sr_config* cfg,
                                     const asr_sr_data_term* dt, const asr_sr_monitor* mon, asr_stream_t stream) {
-    const char* fn = "asr_sr_solve_mon_f32";
-    SrDt a;
-    const int rc = make_data_term(fn, dt, n, h, w, &a);
-    if (rc != ASR_OK) return rc;
-    ASR_REQUIRE(mon, "%s: null monitor", fn);
-    ASR_REQUIRE(mon->every >= 1, "%s: monitor every=%d must be >= 1", fn, mon->every);
-    ASR_REQUIRE(mon->rel_tol >= 0.0 && mon->rel_tol < __builtin_inf(), "%s: monitor rel_tol=%g must be finite and >= 0", fn,
-                mon->rel_tol);
-    ASR_REQUIRE(mon->patience >= 0, "%s: monitor patience=%d must be >= 0", fn, mon->patience);
-    ASR_REQUIRE(mon->min_iter >= 0, "%s: monitor min_iter=%d must be >= 0", fn, mon->min_iter);
-    ASR_REQUIRE(mon->iters_done, "%s: null pointer (monitor iters_done)", fn);
-    const SrTvWArg wa = {dt->wy, dt->wx, dt->tv_shared, dt->wy != nullptr};
-    return sr_solve_impl(fn, x, y, rot_tf, trans_tf, inv_rot_tf, inv_trans_tf, m, v, vhat, alphas, num_iter, last_loss_terms,
-                         workspace, workspace_bytes, batch, n, H, W, h, w, lambda_df, lambda_tv, lambda_l2, lambda_l1, cfg, wa,
-                         stream, &a, mon);
+    return sr_solve_dt_entry("asr_sr_solve_mon_f32", x, y, rot_tf, trans_tf, inv_rot_tf, inv_trans_tf, m, v, vhat, alphas, num_iter,
+                             last_loss_terms, workspace, workspace_bytes, batch, n, H, W, h, w, lambda_df, lambda_tv, lambda_l2,
+                             lambda_l1, cfg, dt, mon, true, 0, stream);
+}
+
+// ---- multi-label coupling: the entry points (include/asr_hip.h, "multi-label coupling") ---------------------------------------------
+extern "C" int asr_simplex_project_f32(float* x, int groups, int group, int64_t pixels, asr_stream_t stream) {
+    ASR_REQUIRE(x, "asr_simplex_project_f32: null pointer");
+    ASR_REQUIRE(group >= 1 && group <= ASR_MAX_CLASS_SET, "asr_simplex_project_f32: group=%d outside 1..%d", group, ASR_MAX_CLASS_SET);
+    ASR_REQUIRE(groups >= 1 && pixels >= 1, "asr_simplex_project_f32: bad shape groups=%d pixels=%lld", groups, (long long)pixels);
+    return asr_simplex_project_launch(asr_stream(stream), x, nullptr, groups, group, pixels, 1, 0, 0, 0, nullptr);
+}
+
+extern "C" size_t asr_sr_solve_workspace_bytes_ml(int batch, int n, int H, int W, int h, int w, const asr_sr_config* cfg,
+                                                  int monitored) {
+    return monitored ? asr_sr_solve_workspace_bytes_mon(batch, n, H, W, h, w, cfg)
+                     : asr_sr_solve_workspace_bytes_dt(batch, n, H, W, h, w, cfg);
+}
+
+extern "C" int asr_sr_solve_ml_f32(float* x, const float* y, const float* rot_tf, const float* trans_tf,
+                                   const float* inv_rot_tf, const float* inv_trans_tf, float* m, float* v, float* vhat,
+                                   const float* alphas, int num_iter, double* last_loss_terms, void* workspace,
+                                   size_t workspace_bytes, int batch, int n, int H, int W, int h, int w, float lambda_df,
+                                   float lambda_tv, float lambda_l2, float lambda_l1, const asr_sr_config* cfg,
+                                   const asr_sr_data_term* dt, const asr_sr_monitor* mon, int group, asr_stream_t stream) {
+    return sr_solve_dt_entry("asr_sr_solve_ml_f32", x, y, rot_tf, trans_tf, inv_rot_tf, inv_trans_tf, m, v, vhat, alphas, num_iter,
+                             last_loss_terms, workspace, workspace_bytes, batch, n, H, W, h, w, lambda_df, lambda_tv, lambda_l2,
+                             lambda_l1, cfg, dt, mon, mon != nullptr, group, stream);
 }
 
 // ---- the step bound of the primal-dual rule (asr_sr_data_bound_f32; include/asr_hip.h, "primal-dual": the rule) -------------

@@ -309,8 +309,8 @@ def dataset_miou(counts):
 def evaluate_labelmaps(path, image_paths, gt_paths, class_ids=tuple(range(1, 21)), num_aug=100, angle_max=0.3, shift_max=30,
                        img_size=(512, 512), rank=0, world=1, seed=1234, sr_types=("aug", "max", "mean"), prune=True,
                        save_dir=None, band_widths=None, band_ignore_label=255, confusion_labels=None, th_factors=None,
-                       guide=None, df_weights=None, sr_stop=None, sr_iters=None, tv_guide=None, crf=None, min_region=None,
-                       segments=None, coverages=None, uncertainty_dir=None):
+                       guide=None, df_weights=None, sr_stop=None, sr_iters=None, couple=False, tv_guide=None, crf=None,
+                       min_region=None, segments=None, coverages=None, uncertainty_dir=None):
     """One fused label map per image and SR type (HotPath.run_image_labels) and its score.  Returns on every rank a
     LabelmapScores, the tuple (rows, counts) plus what the options below append, every entry also an attribute by the name
     given here: rows [images, 4] per-image Mean_IOU in LABELMAP_KEYS order (the reference's per-image-then-mean convention;
@@ -376,8 +376,15 @@ def evaluate_labelmaps(path, image_paths, gt_paths, class_ids=tuple(range(1, 21)
     sr_stop (run_image_labels' sr_stop: rel_tol, patience, every, min_iter): every image's "aug" solves stop class by class
     once their loss has stalled.  The return value keeps its form; sr_iters (a list) receives one row (image stem, class id,
     iterations) per image of THIS rank and solved class (write_sr_iters_csv; in slice_max a second row per class, the class
-    written "<id>_max", for its max map's solve).  The Adam bookkeeping does not change."""
+    written "<id>_max", for its max map's solve).  The Adam bookkeeping does not change.
+
+    couple (True needs the primal_dual optimizer and the argmax mode; not together with th_factors or crf): every image's "aug"
+    solve is one coupled solve over its classes and its "aug" map the threshold-free fusion of the shares (run_image_labels'
+    couple).  The return value keeps its form."""
     stop_kw = {} if path.check_sr_stop(sr_stop) is None else {"sr_stop": dict(sr_stop)}
+    path.check_couple(couple, th_factors, crf)
+    if couple:
+        stop_kw["couple"] = True
     if uncertainty_dir and coverages is None:
         raise ValueError("uncertainty_dir needs coverages: the uncertainty map is only built for the risk-coverage curve")
     opts = path.label_options(tuple(img_size) + (3,), True, band_widths, band_ignore_label, confusion_labels, th_factors,

@@ -7,6 +7,7 @@ returns device tensors.  Nothing here computes on the CPU.
 from __future__ import annotations
 
 import ctypes as C
+import numbers
 from collections import namedtuple
 
 import numpy as np
@@ -377,6 +378,31 @@ def check_sr_monitor(params, name="sr monitor"):
     return p
 
 
+def check_coupling(coupling, batch=None, cfg=None, name="coupling"):
+    """The group size of a coupled solve (include/asr_hip.h, "multi-label coupling") as an int: an integer in
+    0.._lib.MAX_CLASS_SET (0: the entry point runs the uncoupled solve); with batch, a divisor of it; with cfg, G >= 1 needs the
+    primal-dual rule.  Host only; ValueError on anything else."""
+    if not isinstance(coupling, numbers.Integral) or isinstance(coupling, bool) or not 0 <= int(coupling) <= _lib.MAX_CLASS_SET:
+        raise ValueError(f"{name}: an integer in 0..{_lib.MAX_CLASS_SET} expected, got {coupling!r}")
+    g = int(coupling)
+    if g >= 1 and batch is not None and int(batch) % g != 0:
+        raise ValueError(f"{name}: the batch of {batch} planes is no multiple of the group size {g}")
+    if g >= 1 and (cfg is None or cfg.optimizer != _lib.OPT_PRIMAL_DUAL):
+        raise ValueError(f"{name}: the coupled solve needs the primal-dual rule (sr_config(optimizer=_lib.OPT_PRIMAL_DUAL))")
+    return g
+
+
+def simplex_project(x, group):
+    """x [B, ...] float32, B a multiple of group: every pixel's `group` values of each run of `group` consecutive planes are
+    projected onto {v >= 0, sum v <= 1}, in place (asr_simplex_project_f32; the rule: include/asr_hip.h).  Returns x."""
+    if x.dim() < 2 or x.shape[0] == 0 or x.numel() == 0:
+        raise AsrError(f"simplex_project: x must be [B, ...] with B >= 1, got {tuple(x.shape)}")
+    if not isinstance(group, numbers.Integral) or isinstance(group, bool) or int(group) < 1 or x.shape[0] % int(group):
+        raise AsrError(f"simplex_project: group must be an integer >= 1 that divides the {x.shape[0]} planes, got {group!r}")
+    call("asr_simplex_project_f32", ptr(x), x.shape[0] // int(group), int(group), x.numel() // x.shape[0], stream_ptr())
+    return x
+
+
 def sr_loss_from_terms(terms, lambdas):
     """The scalar loss of the monitor from its four terms [..., 4], in float64: ((l_df*t0 + l_tv*t1) + l_L2*t2), then
     + l_L1*t3 only when l_L1 > 0, the lambdas the float32 arguments widened, every operation rounding by itself."""
@@ -405,7 +431,7 @@ class SrTrace:
 
 def sr_solve(x, y, rot_tf, trans_tf, inv_rot_tf, inv_trans_tf, alphas, lambdas, one_minus_beta1=None, one_minus_beta2=None,
              epsilon=None, amsgrad=False, want_loss=True, cfg=None, slot_init=None, state=None, tv_weights=None,
-             data_term=None, weights=None, monitor=None):
+             data_term=None, weights=None, monitor=None, coupling=None):
     """Runs alphas.shape[0] iterations in place on x.  alphas [num_iter, B] (device).  Either the Adam
     hyper-parameters (asr_sr_solve_f32) or cfg (+ slot_init = {"m"/"v"/"vhat": initial value}) for
     asr_sr_solve_cfg_f32.  state: a dict that carries the optimiser slots and the workspace from one call to the next --
@@ -417,11 +443,15 @@ def sr_solve(x, y, rot_tf, trans_tf, inv_rot_tf, inv_trans_tf, alphas, lambdas, 
     iteration, each image stopped by itself when its loss stalls (include/asr_hip.h: the rule) -- and the return value is
     (x, terms, SrTrace); nothing is read back here.  Without it: the calls and the pair above, unchanged.
     cfg with _lib.OPT_PRIMAL_DUAL (sr_config(optimizer=_lib.OPT_PRIMAL_DUAL, c0=1/16)): alphas are the steps tau of pd_steps,
-    the slots m and v come back as the dual planes p_y and p_x (include/asr_hip.h, "primal-dual")."""
+    the slots m and v come back as the dual planes p_y and p_x (include/asr_hip.h, "primal-dual").
+    coupling = G (check_coupling; primal-dual only): the batch is groups of G consecutive planes, the classes of one image, and
+    every iteration ends in the projection of each pixel's G values onto {x >= 0, sum <= 1}; a monitor then stops a group as a
+    whole (include/asr_hip.h, "multi-label coupling"; asr_sr_solve_ml_f32).  None: the calls below, unchanged."""
     b, n, H, W, h, w = _sr_dims(x, y)
+    group = None if coupling is None else check_coupling(coupling, b, cfg, "sr_solve: coupling")
     mon = check_sr_monitor(monitor, "sr_solve: monitor") if monitor is not None else None
     tvw = _tv_weights(tv_weights, x, "sr_solve") if tv_weights is not None else None
-    dt = _data_term(data_term, weights, y, tvw, "sr_solve", always=mon is not None)
+    dt = _data_term(data_term, weights, y, tvw, "sr_solve", always=mon is not None or group is not None)
     if (tvw is not None or dt is not None) and cfg is None:
         cfg = _adam_config(one_minus_beta1, one_minus_beta2, epsilon, amsgrad)
     for t, name in ((rot_tf, "rot_tf"), (trans_tf, "trans_tf"), (inv_rot_tf, "inv_rot_tf"), (inv_trans_tf, "inv_trans_tf")):
@@ -430,7 +460,8 @@ def sr_solve(x, y, rot_tf, trans_tf, inv_rot_tf, inv_trans_tf, alphas, lambdas, 
         raise AsrError(f"alphas must be [num_iter,{b}]")
     num_iter = alphas.shape[0]
     lib = _lib.load()
-    ws_bytes = (lib.asr_sr_solve_workspace_bytes_mon(b, n, H, W, h, w, C.byref(cfg)) if mon is not None else
+    ws_bytes = (lib.asr_sr_solve_workspace_bytes_ml(b, n, H, W, h, w, C.byref(cfg), int(mon is not None)) if group is not None else
+                lib.asr_sr_solve_workspace_bytes_mon(b, n, H, W, h, w, C.byref(cfg)) if mon is not None else
                 lib.asr_sr_solve_workspace_bytes(b, n, H, W, h, w) if cfg is None else
                 lib.asr_sr_solve_workspace_bytes_dt(b, n, H, W, h, w, C.byref(cfg)) if dt is not None else
                 lib.asr_sr_solve_workspace_bytes_cfg(b, n, H, W, h, w, C.byref(cfg)))
@@ -449,17 +480,26 @@ def sr_solve(x, y, rot_tf, trans_tf, inv_rot_tf, inv_trans_tf, alphas, lambdas, 
         if state is not None:
             state.update(ws=ws, m=m, v=v, vhat=vhat)
     terms = torch.zeros((b, 4), dtype=torch.float64, device=x.device) if want_loss else None
+    ms = trace = None
     if mon is not None:
         eval_iters = list(range(0, num_iter, mon["every"]))
         history = (torch.empty((len(eval_iters), b, 4), dtype=torch.float64, device=x.device) if mon["history"] else None)
         iters_done = torch.empty((b,), dtype=torch.int32, device=x.device)
         ms = _lib.SrMonitor(mon["every"], mon["rel_tol"], mon["patience"], mon["min_iter"],
                             history.data_ptr() if history is not None and history.numel() else None, ptr(iters_done, torch.int32))
+        trace = SrTrace(history, eval_iters, iters_done)
+    if group is not None:
+        call("asr_sr_solve_ml_f32", ptr(x), ptr(y), ptr(rot_tf), ptr(trans_tf), ptr(inv_rot_tf), ptr(inv_trans_tf), ptr(m),
+             ptr(v), ptr(vhat), ptr(alphas), num_iter, ptr(terms, torch.float64, allow_none=True), ptr(ws),
+             C.c_size_t(ws_bytes), b, n, H, W, h, w, float(lambdas[0]), float(lambdas[1]), float(lambdas[2]),
+             float(lambdas[3]), C.byref(cfg), C.byref(dt), C.byref(ms) if ms is not None else None, group, stream_ptr())
+        return (x, terms) if trace is None else (x, terms, trace)
+    if mon is not None:
         call("asr_sr_solve_mon_f32", ptr(x), ptr(y), ptr(rot_tf), ptr(trans_tf), ptr(inv_rot_tf), ptr(inv_trans_tf), ptr(m),
              ptr(v), ptr(vhat), ptr(alphas), num_iter, ptr(terms, torch.float64, allow_none=True), ptr(ws),
              C.c_size_t(ws_bytes), b, n, H, W, h, w, float(lambdas[0]), float(lambdas[1]), float(lambdas[2]),
              float(lambdas[3]), C.byref(cfg), C.byref(dt), C.byref(ms), stream_ptr())
-        return x, terms, SrTrace(history, eval_iters, iters_done)
+        return x, terms, trace
     if dt is not None:
         call("asr_sr_solve_dt_f32", ptr(x), ptr(y), ptr(rot_tf), ptr(trans_tf), ptr(inv_rot_tf), ptr(inv_trans_tf), ptr(m),
              ptr(v), ptr(vhat), ptr(alphas), num_iter, ptr(terms, torch.float64, allow_none=True), ptr(ws),
@@ -1047,6 +1087,22 @@ def fuse_labels(scores, class_ids, th_factor=0.15, max_scores=None, truth=None, 
          ptr(truth, torch.int32, allow_none=True), ptr(out, torch.int32), ptr(counts, torch.int64, allow_none=True), per, k,
          float(np.float32(th_factor)), ids, int(classes), stream_ptr())
     return out, counts
+
+
+def fuse_labels_simplex(scores, class_ids, out=None):
+    """scores [K, ...] float32, the planes of a coupled solve (shares of each pixel) -> int32 label map [...]: class_ids[k*],
+    k* the first class of greatest share, where that share exceeds the background's 1 - sum_k scores[k] (float32, index
+    order), else 0 (asr_fuse_labels_simplex_f32).  No threshold; counts come from class_counts."""
+    ids, k = class_set(class_ids)
+    if scores.dim() < 2 or scores.shape[0] != k:
+        raise AsrError(f"fuse_labels_simplex: scores must have one plane per class ({k}), got {tuple(scores.shape)}")
+    per = scores.numel() // k
+    if out is None:
+        out = torch.empty(tuple(scores.shape[1:]), dtype=torch.int32, device=scores.device)
+    elif out.numel() != per:
+        raise AsrError("fuse_labels_simplex: out size mismatch")
+    call("asr_fuse_labels_simplex_f32", ptr(scores), ids, k, ptr(out, torch.int32), per, stream_ptr())
+    return out
 
 
 MAX_LABEL_SWEEP_FACTORS = 64

@@ -232,15 +232,18 @@ class HotPath:
         return [int(adam_starts[c]) for c in ids]
 
     def _classes_scores(self, y, ymax, angles, fshifts, starts, sr_types, tv_weights=None, df_weights=None, stop=None,
-                        iters=None):
+                        iters=None, couple=False):
         """_sr_scores of a class set: class k's solve starts at the Adam step starts[k], its max map's num_iter later; the
         counter itself is left as it was.  tv_weights: the image's edge weights (wy, wx), shared by every solve; df_weights:
         the copies' confidence stack [N, h, w], the weights of every solve's data term.  stop (a checked monitor dict): the
-        solves run under it, and iters (a dict) receives the device int32 [K] iterations of each: "aug", "aug_max"."""
+        solves run under it, and iters (a dict) receives the device int32 [K] iterations of each: "aug", "aug_max".
+        couple: the K classes are one coupled solve (Superresolution.augmented_superresolution_classes' couple)."""
         sr = self.sr
         kw = {} if tv_weights is None else {"tv_guide": tv_weights}
         if df_weights is not None:
             kw["df_weights"] = df_weights
+        if couple:
+            kw["couple"] = True
         solve = lambda stack, a, s, second: sr.augmented_superresolution_classes(
             stack, a[0], s[0], [st + second * sr.num_iter for st in starts], **kw)[0]
         if stop is not None:
@@ -327,8 +330,8 @@ class HotPath:
     def run_image_labels(self, image_dev, angles, shifts, class_ids=range(1, 21), gt_dev=None, adam_starts=None,
                          sr_types=("aug", "max", "mean"), want_standard=True, prune=True, profile=None, keep_scores=False,
                          band_widths=None, band_ignore_label=255, confusion_labels=None, th_factors=None, guide=None,
-                         coverages=None, keep_uncertainty=False, min_region=None, df_weights=None, sr_stop=None, tv_guide=None,
-                         crf=None, segments=None):
+                         coverages=None, keep_uncertainty=False, min_region=None, df_weights=None, sr_stop=None, couple=False,
+                         tv_guide=None, crf=None, segments=None):
         """One label map per SR type from one forward pass: stage 1 and the solves are run_image_classes's; stage 2 ends in the
         fusion kernel (ops.fuse_labels) instead of K thresholds.  class_ids: K <= 32 distinct ids, none 0 (the label of "no
         class").  At each pixel the label is the class whose single-class mask is set there and whose SR output is greatest
@@ -446,8 +449,18 @@ class HotPath:
         The result gains "sr_iters": {"aug": int32 [K'] numpy, the updates applied to each class of solved_ids} and in
         slice_max also {"aug_max": the same of the max maps' solves}; they are read back with the other results, after the
         whole image is enqueued.  The Adam bookkeeping does not change: every solve counts as num_iter steps, stopped or not.
-        With sr_stop=None nothing else is launched and the result is what it was."""
+        With sr_stop=None nothing else is launched and the result is what it was.
+
+        couple (True needs Optimizer("primal_dual"); check_couple): the "aug" solve is ONE coupled solve over the solved classes
+        (include/asr_hip.h, "multi-label coupling": x_k >= 0 and sum_k x_k <= 1 at every pixel; pruned classes are zero anyway, one
+        class left is a group of 1; under sr_stop the classes stop together), and the "aug" map is ops.fuse_labels_simplex of its
+        scores -- the class of largest share where that share exceeds the background's 1 - sum_k x_k, no threshold -- after the
+        guided filter when guide is on; its counts are ops.class_counts'.  "max", "mean" and "standard" are untouched, and every
+        other option works as it does without it.  Refused on the host before the model runs: modes slice and slice_max (their
+        normalised stacks do not sum to at most 1), th_factors and crf (both read the threshold rule), an optimizer other than
+        primal_dual.  With couple=False nothing else is launched and every result is what it was."""
         ids = [int(c) for c in class_ids]
+        self.check_couple(couple, th_factors, crf)
         stop = self.check_sr_stop(sr_stop)
         self.check_df_weights(df_weights)
         tv_beta = self.check_tv_guide(tv_guide, None if image_dev is None else tuple(image_dev.shape))
@@ -519,6 +532,8 @@ class HotPath:
                 tv_weights = ops.tv_edge_weights(image_dev.to(torch.float32).contiguous(), tv_beta)
             if kept:
                 stop_kw = {} if stop is None else {"stop": stop, "iters": sr_iters}
+                if couple:
+                    stop_kw["couple"] = True
                 for t, tgt, tmax in self._classes_scores(y, ymax, angles, fshifts, [starts[k] for k in kept], sr_types,
                                                          tv_weights, conf[0] if conf else None, **stop_kw):
                     j = keys.index(t)
@@ -526,7 +541,10 @@ class HotPath:
                         ops.guided_apply(g_state, g_image, tgt, out=tgt)
                         if tmax is not None:
                             ops.guided_apply(g_state, g_image, tmax, out=tmax)
-                    if crf_opts is not None:
+                    if couple and t == "aug":
+                        ops.fuse_labels_simplex(tgt, solved, out=maps[j])
+                        c = ops.class_counts(gt, maps[j])[0] if gt is not None else None
+                    elif crf_opts is not None:
                         ops.crf_refine(g_image, ops.crf_unaries(tgt, self.th_factor, crf_opts.tau), solved, crf_opts.params,
                                        out=maps[j])
                         c = ops.class_counts(gt, maps[j])[0] if gt is not None else None
@@ -568,6 +586,22 @@ class HotPath:
             res["uncertainty"] = u_map
             res["uncertainty_stacks"] = y if kept else None
         return res
+
+    def check_couple(self, couple, th_factors=None, crf=None):
+        """run_image_labels' couple, checked on the host before any launch: True needs the argmax mode (the normalised stacks
+        of slice and slice_max do not sum to at most 1 over the classes), no th_factors and no crf (both read the threshold
+        rule, which the coupled map does not have) and Optimizer("primal_dual").  ValueError otherwise."""
+        if not isinstance(couple, (bool, np.bool_)):
+            raise ValueError(f"couple must be True or False, got {couple!r}")
+        if not couple:
+            return
+        if self.mode != "argmax":
+            raise ValueError(f"couple in {self.mode} mode: the classes' normalised stacks do not sum to at most 1 there")
+        if th_factors is not None:
+            raise ValueError("th_factors with couple: the coupled label map has no threshold to sweep")
+        if crf is not None:
+            raise ValueError("crf with couple: the CRF's unaries are margins over the threshold rule, which the coupled map does not have")
+        self.sr.check_couple()
 
     def check_df_weights(self, df_weights):
         """run_image_labels' df_weights, checked on the host before any launch: None, "maxprob" or "margin".  The confidence is

@@ -281,17 +281,23 @@ class Superresolution:
                                  lambda b: np.stack([self.optimizer.schedule_alphas(self.num_iter) for _ in range(b)], axis=1),
                                  tv_guide, df_weights)
 
-    def augmented_superresolution_classes(self, copies, angles, shifts, start_steps, tv_guide=None, df_weights=None):
+    def augmented_superresolution_classes(self, copies, angles, shifts, start_steps, tv_guide=None, df_weights=None,
+                                          couple=False):
         """The copies of K classes of ONE image in one batched solve: copies [K,N,h,w] device tensor, angles [N], shifts [N,2]
         (the image's transforms, repeated for every class), start_steps [K] -> (device [K,H,W], [K] losses).  Class k's
         step scalars are those of a solve that starts at the global step counter start_steps[k]; the counter itself is left
         as it was (the caller decides what the classes' solves count as).  copy_dropout uses the object's frozen mask.
         tv_guide: the image's RGB [H,W,3], or its edge weights (wy, wx) [H,W], shared by the K classes.
-        df_weights: the weights of the data term, [N,h,w] shared by the K classes (or [K,N,h,w])."""
+        df_weights: the weights of the data term, [N,h,w] shared by the K classes (or [K,N,h,w]).
+        couple: the K classes are one coupled solve (ops.sr_solve's coupling=K: x >= 0 and sum_k x_k <= 1 at every pixel, a
+        monitor stops them together); needs Optimizer("primal_dual"), ValueError otherwise.  augmented_superresolution_batch
+        solves different images and is never coupled."""
         self._check_tv_guide(tv_guide)
         self._check_df_weights(df_weights)
         if self.optimizer is None:
             raise Exception("You must provide an instance of the Optimizer class to compute the augmented SR")
+        if couple:
+            self.check_couple()
         k = copies.shape[0]
         starts = [int(s) for s in start_steps]
         if len(starts) != k:
@@ -308,10 +314,15 @@ class Superresolution:
         a = np.repeat(np.asarray(angles, dtype=np.float32)[None], k, axis=0)
         s = np.repeat(np.asarray(shifts, dtype=np.float32)[None], k, axis=0)
         return self._solve_batch(copies, a, s, lambda b: np.stack(columns, axis=1).reshape(self.num_iter, b), tv_guide,
-                                 df_weights)
+                                 df_weights, coupling=k if couple else None)
 
-    def _solve_batch(self, copies, angles, shifts, make_alphas, tv_guide=None, df_weights=None):
-        """The batched solve; make_alphas(B) -> float32 [num_iter, B] step scalars."""
+    def check_couple(self):
+        """Host check of couple=True: the projection is the last prox step of the primal-dual iteration and of no other rule."""
+        if self.optimizer is None or self.optimizer.optimizer.kind != _lib.OPT_PRIMAL_DUAL:
+            raise ValueError("Superresolution: couple=True needs Optimizer('primal_dual') (the coupling is a prox step of that rule)")
+
+    def _solve_batch(self, copies, angles, shifts, make_alphas, tv_guide=None, df_weights=None, coupling=None):
+        """The batched solve; make_alphas(B) -> float32 [num_iter, B] step scalars.  coupling: ops.sr_solve's."""
         if self.optimizer is None:
             raise Exception("You must provide an instance of the Optimizer class to compute the augmented SR")
         dev = copies.device
@@ -351,6 +362,8 @@ class Superresolution:
             kw["tv_weights"] = self._tv_weights(tv_guide, b, dev)
         if self._data_term() is not None or wts is not None:
             kw.update(data_term=self._data_term(), weights=wts)
+        if coupling is not None:
+            kw["coupling"] = coupling
         if self.monitor is not None:
             # the schedule above covers all num_iter iterations whether an image stops or not: the optimiser's step counter
             # never depends on a device result

@@ -46,6 +46,12 @@ each class's margin over its threshold divided by U (default 0.1), and neighbour
 mode and not together with --th_sweep / --th_factors.  What it does to real network output is not known: compare the --band_widths
 curve with and without it.  Off when omitted: nothing else is launched and every CSV keeps its columns either way.
 
+--couple_classes (needs --sr_optimizer primal_dual; argmax mode; not with --th_sweep / --th_factors or --crf_iters): the classes of an
+image are ONE coupled solve (include/asr_hip.h, "multi-label coupling": every pixel's class values stay >= 0 and sum to at most 1, the
+rest being "no class"), and the "aug" label map takes the class of largest share wherever that share exceeds the background's -- no
+threshold factor plays a part.  The other label maps are untouched.  What it does to real network output is not known: compare the
+CSV with and without it.  Off when omitted: nothing else is launched and every CSV is what it was.
+
 --coverages 50,60,70,80,90,100 [--coverage_out FILE] [--uncertainty_dir DIR]: the risk-coverage curve as well -- the variance of
 the class stacks over the realigned copies (include/asr_hip.h at asr_realign_moments_f32; utils.uncertainty_map) says where the
 copies disagreed, and every label map is scored on each image's p % most certain non-void pixels (asr_binned_class_counts_f32),
@@ -126,6 +132,9 @@ parser.add_argument("--sr_iters_out", default=None, help="CSV file (image, class
 parser.add_argument("--sr_optimizer", choices=["primal_dual"], default=None,
                     help="update rule of the iterative solve: primal_dual needs no learning rate (default: the reference's AMSGrad schedule)")
 parser.add_argument("--pd_bound_iters", type=int, default=None, help="repetitions of the primal-dual step bound, 1..64 (default 6); needs --sr_optimizer primal_dual")
+parser.add_argument("--couple_classes", action="store_true",
+                    help="solve the classes of an image as one coupled problem (x >= 0, sum <= 1 per pixel) and fuse the 'aug' map "
+                         "without a threshold; needs --sr_optimizer primal_dual")
 parser.add_argument("--crf_iters", type=int, default=None,
                     help="decide the SR label maps with the windowed CRF of this many mean-field iterations (0..32)")
 parser.add_argument("--crf_radius", type=int, default=None, help="the CRF's window radius (1..7, default 3)")
@@ -256,6 +265,15 @@ def main():
             check_crf({k: v for k, v in crf.items() if k not in ("tau", "standard_conf")})
         except ValueError as e:
             parser.error(f"--crf_*: {e}")
+    if args.couple_classes:
+        if args.sr_optimizer != "primal_dual":
+            parser.error("--couple_classes needs --sr_optimizer primal_dual: the coupling is a prox step of that rule")
+        if args.mode != "argmax":
+            parser.error(f"--couple_classes in {args.mode} mode: the classes' normalised stacks do not sum to at most 1 there")
+        if factors is not None:
+            parser.error("--couple_classes with --th_sweep / --th_factors: the coupled label map has no threshold to sweep")
+        if crf is not None:
+            parser.error("--couple_classes with --crf_iters: the CRF's unaries are margins over the threshold rule")
     if (args.coverage_out or args.uncertainty_dir) and not args.coverages:
         parser.error("--coverage_out and --uncertainty_dir need --coverages")
     covs = None
@@ -297,7 +315,8 @@ def main():
                              **(dict(coverages=covs, uncertainty_dir=args.uncertainty_dir) if covs is not None else {}),
                              **(dict(min_region=min_region) if min_region is not None else {}),
                              **(dict(segments=segments) if segments is not None else {}),
-                             **(dict(sr_stop=sr_stop, sr_iters=sr_iters) if sr_stop is not None else {}))
+                             **(dict(sr_stop=sr_stop, sr_iters=sr_iters) if sr_stop is not None else {}),
+                             **(dict(couple=True) if args.couple_classes else {}))
     rows, counts = out.rows, out.counts
     if args.sr_iters_out:             # every rank holds the solves of its own images
         stem, ext = os.path.splitext(args.sr_iters_out)
