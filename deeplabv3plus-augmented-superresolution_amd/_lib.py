@@ -72,6 +72,17 @@ class SrMonitor(C.Structure):
                 ("history", C.c_void_p), ("iters_done", C.c_void_p)]
 
 
+RW_CAUCHY, RW_HARD = 0, 1                            # ASR_RW_*
+RW_KINDS = {"cauchy": RW_CAUCHY, "hard": RW_HARD}
+RW_MAX_COPIES = 640                                  # ASR_RW_MAX_COPIES
+
+
+class SrReweight(C.Structure):
+    """struct asr_sr_reweight (include/asr_hip.h): rule, schedule and outputs of the copy reweighting of asr_sr_solve_rw_f32."""
+    _fields_ = [("kind", C.c_int), ("kappa", C.c_double), ("every", C.c_int), ("start", C.c_int),
+                ("copy_weights", C.c_void_p), ("history", C.c_void_p)]
+
+
 class CrfConfig(C.Structure):
     """struct asr_crf_config (include/asr_hip.h): window, iterations and kernels of asr_crf_refine_f32."""
     _fields_ = [("radius", C.c_int), ("dilation", C.c_int), ("iterations", C.c_int), ("w_app", C.c_float),
@@ -83,6 +94,7 @@ _cfg = C.POINTER(SrConfig)
 _crf = C.POINTER(CrfConfig)
 _dt = C.POINTER(SrDataTerm)
 _mon = C.POINTER(SrMonitor)
+_rw = C.POINTER(SrReweight)
 ABI_VERSION = 3          # ASR_ABI_VERSION of include/asr_hip.h this table mirrors
 
 # name -> (restype, argtypes).  Order and types mirror include/asr_hip.h exactly.
@@ -116,6 +128,11 @@ SIGNATURES = {
     "asr_simplex_project_f32": (_i, [_vp, _i, _i, _i64, _vp]),
     "asr_sr_solve_workspace_bytes_ml": (_sz, [_i] * 6 + [_cfg, _i]),
     "asr_sr_solve_ml_f32": (_i, [_vp] * 10 + [_i, _vp, _vp, _sz] + [_i] * 6 + [_fl] * 4 + [_cfg, _dt, _mon, _i, _vp]),
+    "asr_sr_copy_energy_f64": (_i, [_vp, _dt, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "asr_sr_copy_weights_f32": (_i, [_vp, _vp, _i, C.c_double, _vp, _vp, _i, _i, _vp]),
+    "asr_sr_apply_copy_weights_f32": (_i, [_vp, _dt, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "asr_sr_solve_workspace_bytes_rw": (_sz, [_i] * 6 + [_cfg, _i]),
+    "asr_sr_solve_rw_f32": (_i, [_vp] * 10 + [_i, _vp, _vp, _sz] + [_i] * 6 + [_fl] * 4 + [_cfg, _dt, _mon, _i, _rw, _vp]),
     "asr_sr_data_bound_workspace_bytes": (_sz, [_i] * 6 + [_cfg]),
     "asr_sr_data_bound_f32": (_i, [_vp] * 6 + [_i, _i, _vp, _sz] + [_i] * 6 + [_fl, _cfg, _vp]),
     "asr_realign_max_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),

@@ -1914,6 +1914,37 @@ __global__ __launch_bounds__(64) SR_NO_PK_F32 void sr_mon_decide_kernel(SrMonSta
     }
 }
 
+// ---- copy reweighting (include/asr_hip.h, "copy reweighting": the rule) ----------------------------------------------------------
+// The four kernels and their launches (sr_rw_energy_launch, sr_rw_weights_launch, sr_rw_apply_launch, sr_rw_rearm_launch) and
+// kRwMaxCopies live in sr_rw_kernels.h, a section of this translation unit.
+#include "sr_rw_kernels.h"
+
+int check_reweight_rule(const char* fn, int kind, double kappa) {
+    ASR_REQUIRE(kind == ASR_RW_CAUCHY || kind == ASR_RW_HARD, "%s: unknown reweighting kind %d", fn, kind);
+    ASR_REQUIRE(kappa > 0.0 && kappa < __builtin_inf(), "%s: reweighting kappa=%g must be finite and > 0", fn, kappa);
+    return ASR_OK;
+}
+
+// The shape limits of the three launches: the ranking's LDS (n), the energy grid (batch * n), the apply grid's y (h * w)
+int check_rw_shape(const char* fn, int batch, int n, int h, int w) {
+    ASR_REQUIRE(batch > 0 && n > 0 && h > 0 && w > 0, "%s: bad shape batch=%d n=%d %dx%d", fn, batch, n, h, w);
+    ASR_REQUIRE(n <= kRwMaxCopies, "%s: n=%d exceeds %d copies", fn, n, kRwMaxCopies);
+    ASR_REQUIRE((int64_t)batch * n <= 2147483647LL, "%s: batch*n=%lld exceeds 2^31 - 1 (grid.x)", fn, (long long)batch * n);
+    ASR_REQUIRE((int64_t)h * w <= 65535LL * 256, "%s: h*w=%lld exceeds %lld (grid.y)", fn, (long long)h * w, 65535LL * 256);
+    return ASR_OK;
+}
+
+// Is `it` a reweighting iteration of rw, and how many lie below num_iter
+bool sr_rw_is_point(const asr_sr_reweight* rw, int it) { return rw && it >= rw->start && (it - rw->start) % rw->every == 0; }
+int sr_rw_points(const asr_sr_reweight* rw, int num_iter) {
+    return (rw && num_iter > rw->start) ? (num_iter - rw->start + rw->every - 1) / rw->every : 0;
+}
+size_t sr_rw_workspace_extra(int batch, int n, int h, int w) {
+    if (batch <= 0 || n <= 0 || h <= 0 || w <= 0) return 0;
+    // w_eff + 8 bytes of slack to align the doubles + energy + mass
+    return sizeof(float) * (size_t)batch * n * h * w + 8 + sizeof(double) * 2 * (size_t)batch * n;
+}
+
 // ---- multi-label coupling (include/asr_hip.h, "multi-label coupling") ------------------------------------------------------------
 // The projection kernel lives in reduce.hip with the other per-pixel kernels over class planes (asr_simplex_project_launch,
 // asr_common.h); here only the geometry of the bordered copy xb that it also writes inside a solve.
@@ -1933,7 +1964,11 @@ int sr_solve_impl(const char* fn, float* x, const float* y, const float* rot_tf,
                   double* last_loss_terms, void* workspace, size_t workspace_bytes, int batch, int n, int H, int W, int h, int w,
                   float lambda_df, float lambda_tv, float lambda_l2, float lambda_l1, const asr_sr_config* cfg,
                   const SrTvWArg& wa, asr_stream_t stream, const SrDt* dt = nullptr, const asr_sr_monitor* mon = nullptr,
-                  int group = 0) {
+                  int group = 0, const asr_sr_reweight* rw = nullptr) {
+    // rw (asr_sr_solve_rw_f32, always with dt; checked by the entry point): on a reweighting iteration K_fwd also writes the raw
+    // residual, then the three sr_rw_* launches rewrite the copy weights, w_eff (at the workspace's end) and q; from then on
+    // K_fwd and the monitor's term 0 read w_eff where they read the caller's weights.  Under a monitor one more small launch
+    // re-arms the stop rule.  Without rw nothing below differs from what it was.
     // group >= 1 (asr_sr_solve_ml_f32): after the update launch of an iteration's last chunk, one projection launch over the
     // batch's groups of `group` planes rewrites the new x and its bordered copy; the stop rule then decides per group.
     // mon (asr_sr_solve_mon_f32, always with dt): the MON instantiations of the three per-iteration kernels and, at every
@@ -1963,7 +1998,8 @@ int sr_solve_impl(const char* fn, float* x, const float* y, const float* rot_tf,
     ASR_REQUIRE((int64_t)batch * chunk <= 65535, "%s: batch*chunk=%lld exceeds 65535 (grid.z)", fn, (long long)batch * chunk);
     const size_t base = sr_workspace_bytes(batch, n, H, W, h, w, chunk);
     const size_t pd_at = base + (dt ? sr_dt_workspace_extra(batch, n, h, w) : 0) + (mon ? sr_mon_workspace_extra(batch) : 0);
-    const size_t need = pd_at + sr_pd_workspace_extra(cfg, batch, H, W);
+    const size_t rw_at = pd_at + sr_pd_workspace_extra(cfg, batch, H, W);
+    const size_t need = rw_at + (rw ? sr_rw_workspace_extra(batch, n, h, w) : 0);
     if (workspace_bytes < need) {
         asr_set_error("%s: workspace %zu < required %zu bytes", fn, workspace_bytes, need);
         return ASR_ERR_WORKSPACE;
@@ -1996,6 +2032,31 @@ int sr_solve_impl(const char* fn, float* x, const float* y, const float* rot_tf,
         if (mon->history && mon_rows > 0)     // NaN: the rows an image does not reach
             ASR_HIP_CHECK(hipMemsetAsync(mon->history, 0xFF, sizeof(double) * 4 * (size_t)mon_rows * batch, s));
     }
+    // copy reweighting: w_eff, then energy and mass per copy; dtc is the data term in force (the caller's until the first reweighting)
+    float* const w_eff = reinterpret_cast<float*>(static_cast<char*>(workspace) + rw_at);
+    double* const rw_energy = reinterpret_cast<double*>((reinterpret_cast<uintptr_t>(w_eff + (size_t)batch * n * h * w) + 7) & ~(uintptr_t)7);
+    double* const rw_mass = rw_energy + (size_t)batch * n;
+    SrDt dtc = dt ? *dt : SrDt{};
+    if (rw) {
+        ASR_HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(rw->copy_weights), 0x3f800000 /* 1.0f */, (size_t)batch * n, s));
+        const int points = sr_rw_points(rw, num_iter);
+        if (rw->history && points > 0)        // NaN: the rows an image stopped by the monitor does not reach
+            ASR_HIP_CHECK(hipMemsetAsync(rw->history, 0xFF, sizeof(float) * (size_t)points * batch * n, s));
+    }
+    // the three launches of a reweighting iteration, after its K_fwd (which wrote the raw residual)
+    auto reweight = [&](int it, const int* stopped) -> int {
+        const int per_copy = h * w;
+        float* const hist = rw->history ? rw->history + (size_t)((it - rw->start) / rw->every) * batch * n : nullptr;
+        int rc2 = sr_rw_energy_launch(s, raw, rw_energy, rw_mass, batch, n, per_copy, *dt, stopped);
+        if (rc2 != ASR_OK) return rc2;
+        rc2 = sr_rw_weights_launch(s, rw_energy, rw_mass, rw->copy_weights, hist, nullptr, batch, n, rw->kind, rw->kappa, stopped);
+        if (rc2 != ASR_OK) return rc2;
+        rc2 = sr_rw_apply_launch(s, raw, rw->copy_weights, w_eff, resid, batch, n, per_copy, *dt, stopped);
+        if (rc2 != ASR_OK) return rc2;
+        dtc.w = w_eff;
+        dtc.w_stride = (int64_t)n * h * w;
+        return ASR_OK;
+    };
     if (num_iter > 0) {
         hipLaunchKernelGGL(sr_affine_flags_kernel, dim3((unsigned)batch), dim3(64), 0, s, inv_rot_tf, affine_flags, n);
         ASR_LAUNCH_CHECK();
@@ -2024,14 +2085,21 @@ int sr_solve_impl(const char* fn, float* x, const float* y, const float* rot_tf,
         if (mon) {
             // an evaluation (it % every == 0) or, for last_loss_terms, the last iteration: the terms of the current x, then the rule
             const bool is_eval = it % mon->every == 0;
-            SrDt a = *dt;
-            a.r_out = (is_eval || want_terms) ? raw : nullptr;
+            const bool rw_now = sr_rw_is_point(rw, it);
+            SrDt a = dtc;
+            a.r_out = (is_eval || want_terms || rw_now) ? raw : nullptr;
             hipLaunchKernelGGL((sr_forward_residual_kernel<true, true, true>), lr_grid(d), kBlock, 0, s, xb, y, rot_tf, trans_tf, resid,
                                d, a, marg);
             ASR_LAUNCH_CHECK();
+            if (rw_now) {
+                rc = reweight(it, ms.stopped);
+                if (rc != ASR_OK) return rc;
+                rc = sr_rw_rearm_launch(s, ms, batch);
+                if (rc != ASR_OK) return rc;
+            }
             if (is_eval || want_terms) {
                 hipLaunchKernelGGL(sr_mon_loss_df_kernel, dim3(kMonParts, batch), dim3(256), 0, s, raw, ms.parts,
-                                   (int64_t)n * h * w, *dt, ms.stopped);
+                                   (int64_t)n * h * w, dtc, ms.stopped);
                 ASR_LAUNCH_CHECK();
                 if (wa.weighted)
                     hipLaunchKernelGGL(sr_mon_loss_prior_kernel<true>, dim3(kMonParts, batch), dim3(256), 0, s, cur, ms.parts, H, W, st,
@@ -2077,9 +2145,10 @@ int sr_solve_impl(const char* fn, float* x, const float* y, const float* rot_tf,
             swap_duals();
             continue;
         }
+        const bool rw_now = sr_rw_is_point(rw, it);
         if (dt) {
-            SrDt a = *dt;
-            a.r_out = want_terms ? raw : nullptr;
+            SrDt a = dtc;
+            a.r_out = (want_terms || rw_now) ? raw : nullptr;
             hipLaunchKernelGGL((sr_forward_residual_kernel<true, true>), lr_grid(d), kBlock, 0, s, xb, y, rot_tf, trans_tf, resid, d, a,
                                SrMonArg<false>{});
         } else {
@@ -2087,8 +2156,13 @@ int sr_solve_impl(const char* fn, float* x, const float* y, const float* rot_tf,
                                SrDtArg<false>{}, SrMonArg<false>{});
         }
         ASR_LAUNCH_CHECK();
+        if (rw_now) {
+            rc = reweight(it, nullptr);
+            if (rc != ASR_OK) return rc;
+        }
         if (want_terms) {
-            rc = sr_loss_terms_impl(fn, cur, dt ? raw : resid, last_loss_terms, batch, n, H, W, h, w, cfg, wa, stream, dt);
+            rc = sr_loss_terms_impl(fn, cur, dt ? raw : resid, last_loss_terms, batch, n, H, W, h, w, cfg, wa, stream,
+                                    dt ? &dtc : nullptr);
             if (rc != ASR_OK) return rc;
         }
         for (int n0 = 0; n0 < n; n0 += chunk) {
@@ -2202,10 +2276,20 @@ int sr_solve_dt_entry(const char* fn, float* x, const float* y, const float* rot
                       const float* inv_trans_tf, float* m, float* v, float* vhat, const float* alphas, int num_iter,
                       double* last_loss_terms, void* workspace, size_t workspace_bytes, int batch, int n, int H, int W, int h, int w,
                       float lambda_df, float lambda_tv, float lambda_l2, float lambda_l1, const asr_sr_config* cfg,
-                      const asr_sr_data_term* dt, const asr_sr_monitor* mon, bool monitored, int group, asr_stream_t stream) {
+                      const asr_sr_data_term* dt, const asr_sr_monitor* mon, bool monitored, int group, asr_stream_t stream,
+                      const asr_sr_reweight* rw = nullptr) {
     SrDt a;
-    const int rc = make_data_term(fn, dt, n, h, w, &a);
+    int rc = make_data_term(fn, dt, n, h, w, &a);
     if (rc != ASR_OK) return rc;
+    if (rw) {
+        rc = check_reweight_rule(fn, rw->kind, rw->kappa);
+        if (rc != ASR_OK) return rc;
+        ASR_REQUIRE(rw->every >= 1, "%s: reweighting every=%d must be >= 1", fn, rw->every);
+        ASR_REQUIRE(rw->start >= 0, "%s: reweighting start=%d must be >= 0", fn, rw->start);
+        ASR_REQUIRE(rw->copy_weights, "%s: null pointer (reweighting copy_weights)", fn);
+        rc = check_rw_shape(fn, batch, n, h, w);          // n <= 640 and the grid limits of the three launches, as stand-alone
+        if (rc != ASR_OK) return rc;
+    }
     if (monitored) {
         ASR_REQUIRE(mon, "%s: null monitor", fn);
         ASR_REQUIRE(mon->every >= 1, "%s: monitor every=%d must be >= 1", fn, mon->every);
@@ -2218,7 +2302,7 @@ int sr_solve_dt_entry(const char* fn, float* x, const float* y, const float* rot
     const SrTvWArg wa = {dt->wy, dt->wx, dt->tv_shared, dt->wy != nullptr};
     return sr_solve_impl(fn, x, y, rot_tf, trans_tf, inv_rot_tf, inv_trans_tf, m, v, vhat, alphas, num_iter, last_loss_terms,
                          workspace, workspace_bytes, batch, n, H, W, h, w, lambda_df, lambda_tv, lambda_l2, lambda_l1, cfg, wa,
-                         stream, &a, monitored ? mon : nullptr, group);
+                         stream, &a, monitored ? mon : nullptr, group, rw);
 }
 }  // namespace
 
@@ -2271,6 +2355,57 @@ extern "C" int asr_sr_solve_ml_f32(float* x, const float* y, const float* rot_tf
     return sr_solve_dt_entry("asr_sr_solve_ml_f32", x, y, rot_tf, trans_tf, inv_rot_tf, inv_trans_tf, m, v, vhat, alphas, num_iter,
                              last_loss_terms, workspace, workspace_bytes, batch, n, H, W, h, w, lambda_df, lambda_tv, lambda_l2,
                              lambda_l1, cfg, dt, mon, mon != nullptr, group, stream);
+}
+
+// ---- copy reweighting: the entry points (include/asr_hip.h, "copy reweighting") --------------------------------------------------
+extern "C" int asr_sr_copy_energy_f64(const float* r, const asr_sr_data_term* dt, double* energy, double* mass, int batch, int n,
+                                      int h, int w, asr_stream_t stream) {
+    ASR_REQUIRE(r && energy && mass, "asr_sr_copy_energy_f64: null pointer");
+    SrDt a;
+    int rc = make_data_term("asr_sr_copy_energy_f64", dt, n, h, w, &a);
+    if (rc != ASR_OK) return rc;
+    rc = check_rw_shape("asr_sr_copy_energy_f64", batch, n, h, w);
+    if (rc != ASR_OK) return rc;
+    return sr_rw_energy_launch(asr_stream(stream), r, energy, mass, batch, n, h * w, a, nullptr);
+}
+
+extern "C" int asr_sr_copy_weights_f32(const double* energy, const double* mass, int kind, double kappa, float* c, double* scale_out,
+                                       int batch, int n, asr_stream_t stream) {
+    ASR_REQUIRE(energy && mass && c, "asr_sr_copy_weights_f32: null pointer");
+    int rc = check_reweight_rule("asr_sr_copy_weights_f32", kind, kappa);
+    if (rc != ASR_OK) return rc;
+    rc = check_rw_shape("asr_sr_copy_weights_f32", batch, n, 1, 1);
+    if (rc != ASR_OK) return rc;
+    return sr_rw_weights_launch(asr_stream(stream), energy, mass, c, nullptr, scale_out, batch, n, kind, kappa, nullptr);
+}
+
+extern "C" int asr_sr_apply_copy_weights_f32(const float* r, const asr_sr_data_term* dt, const float* c, float* w_eff, float* q,
+                                             int batch, int n, int h, int w, asr_stream_t stream) {
+    ASR_REQUIRE(r && c && w_eff && q, "asr_sr_apply_copy_weights_f32: null pointer");
+    SrDt a;
+    int rc = make_data_term("asr_sr_apply_copy_weights_f32", dt, n, h, w, &a);
+    if (rc != ASR_OK) return rc;
+    rc = check_rw_shape("asr_sr_apply_copy_weights_f32", batch, n, h, w);
+    if (rc != ASR_OK) return rc;
+    ASR_REQUIRE(w_eff != a.w, "asr_sr_apply_copy_weights_f32: w_eff aliases the data term's weights");
+    return sr_rw_apply_launch(asr_stream(stream), r, c, w_eff, q, batch, n, h * w, a, nullptr);
+}
+
+extern "C" size_t asr_sr_solve_workspace_bytes_rw(int batch, int n, int H, int W, int h, int w, const asr_sr_config* cfg,
+                                                  int monitored) {
+    return asr_sr_solve_workspace_bytes_ml(batch, n, H, W, h, w, cfg, monitored) + sr_rw_workspace_extra(batch, n, h, w);
+}
+
+extern "C" int asr_sr_solve_rw_f32(float* x, const float* y, const float* rot_tf, const float* trans_tf,
+                                   const float* inv_rot_tf, const float* inv_trans_tf, float* m, float* v, float* vhat,
+                                   const float* alphas, int num_iter, double* last_loss_terms, void* workspace,
+                                   size_t workspace_bytes, int batch, int n, int H, int W, int h, int w, float lambda_df,
+                                   float lambda_tv, float lambda_l2, float lambda_l1, const asr_sr_config* cfg,
+                                   const asr_sr_data_term* dt, const asr_sr_monitor* mon, int group,
+                                   const asr_sr_reweight* rw, asr_stream_t stream) {
+    return sr_solve_dt_entry("asr_sr_solve_rw_f32", x, y, rot_tf, trans_tf, inv_rot_tf, inv_trans_tf, m, v, vhat, alphas, num_iter,
+                             last_loss_terms, workspace, workspace_bytes, batch, n, H, W, h, w, lambda_df, lambda_tv, lambda_l2,
+                             lambda_l1, cfg, dt, mon, mon != nullptr, group, stream, rw);
 }
 
 // ---- the step bound of the primal-dual rule (asr_sr_data_bound_f32; include/asr_hip.h, "primal-dual": the rule) -------------

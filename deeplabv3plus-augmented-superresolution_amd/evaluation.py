@@ -242,6 +242,30 @@ def read_sr_iters_csv(path):
     return [(r[0], r[1], int(r[2])) for r in rows[1:]]
 
 
+COPY_WEIGHTS_CSV_COLUMNS = ("image", "class", "copy", "weight")
+
+
+def write_copy_weights_csv(path, rows):
+    """rows of (image, class, copy, weight) -- evaluate_labelmaps' copy_weights -- as a CSV, every field quoted; the weight is
+    written with repr of its float32 value, so the file reads back to the same bits."""
+    import csv
+    with open(path, "w", newline="") as fh:
+        wr = csv.writer(fh, quoting=csv.QUOTE_ALL, lineterminator="\n")
+        wr.writerow(COPY_WEIGHTS_CSV_COLUMNS)
+        for image, cls, copy, weight in rows:
+            wr.writerow([str(image), str(cls), str(int(copy)), repr(float(np.float32(weight)))])
+
+
+def read_copy_weights_csv(path):
+    """write_copy_weights_csv's file -> [(image, class, copy, weight)], image and class as strings, weight a float."""
+    import csv
+    with open(path, newline="") as fh:
+        rows = list(csv.reader(fh))
+    if not rows or tuple(rows[0]) != COPY_WEIGHTS_CSV_COLUMNS:
+        raise ValueError(f"{path}: not a copy-weights CSV (header {rows[:1]})")
+    return [(r[0], r[1], int(r[2]), float(r[3])) for r in rows[1:]]
+
+
 # ---- label maps: one fused label map per image and SR type, scored with the multi-class Mean_IOU ------------------------
 LABELMAP_KEYS = ("standard", "aug", "max", "mean")
 LABELMAP_CSV_COLUMNS = ("standard_iou", "aug_iou", "max_iou", "mean_iou")
@@ -309,7 +333,8 @@ def dataset_miou(counts):
 def evaluate_labelmaps(path, image_paths, gt_paths, class_ids=tuple(range(1, 21)), num_aug=100, angle_max=0.3, shift_max=30,
                        img_size=(512, 512), rank=0, world=1, seed=1234, sr_types=("aug", "max", "mean"), prune=True,
                        save_dir=None, band_widths=None, band_ignore_label=255, confusion_labels=None, th_factors=None,
-                       guide=None, df_weights=None, sr_stop=None, sr_iters=None, couple=False, tv_guide=None, crf=None,
+                       guide=None, df_weights=None, sr_stop=None, sr_iters=None, couple=False, sr_reweight=None, copy_weights=None,
+                       tv_guide=None, crf=None,
                        min_region=None, segments=None, coverages=None, uncertainty_dir=None):
     """One fused label map per image and SR type (HotPath.run_image_labels) and its score.  Returns on every rank a
     LabelmapScores, the tuple (rows, counts) plus what the options below append, every entry also an attribute by the name
@@ -380,8 +405,16 @@ def evaluate_labelmaps(path, image_paths, gt_paths, class_ids=tuple(range(1, 21)
 
     couple (True needs the primal_dual optimizer and the argmax mode; not together with th_factors or crf): every image's "aug"
     solve is one coupled solve over its classes and its "aug" map the threshold-free fusion of the shares (run_image_labels'
-    couple).  The return value keeps its form."""
+    couple).  The return value keeps its form.
+
+    sr_reweight (run_image_labels' sr_reweight: a kind name, or kind, kappa, every, start): every image's "aug" solves
+    down-weight whole unreliable copies, class by class.  The return value keeps its form; copy_weights (a list) receives one
+    row (image stem, class id, copy index, final weight) per image of THIS rank, solved class and copy (write_copy_weights_csv;
+    in slice_max a second set of rows per class, the class written "<id>_max", for its max map's solve)."""
     stop_kw = {} if path.check_sr_stop(sr_stop) is None else {"sr_stop": dict(sr_stop)}
+    rw_on = path.check_sr_reweight(sr_reweight) is not None
+    if rw_on:
+        stop_kw["sr_reweight"] = dict(sr_reweight) if isinstance(sr_reweight, dict) else sr_reweight
     path.check_couple(couple, th_factors, crf)
     if couple:
         stop_kw["couple"] = True
@@ -416,7 +449,12 @@ def evaluate_labelmaps(path, image_paths, gt_paths, class_ids=tuple(range(1, 21)
                                     confusion_labels=opts.n_conf or None, th_factors=opts.factors, guide=opts.guide,
                                     coverages=opts.covs, keep_uncertainty=bool(uncertainty_dir), min_region=opts.min_region,
                                     segments=opts.segments, **tv_kw, **stop_kw)
-        if stop_kw and sr_iters is not None:
+        if rw_on and copy_weights is not None:
+            stem = os.path.splitext(os.path.basename(image_paths[g]))[0]
+            for solve, cw in sorted(res["copy_weights"].items()):
+                tag = "_max" if solve == "aug_max" else ""
+                copy_weights.extend((stem, f"{c}{tag}", i, float(v)) for c, row in zip(res["solved_ids"], cw) for i, v in enumerate(row))
+        if "sr_stop" in stop_kw and sr_iters is not None:
             stem = os.path.splitext(os.path.basename(image_paths[g]))[0]
             for solve, its in sorted(res["sr_iters"].items()):
                 tag = "_max" if solve == "aug_max" else ""

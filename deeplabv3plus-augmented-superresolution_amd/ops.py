@@ -429,9 +429,108 @@ class SrTrace:
         return sr_loss_from_terms(self.history.cpu().numpy(), lambdas)
 
 
+SR_REWEIGHT_DEFAULTS = dict(kind="cauchy", kappa=2.0, every=10, start=10, history=False)
+
+
+def check_sr_reweight(params, name="sr reweight"):
+    """The copy reweighting of a solve (include/asr_hip.h: asr_sr_reweight) as a complete dict: a mapping with any of the keys
+    kind ("cauchy" or "hard"), kappa (finite number > 0), every (int >= 1), start (int >= 0) and history (bool), the others from
+    SR_REWEIGHT_DEFAULTS; a bare kind name stands for dict(kind=name).  Host only; ValueError on anything else."""
+    if isinstance(params, str):
+        params = dict(kind=params)
+    if not isinstance(params, dict):
+        raise ValueError(f"{name}: a dict with keys among {sorted(SR_REWEIGHT_DEFAULTS)} expected, got {params!r}")
+    unknown = sorted(set(params) - set(SR_REWEIGHT_DEFAULTS))
+    if unknown:
+        raise ValueError(f"{name}: unknown keys {unknown} (known: {sorted(SR_REWEIGHT_DEFAULTS)})")
+    p = dict(SR_REWEIGHT_DEFAULTS, **params)
+    if not isinstance(p["kind"], str) or p["kind"].lower() not in _lib.RW_KINDS:
+        raise ValueError(f"{name}: kind must be one of {sorted(_lib.RW_KINDS)}, got {p['kind']!r}")
+    p["kind"] = p["kind"].lower()
+    k = p["kappa"]
+    if not isinstance(k, numbers.Real) or isinstance(k, bool) or not np.isfinite(float(k)) or float(k) <= 0.0:
+        raise ValueError(f"{name}: kappa must be a finite number > 0, got {k!r}")
+    p["kappa"] = float(k)
+    for key, low in (("every", 1), ("start", 0)):
+        v = p[key]
+        if not isinstance(v, numbers.Integral) or isinstance(v, bool) or not low <= int(v) < 2 ** 31:
+            raise ValueError(f"{name}: {key} must be an integer >= {low}, got {v!r}")
+        p[key] = int(v)
+    if not isinstance(p["history"], (bool, np.bool_)):
+        raise ValueError(f"{name}: history must be True or False, got {p['history']!r}")
+    p["history"] = bool(p["history"])
+    return p
+
+
+def sr_reweight_iters(params, num_iter):
+    """The iterations below num_iter at which a solve under check_sr_reweight's dict reweights."""
+    return list(range(params["start"], int(num_iter), params["every"]))
+
+
+class SrCopyWeights:
+    """What a reweighted solve leaves behind.  weights: device float32 [B, N], the last weight of every copy (1 where the solve
+    never reweighted); history: device float32 [R, B, N], the weights after each of the R reweightings (NaN for an image the
+    monitor had stopped), or None; iters: the R iterations that reweighted.  Reading a tensor on the host synchronises."""
+
+    def __init__(self, weights, history, iters):
+        self.weights, self.history, self.iters = weights, history, list(iters)
+
+
+def _rw_residual(r, name):
+    if not isinstance(r, torch.Tensor) or r.dim() != 4 or r.dtype != f32 or not r.is_contiguous() or r.numel() == 0:
+        raise AsrError(f"{name}: r must be a contiguous float32 tensor [B,N,h,w]")
+    if r.shape[1] > _lib.RW_MAX_COPIES:
+        raise AsrError(f"{name}: at most {_lib.RW_MAX_COPIES} copies, got {r.shape[1]}")
+    return tuple(r.shape)
+
+
+def sr_copy_energy(r, data_term=None, weights=None):
+    """r [B,N,h,w], the RAW residual (sr_forward_residual's second output) -> (energy, mass), float64 [B,N]: per copy
+    sum weights * rho(r) and sum weights (h*w without weights), in the fixed order of include/asr_hip.h, "copy reweighting"."""
+    b, n, h, w = _rw_residual(r, "sr_copy_energy")
+    dt = _data_term(data_term, weights, r, None, "sr_copy_energy", always=True)
+    energy = torch.empty((b, n), dtype=torch.float64, device=r.device)
+    mass = torch.empty((b, n), dtype=torch.float64, device=r.device)
+    call("asr_sr_copy_energy_f64", ptr(r), C.byref(dt), ptr(energy, torch.float64), ptr(mass, torch.float64), b, n, h, w,
+         stream_ptr())
+    return energy, mass
+
+
+def sr_copy_weights(energy, mass, kind="cauchy", kappa=2.0, want_scale=False):
+    """energy, mass float64 [B,N] -> the copy weights c, float32 [B,N] (and, want_scale, the scale s, float64 [B]): each copy's
+    energy per unit mass against kappa times the lower median over the active copies of its image (include/asr_hip.h)."""
+    p = check_sr_reweight(dict(kind=kind, kappa=kappa), "sr_copy_weights")
+    for t in (energy, mass):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.dtype != torch.float64 or not t.is_contiguous() or t.numel() == 0:
+            raise AsrError("sr_copy_weights: energy and mass must be contiguous float64 tensors [B,N]")
+    if energy.shape != mass.shape or energy.device != mass.device:
+        raise AsrError(f"sr_copy_weights: energy {tuple(energy.shape)} and mass {tuple(mass.shape)} differ")
+    b, n = energy.shape
+    if n > _lib.RW_MAX_COPIES:
+        raise AsrError(f"sr_copy_weights: at most {_lib.RW_MAX_COPIES} copies, got {n}")
+    c = torch.empty((b, n), dtype=f32, device=energy.device)
+    scale = torch.empty((b,), dtype=torch.float64, device=energy.device) if want_scale else None
+    call("asr_sr_copy_weights_f32", ptr(energy, torch.float64), ptr(mass, torch.float64), _lib.RW_KINDS[p["kind"]], p["kappa"],
+         ptr(c), ptr(scale, torch.float64, allow_none=True), b, n, stream_ptr())
+    return (c, scale) if want_scale else c
+
+
+def sr_apply_copy_weights(r, c, data_term=None, weights=None):
+    """r [B,N,h,w] (raw residual), c [B,N] -> (w_eff, q), each [B,N,h,w]: w_eff = weights * c (c without weights) and
+    q = w_eff * psi(r), bit for bit what sr_forward_residual(..., weights=w_eff) returns for the x that gave r."""
+    b, n, h, w = _rw_residual(r, "sr_apply_copy_weights")
+    if not isinstance(c, torch.Tensor) or tuple(c.shape) != (b, n) or c.dtype != f32 or not c.is_contiguous() or c.device != r.device:
+        raise AsrError(f"sr_apply_copy_weights: c must be a contiguous float32 tensor [{b},{n}] on the device of r")
+    dt = _data_term(data_term, weights, r, None, "sr_apply_copy_weights", always=True)
+    w_eff = torch.empty_like(r)
+    q = torch.empty_like(r)
+    call("asr_sr_apply_copy_weights_f32", ptr(r), C.byref(dt), ptr(c), ptr(w_eff), ptr(q), b, n, h, w, stream_ptr())
+    return w_eff, q
+
+
 def sr_solve(x, y, rot_tf, trans_tf, inv_rot_tf, inv_trans_tf, alphas, lambdas, one_minus_beta1=None, one_minus_beta2=None,
              epsilon=None, amsgrad=False, want_loss=True, cfg=None, slot_init=None, state=None, tv_weights=None,
-             data_term=None, weights=None, monitor=None, coupling=None):
+             data_term=None, weights=None, monitor=None, coupling=None, reweight=None):
     """Runs alphas.shape[0] iterations in place on x.  alphas [num_iter, B] (device).  Either the Adam
     hyper-parameters (asr_sr_solve_f32) or cfg (+ slot_init = {"m"/"v"/"vhat": initial value}) for
     asr_sr_solve_cfg_f32.  state: a dict that carries the optimiser slots and the workspace from one call to the next --
@@ -446,12 +545,19 @@ def sr_solve(x, y, rot_tf, trans_tf, inv_rot_tf, inv_trans_tf, alphas, lambdas, 
     the slots m and v come back as the dual planes p_y and p_x (include/asr_hip.h, "primal-dual").
     coupling = G (check_coupling; primal-dual only): the batch is groups of G consecutive planes, the classes of one image, and
     every iteration ends in the projection of each pixel's G values onto {x >= 0, sum <= 1}; a monitor then stops a group as a
-    whole (include/asr_hip.h, "multi-label coupling"; asr_sr_solve_ml_f32).  None: the calls below, unchanged."""
+    whole (include/asr_hip.h, "multi-label coupling"; asr_sr_solve_ml_f32).  None: the calls below, unchanged.
+    reweight (check_sr_reweight's dict, or a kind name): every `every` iterations from `start` each copy's residual energy is
+    compared with the median over the copies of its image and the whole copy is scaled by a robust weight, on top of `weights`
+    (include/asr_hip.h, "copy reweighting"; asr_sr_solve_rw_f32); combines with everything above.  The return value gains one
+    last element, an SrCopyWeights.  None: the calls below and their return values, unchanged."""
     b, n, H, W, h, w = _sr_dims(x, y)
+    rwp = check_sr_reweight(reweight, "sr_solve: reweight") if reweight is not None else None
+    if rwp is not None and n > _lib.RW_MAX_COPIES:
+        raise AsrError(f"sr_solve: reweight ranks at most {_lib.RW_MAX_COPIES} copies, got {n}")
     group = None if coupling is None else check_coupling(coupling, b, cfg, "sr_solve: coupling")
     mon = check_sr_monitor(monitor, "sr_solve: monitor") if monitor is not None else None
     tvw = _tv_weights(tv_weights, x, "sr_solve") if tv_weights is not None else None
-    dt = _data_term(data_term, weights, y, tvw, "sr_solve", always=mon is not None or group is not None)
+    dt = _data_term(data_term, weights, y, tvw, "sr_solve", always=mon is not None or group is not None or rwp is not None)
     if (tvw is not None or dt is not None) and cfg is None:
         cfg = _adam_config(one_minus_beta1, one_minus_beta2, epsilon, amsgrad)
     for t, name in ((rot_tf, "rot_tf"), (trans_tf, "trans_tf"), (inv_rot_tf, "inv_rot_tf"), (inv_trans_tf, "inv_trans_tf")):
@@ -460,7 +566,8 @@ def sr_solve(x, y, rot_tf, trans_tf, inv_rot_tf, inv_trans_tf, alphas, lambdas, 
         raise AsrError(f"alphas must be [num_iter,{b}]")
     num_iter = alphas.shape[0]
     lib = _lib.load()
-    ws_bytes = (lib.asr_sr_solve_workspace_bytes_ml(b, n, H, W, h, w, C.byref(cfg), int(mon is not None)) if group is not None else
+    ws_bytes = (lib.asr_sr_solve_workspace_bytes_rw(b, n, H, W, h, w, C.byref(cfg), int(mon is not None)) if rwp is not None else
+                lib.asr_sr_solve_workspace_bytes_ml(b, n, H, W, h, w, C.byref(cfg), int(mon is not None)) if group is not None else
                 lib.asr_sr_solve_workspace_bytes_mon(b, n, H, W, h, w, C.byref(cfg)) if mon is not None else
                 lib.asr_sr_solve_workspace_bytes(b, n, H, W, h, w) if cfg is None else
                 lib.asr_sr_solve_workspace_bytes_dt(b, n, H, W, h, w, C.byref(cfg)) if dt is not None else
@@ -488,6 +595,19 @@ def sr_solve(x, y, rot_tf, trans_tf, inv_rot_tf, inv_trans_tf, alphas, lambdas, 
         ms = _lib.SrMonitor(mon["every"], mon["rel_tol"], mon["patience"], mon["min_iter"],
                             history.data_ptr() if history is not None and history.numel() else None, ptr(iters_done, torch.int32))
         trace = SrTrace(history, eval_iters, iters_done)
+    if rwp is not None:
+        rw_iters = sr_reweight_iters(rwp, num_iter)
+        cw = torch.empty((b, n), dtype=f32, device=x.device)
+        cw_hist = torch.empty((len(rw_iters), b, n), dtype=f32, device=x.device) if rwp["history"] else None
+        rs = _lib.SrReweight(_lib.RW_KINDS[rwp["kind"]], rwp["kappa"], rwp["every"], rwp["start"], ptr(cw),
+                             cw_hist.data_ptr() if cw_hist is not None and cw_hist.numel() else None)
+        call("asr_sr_solve_rw_f32", ptr(x), ptr(y), ptr(rot_tf), ptr(trans_tf), ptr(inv_rot_tf), ptr(inv_trans_tf), ptr(m),
+             ptr(v), ptr(vhat), ptr(alphas), num_iter, ptr(terms, torch.float64, allow_none=True), ptr(ws),
+             C.c_size_t(ws_bytes), b, n, H, W, h, w, float(lambdas[0]), float(lambdas[1]), float(lambdas[2]),
+             float(lambdas[3]), C.byref(cfg), C.byref(dt), C.byref(ms) if ms is not None else None,
+             group if group is not None else 0, C.byref(rs), stream_ptr())
+        out = SrCopyWeights(cw, cw_hist, rw_iters)
+        return (x, terms, out) if trace is None else (x, terms, trace, out)
     if group is not None:
         call("asr_sr_solve_ml_f32", ptr(x), ptr(y), ptr(rot_tf), ptr(trans_tf), ptr(inv_rot_tf), ptr(inv_trans_tf), ptr(m),
              ptr(v), ptr(vhat), ptr(alphas), num_iter, ptr(terms, torch.float64, allow_none=True), ptr(ws),

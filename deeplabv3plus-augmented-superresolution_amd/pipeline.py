@@ -232,12 +232,14 @@ class HotPath:
         return [int(adam_starts[c]) for c in ids]
 
     def _classes_scores(self, y, ymax, angles, fshifts, starts, sr_types, tv_weights=None, df_weights=None, stop=None,
-                        iters=None, couple=False):
+                        iters=None, couple=False, reweight=None, copy_weights=None):
         """_sr_scores of a class set: class k's solve starts at the Adam step starts[k], its max map's num_iter later; the
         counter itself is left as it was.  tv_weights: the image's edge weights (wy, wx), shared by every solve; df_weights:
         the copies' confidence stack [N, h, w], the weights of every solve's data term.  stop (a checked monitor dict): the
         solves run under it, and iters (a dict) receives the device int32 [K] iterations of each: "aug", "aug_max".
-        couple: the K classes are one coupled solve (Superresolution.augmented_superresolution_classes' couple)."""
+        couple: the K classes are one coupled solve (Superresolution.augmented_superresolution_classes' couple).
+        reweight (a checked reweight dict): the solves reweight their copies under it, and copy_weights (a dict) receives the
+        device float32 [K, N] weights of each: "aug", "aug_max"."""
         sr = self.sr
         kw = {} if tv_weights is None else {"tv_guide": tv_weights}
         if df_weights is not None:
@@ -258,7 +260,31 @@ class HotPath:
                 if sr.last_trace is not None:              # (num_iter = 0: no solve, no trace)
                     iters["aug_max" if second else "aug"] = sr.last_trace.iters_done
                 return x
+        if reweight is not None:
+            inner = solve
+
+            def solve(stack, a, s, second):
+                saved, sr.reweight, sr.last_copy_weights = sr.reweight, reweight, None
+                try:
+                    x = inner(stack, a, s, second)
+                finally:
+                    sr.reweight = saved
+                if sr.last_copy_weights is not None:       # (num_iter = 0: no solve, no weights)
+                    copy_weights["aug_max" if second else "aug"] = sr.last_copy_weights.weights
+                return x
         return self._sr_scores(y, ymax, angles, fshifts, sr_types, solve)
+
+    @staticmethod
+    def check_sr_reweight(sr_reweight):
+        """run_image_labels' sr_reweight, checked on the host before any launch: None, a kind name ("cauchy", "hard") or a dict
+        with any of kind, kappa (default 2), every (10), start (10) -> None or the reweight dict of the solver (no history)."""
+        if sr_reweight is None:
+            return None
+        if isinstance(sr_reweight, str):
+            sr_reweight = dict(kind=sr_reweight)
+        if not isinstance(sr_reweight, dict) or set(sr_reweight) - {"kind", "kappa", "every", "start"}:
+            raise ValueError(f"sr_reweight must be a kind name or a dict with keys among kind, kappa, every, start, got {sr_reweight!r}")
+        return ops.check_sr_reweight(dict(sr_reweight, history=False), "sr_reweight")
 
     @staticmethod
     def check_sr_stop(sr_stop):
@@ -331,6 +357,7 @@ class HotPath:
                          sr_types=("aug", "max", "mean"), want_standard=True, prune=True, profile=None, keep_scores=False,
                          band_widths=None, band_ignore_label=255, confusion_labels=None, th_factors=None, guide=None,
                          coverages=None, keep_uncertainty=False, min_region=None, df_weights=None, sr_stop=None, couple=False,
+                         sr_reweight=None,
                          tv_guide=None, crf=None, segments=None):
         """One label map per SR type from one forward pass: stage 1 and the solves are run_image_classes's; stage 2 ends in the
         fusion kernel (ops.fuse_labels) instead of K thresholds.  class_ids: K <= 32 distinct ids, none 0 (the label of "no
@@ -451,6 +478,13 @@ class HotPath:
         whole image is enqueued.  The Adam bookkeeping does not change: every solve counts as num_iter steps, stopped or not.
         With sr_stop=None nothing else is launched and the result is what it was.
 
+        sr_reweight ("cauchy", "hard" or {"kind": .., "kappa": .., "every": .., "start": ..}, any subset; check_sr_reweight): the
+        "aug" solves down-weight whole unreliable copies (include/asr_hip.h, "copy reweighting"), on top of df_weights, per class.
+        The result gains "copy_weights": {"aug": float32 [K', N] numpy, the final weight of every copy for each class of
+        solved_ids} and in slice_max, whose max maps' solve is reweighted as well, also {"aug_max": the same of that solve}
+        (under copy_dropout N counts the kept copies); read back with the other results.  With sr_reweight=None nothing else is
+        launched and the result is what it was.
+
         couple (True needs Optimizer("primal_dual"); check_couple): the "aug" solve is ONE coupled solve over the solved classes
         (include/asr_hip.h, "multi-label coupling": x_k >= 0 and sum_k x_k <= 1 at every pixel; pruned classes are zero anyway, one
         class left is a group of 1; under sr_stop the classes stop together), and the "aug" map is ops.fuse_labels_simplex of its
@@ -462,6 +496,9 @@ class HotPath:
         ids = [int(c) for c in class_ids]
         self.check_couple(couple, th_factors, crf)
         stop = self.check_sr_stop(sr_stop)
+        reweight = self.check_sr_reweight(sr_reweight)
+        if reweight is not None and getattr(self.sr, "verbose", False):
+            raise ValueError("sr_reweight: the solver object is verbose (it cuts the solve into calls, where the weights would start over)")
         self.check_df_weights(df_weights)
         tv_beta = self.check_tv_guide(tv_guide, None if image_dev is None else tuple(image_dev.shape))
         crf_opts = self.check_crf(crf, None if image_dev is None else tuple(image_dev.shape), th_factors, len(ids))
@@ -510,6 +547,7 @@ class HotPath:
             y, ymax = self._normalise(y, ymax)
         scores = {}
         sr_iters = {}                      # sr_stop: device int32 [K'] per solve, read back at the end
+        copy_weights = {}                  # sr_reweight: device float32 [K', N] per solve, read back at the end
         fshifts = self._sr_frame(image_dev, shifts)
         with self._sr_stage_timed(profile):
             gt = self._gt_int32(gt_dev) if gt_dev is not None else None
@@ -534,6 +572,8 @@ class HotPath:
                 stop_kw = {} if stop is None else {"stop": stop, "iters": sr_iters}
                 if couple:
                     stop_kw["couple"] = True
+                if reweight is not None:
+                    stop_kw.update(reweight=reweight, copy_weights=copy_weights)
                 for t, tgt, tmax in self._classes_scores(y, ymax, angles, fshifts, [starts[k] for k in kept], sr_types,
                                                          tv_weights, conf[0] if conf else None, **stop_kw):
                     j = keys.index(t)
@@ -582,6 +622,8 @@ class HotPath:
             res["scores"] = scores
         if stop is not None:
             res["sr_iters"] = {k: v.cpu().numpy() for k, v in sr_iters.items()}
+        if reweight is not None:
+            res["copy_weights"] = {k: v.cpu().numpy() for k, v in copy_weights.items()}
         if keep_uncertainty:
             res["uncertainty"] = u_map
             res["uncertainty_stacks"] = y if kept else None

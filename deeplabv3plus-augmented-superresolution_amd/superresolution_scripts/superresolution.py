@@ -24,6 +24,11 @@ of the solution is cheap across an image edge and costs full price elsewhere (in
 ``Optimizer("primal_dual")`` (not in the reference) swaps the update rule for the primal-dual iteration of include/asr_hip.h,
 "primal-dual": no learning rate; ``_solve_batch`` computes the step on the device from the transforms, weights and dropout
 mask it solves (ops.sr_data_bound, ops.pd_steps).  It refuses ``use_BTV`` and ``df_loss="l1"``.
+
+``reweight`` (not in the reference) down-weights whole unreliable copies inside the solve: "cauchy" or "hard", every
+``reweight_every`` iterations from ``reweight_start`` each copy's residual energy against ``reweight_kappa`` times the median over
+the copies of its image (include/asr_hip.h, "copy reweighting"); ``last_copy_weights`` then holds the ops.SrCopyWeights of the
+last solve.  It multiplies ``df_weights`` and combines with every option above.
 """
 from __future__ import annotations
 
@@ -85,7 +90,7 @@ class Superresolution:
                  optimizer: Optimizer = None, feature_size=(64, 64), output_size=(512, 512), use_BTV=False,
                  verbose=False, copy_dropout=0.0, trim=0.1, cover="frame", cov_min=0.5, valid_min=0.5, tv_beta=100.0,
                  df_loss="l2", df_delta=0.1, stop_rel_tol=None, stop_patience=3, stop_every=1, stop_min_iter=0,
-                 keep_history=False):
+                 keep_history=False, reweight=None, reweight_kappa=2.0, reweight_every=10, reweight_start=10):
         self.tv_beta = ops.check_tv_beta(tv_beta, "Superresolution: tv_beta")
         # the convergence monitor (include/asr_hip.h): with stop_rel_tol each image of a solve stops by itself once its loss
         # has not improved by that relative amount for stop_patience evaluations in a row (one every stop_every iterations,
@@ -96,6 +101,14 @@ class Superresolution:
             raise ValueError("Superresolution: verbose prints by cutting the solve into calls and cannot be combined with "
                              "stop_rel_tol / keep_history (read last_trace instead)")
         self.last_trace = None
+        # copy reweighting (include/asr_hip.h): None, or the reweight dict of ops.sr_solve.  self.last_copy_weights: the
+        # ops.SrCopyWeights of the last solve, None when that solve did not reweight ([B, N] per solved plane; under copy_dropout
+        # N counts the kept copies).
+        self.reweight = self.check_reweight(reweight, reweight_kappa, reweight_every, reweight_start)
+        if self.reweight is not None and verbose:
+            raise ValueError("Superresolution: verbose prints by cutting the solve into calls and cannot be combined with "
+                             "reweight (the weights would start over in every call)")
+        self.last_copy_weights = None
         # the data term sum w * rho(r): "l2" (the reference's), "l1" or "huber" with threshold df_delta, in the units of the
         # stacks (the path normalises them to [0, 1]); the weights w come per solve (df_weights=)
         ops.check_data_term(df_loss, df_delta, "Superresolution: df_loss")
@@ -145,6 +158,25 @@ class Superresolution:
         if mon["patience"] < 1:
             raise ValueError(f"Superresolution: stop_patience must be >= 1 with stop_rel_tol, got {stop_patience!r}")
         return mon
+
+    @staticmethod
+    def check_reweight(reweight=None, reweight_kappa=2.0, reweight_every=10, reweight_start=10):
+        """The reweight* keywords -> None (no reweighting) or the reweight dict of ops.sr_solve; ValueError on a bad value, on
+        the host (the other three are checked even when reweight is None)."""
+        p = ops.check_sr_reweight(dict(kind="cauchy" if reweight is None else reweight, kappa=reweight_kappa, every=reweight_every,
+                                       start=reweight_start, history=False), "Superresolution: reweight")
+        return None if reweight is None else p
+
+    @staticmethod
+    def reweight_keywords(reweight):
+        """A reweight dict (kind and any of kappa, every, start; None: no reweighting) -> the constructor's reweight* keywords:
+        what the scripts build from their --sr_reweight* flags."""
+        if reweight is None:
+            return {}
+        unknown = sorted(set(reweight) - {"kind", "kappa", "every", "start"})
+        if unknown or "kind" not in reweight:
+            raise ValueError(f"Superresolution: reweight_keywords takes kind and any of kappa, every, start, got {reweight!r}")
+        return dict({"reweight_" + k: v for k, v in reweight.items() if k != "kind"}, reweight=reweight["kind"])
 
     @property
     def _lambdas(self):
@@ -325,6 +357,10 @@ class Superresolution:
         """The batched solve; make_alphas(B) -> float32 [num_iter, B] step scalars.  coupling: ops.sr_solve's."""
         if self.optimizer is None:
             raise Exception("You must provide an instance of the Optimizer class to compute the augmented SR")
+        if self.reweight is not None and self.verbose:      # also when a caller set self.reweight after construction (HotPath does)
+            raise ValueError("Superresolution: verbose prints by cutting the solve into calls and cannot be combined with "
+                             "reweight (the weights would start over in every call)")
+        self.last_copy_weights = None                       # of THIS solve: None when it does not reweight (or num_iter = 0)
         dev = copies.device
         b, n, h, w = copies.shape
         if (h, w) != self.feature_size:
@@ -364,6 +400,13 @@ class Superresolution:
             kw.update(data_term=self._data_term(), weights=wts)
         if coupling is not None:
             kw["coupling"] = coupling
+        if self.reweight is not None:
+            out = ops.sr_solve(x, copies, rot, tr, irot, itr, alphas_dev, self._lambdas, monitor=self.monitor,
+                               reweight=self.reweight, **kw)
+            self.last_copy_weights = out[-1]
+            if self.monitor is not None:
+                self.last_trace = out[2]
+            return out[0], out[1]
         if self.monitor is not None:
             # the schedule above covers all num_iter iterations whether an image stops or not: the optimiser's step counter
             # never depends on a device result

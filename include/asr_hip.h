@@ -445,6 +445,102 @@ int asr_sr_solve_ml_f32(float* x, const float* y, const float* rot_tf, const flo
                         const asr_sr_config* cfg, const asr_sr_data_term* dt, const asr_sr_monitor* mon /* may be NULL */,
                         int group, asr_stream_t stream);
 
+/* --- copy reweighting: whole unreliable copies down-weighted inside the solve (IRLS over the copies) ------------------------
+ * Huber caps the pull of each pixel; a copy on which the network failed outright still pulls with all of its h*w pixels.
+ * Every few iterations the reweighted solve measures each copy's residual energy, compares it with the median over the copies
+ * of its image and scales the whole copy by a robust weight c in [0, 1].  No existing kernel changes: the forward kernel already
+ * multiplies by a weight buffer, and the launches below only rewrite that buffer (w_eff) and the buffer q the backward kernels
+ * read, on the iterations that reweight.  No floating-point atomics anywhere.  The rule:
+ *
+ *   Inputs.  r [batch, n, h, w]: the RAW residual D(T(R(x))) - y, what asr_sr_forward_residual_dt_f32 writes to r_out.
+ *     u: the data term's weights (weights / weights_shared as above), or none (u = 1).  rho, psi: the float32 statements of
+ *     "data term" above.
+ *   Per copy (b, i), over its P = h*w elements p = 0 .. P-1:
+ *       energy e = sum_p (double)(u_p * rho(r_p))     each summand the float32 value asr_sr_loss_terms_dt_f64 adds (rho, then the
+ *                                                     weight; no multiply without weights)
+ *       mass   a = sum_p (double)u_p                  (double)P without weights, no sum
+ *     both in float64 in one fixed order: one workgroup of 256 threads per copy; thread t adds p = t, t + 256, ... in rising p
+ *     from 0.0; a wave adds its 64 lanes by the tree s[l] += s[l + o], o = 32, 16, 8, 4, 2, 1; the workgroup adds its four waves
+ *     as ((w0 + w1) + w2) + w3 (the monitor's scheme at the scale of one copy).
+ *       ebar = e / a, one float64 division.  The copy is ACTIVE when a > 0 and ebar is finite; an inactive copy (all-zero
+ *       weights, e.g. one masked by the caller's copy dropout; a NaN residual) gets c = 0 and takes no part in the scale.
+ *   Per image, with A = the number of active copies:
+ *       s = the lower median of the active ebar: the value of rank (A-1)/2 (integer division), where
+ *           rank(i) = #{j active : ebar_j < ebar_i  or  (ebar_j == ebar_i and j < i)}        (ranking by counting; n <= 640)
+ *       if (A == 0 or s == 0)  c_i = 1 for every active copy (nothing to compare with: no reweighting); scale_out = s, or 0 for A = 0
+ *       else  t_i = ebar_i / (kappa * s)  in float64: one multiply, one division, and
+ *           ASR_RW_CAUCHY:  c_i = 1.0 / (1.0 + t_i*t_i)        (float64: a product, a sum, a division)
+ *           ASR_RW_HARD:    c_i = (t_i <= 1.0) ? 1 : 0
+ *         c_i is rounded ONCE to float32.  kappa is finite and > 0; a huge kappa (1e30) gives c = 1 exactly.
+ *   Apply, per element:  w_eff = u * c_i, ONE float32 multiply (c_i itself without weights);  q = w_eff * psi(r): sr_dt_psi, then
+ *     the multiply -- the statements of the forward kernel's data-term tail.  Hence q is bit for bit what a forward launch with
+ *     weights = w_eff would have written.
+ *   Nothing depends on plane_chunk, on the batch size or on what ran before.
+ *
+ *   asr_sr_solve_rw_f32: the arguments of asr_sr_solve_ml_f32 and rw.  rw == NULL: asr_sr_solve_ml_f32, bit for bit, the same
+ *     launches.  Iteration `it` (0-based) reweights when it >= start and (it - start) % every == 0.  On such an iteration the
+ *     forward launch also writes the raw residual (its existing second output); then energy + mass, copy weights and apply run
+ *     (three launches) and the iteration proceeds as always.  The new weights are in force for that iteration's gradient and for
+ *     every later forward launch until the next reweighting; before the first one w_eff = u (the caller's buffer is read as it
+ *     is).  w_eff is a solver-owned [batch, n, h, w] buffer even when u is shared.  copy_weights starts at 1 for every copy and
+ *     holds the last c at the end.  history (optional) [R, batch, n], R = the number of reweighting iterations below num_iter:
+ *     row k holds the c of the k-th reweighting; the call first fills it with 0xFF bytes, so the rows of an image stopped by the
+ *     monitor read NaN from its stop on.
+ *     Hence, bit for bit: the solve equals the host-driven sequence {a solve of the iterations up to a reweighting point,
+ *     carrying its slots; asr_sr_forward_residual_dt_f32 with r_out; the three stand-alone entry points below; the next segment
+ *     with weights = w_eff}.  start >= num_iter is the unreweighted solve with every copy weight 1.
+ *     Monitor.  Term 0 is evaluated under the weights in force at that iteration, after its reweighting if there was one.  The
+ *       objective changes at a reweighting: on a reweighting iteration best goes back to +inf and stall to 0 for every image (or
+ *       group) not yet stopped, before the decision (one small launch; the decision kernel is unchanged) -- so a reweighting
+ *       iteration that is an evaluation always counts as an improvement.  A stopped image is frozen and never reweighted again:
+ *       its w_eff, its copy_weights and, from then on, its history rows are not written.
+ *     Coupling.  Weights stay per (plane, copy); nothing is shared across a group.
+ *     Primal-dual.  The step bound (asr_sr_data_bound_f32) is still computed from the base weights u.  Every c <= 1 and every entry
+ *       of the gradient map M is >= 0, so M under w_eff = u*c is entrywise <= M under u: reweighting only shrinks the map, its
+ *       spectral radius can only fall (Perron-Frobenius), and the bound stays a bound.  The refusals of the wrapped entry points
+ *       stay (ASR_DF_L1, bilateral TV, the dual ratio).
+ *     Workspace: asr_sr_solve_workspace_bytes_rw = asr_sr_solve_workspace_bytes_ml + one [batch, n, h, w] float32 buffer (w_eff)
+ *       + two float64 per copy (energy, mass), needed only when rw != NULL.
+ *     Refusals, before any launch, outputs untouched: every refusal of asr_sr_solve_ml_f32; an unknown kind, kappa not finite or
+ *       <= 0, every < 1, start < 0, copy_weights NULL -> ASR_ERR_INVALID_ARG.
+ *   The stand-alone entry points (host-driven use; r, energy, mass, c, w_eff, q on the device):
+ *     asr_sr_copy_energy_f64: energy, mass [batch, n] float64 from r; dt: loss, delta, weights, weights_shared are read.
+ *     asr_sr_copy_weights_f32: c [batch, n] float32 and, optionally, scale_out [batch] float64 from energy and mass.
+ *     asr_sr_apply_copy_weights_f32: w_eff and q [batch, n, h, w] from r, dt and c; four distinct buffers (w_eff must not
+ *       alias the weights of dt).
+ *     Refusals: null pointers (scale_out may be NULL), batch, n, h or w < 1, n > 640, batch * n > 2^31 - 1, h * w > 65535 * 256, the data term's
+ *       own refusals, an unknown kind, kappa not finite or <= 0 -> ASR_ERR_INVALID_ARG. */
+#define ASR_RW_CAUCHY 0
+#define ASR_RW_HARD 1
+#define ASR_RW_MAX_COPIES 640
+
+typedef struct asr_sr_reweight {
+    int kind;             /* ASR_RW_* */
+    double kappa;         /* finite, > 0: a copy at kappa times the median energy gets weight 1/2 (Cauchy) or is the last kept (hard) */
+    int every;            /* >= 1 */
+    int start;            /* >= 0: iteration it reweights when it >= start and (it - start) % every == 0 */
+    float* copy_weights;  /* device [batch, n]: 1 on entry to the loop, the last c at the end */
+    float* history;       /* device [R, batch, n] or NULL */
+} asr_sr_reweight;
+
+int asr_sr_copy_energy_f64(const float* r, const asr_sr_data_term* dt, double* energy, double* mass, int batch, int n, int h,
+                           int w, asr_stream_t stream);
+
+int asr_sr_copy_weights_f32(const double* energy, const double* mass, int kind, double kappa, float* c, double* scale_out,
+                            int batch, int n, asr_stream_t stream);
+
+int asr_sr_apply_copy_weights_f32(const float* r, const asr_sr_data_term* dt, const float* c, float* w_eff, float* q, int batch,
+                                  int n, int h, int w, asr_stream_t stream);
+
+size_t asr_sr_solve_workspace_bytes_rw(int batch, int n, int H, int W, int h, int w, const asr_sr_config* cfg, int monitored);
+
+int asr_sr_solve_rw_f32(float* x, const float* y, const float* rot_tf, const float* trans_tf, const float* inv_rot_tf,
+                        const float* inv_trans_tf, float* m, float* v, float* vhat, const float* alphas, int num_iter,
+                        double* last_loss_terms, void* workspace, size_t workspace_bytes, int batch, int n, int H, int W,
+                        int h, int w, float lambda_df, float lambda_tv, float lambda_l2, float lambda_l1,
+                        const asr_sr_config* cfg, const asr_sr_data_term* dt, const asr_sr_monitor* mon /* may be NULL */,
+                        int group, const asr_sr_reweight* rw /* may be NULL */, asr_stream_t stream);
+
 /* out[b] = max / mean over copies of rotate(translate(resize(y[b,i], (H,W)), trans_tf), rot_tf)
  * -- max_superresolution / mean_superresolution, superresolution.py:139-161 (trans_tf built
  * from -shifts, rot_tf from -angles).  out [batch,H,W]; (H, W) need not be a multiple of (h, w).  The maximum runs

@@ -40,6 +40,11 @@ def main():
     ap.add_argument("--sr_stop_patience", type=int, default=None, help="evaluations in a row without that improvement before a solve stops (default 3)")
     ap.add_argument("--sr_stop_every", type=int, default=None, help="evaluate the loss every this many iterations (default 1)")
     ap.add_argument("--sr_stop_min_iter", type=int, default=None, help="no solve stops before this iteration (default 0)")
+    ap.add_argument("--sr_reweight", choices=["cauchy", "hard"], default=None,
+                    help="down-weight whole unreliable copies inside the iterative solve: each copy's residual energy against --sr_reweight_kappa times the median over the copies")
+    ap.add_argument("--sr_reweight_kappa", type=float, default=None, help="a copy at this many times the median energy gets weight 1/2 (cauchy) or is the last kept (hard); finite, > 0 (default 2)")
+    ap.add_argument("--sr_reweight_every", type=int, default=None, help="reweight every this many iterations (default 10)")
+    ap.add_argument("--sr_reweight_start", type=int, default=None, help="first reweighting iteration (default 10)")
     ap.add_argument("--sr_optimizer", choices=["primal_dual"], default=None,
                     help="update rule of the iterative solve: primal_dual needs no learning rate (default: the reference's AMSGrad schedule)")
     ap.add_argument("--pd_bound_iters", type=int, default=None, help="repetitions of the primal-dual step bound, 1..64 (default 6); needs --sr_optimizer primal_dual")
@@ -63,6 +68,18 @@ def main():
             _Sr.check_stop(**stop_kw)
         except ValueError as e:
             ap.error(f"--sr_stop_*: {e}")
+    rw_flags = {"kappa": args.sr_reweight_kappa, "every": args.sr_reweight_every, "start": args.sr_reweight_start}
+    sr_reweight = None
+    if args.sr_reweight is None:
+        if any(v is not None for v in rw_flags.values()):
+            ap.error("--sr_reweight_kappa, --sr_reweight_every and --sr_reweight_start need --sr_reweight")
+    else:
+        sr_reweight = dict({k: v for k, v in rw_flags.items() if v is not None}, kind=args.sr_reweight)
+        try:
+            from asr_amd.ops import check_sr_reweight
+            check_sr_reweight(sr_reweight, "--sr_reweight_*")
+        except ValueError as e:
+            ap.error(str(e))
     extra = tuple(t for t in args.extra_sr_types.split(",") if t)
     out_dir = args.out or os.path.join(ROOT, "data", "superres_root", "superres_output")
 
@@ -76,7 +93,8 @@ def main():
     sr =Superresolution(lambda_df=HYPER["lambda_df"], lambda_tv=HYPER["lambda_tv"], lambda_L2=HYPER["lambda_L2"],
                          lambda_L1=HYPER["lambda_L1"], num_iter=HYPER["num_iter"], num_aug=args.num_aug,
                          optimizer=optimizer_obj, feature_size=(args.feature_size, args.feature_size), trim=args.trim,
-                         cover=args.cover, df_loss=args.df_loss, df_delta=args.df_delta, **stop_kw)
+                         cover=args.cover, df_loss=args.df_loss, df_delta=args.df_delta, **stop_kw,
+                         **Superresolution.reweight_keywords(sr_reweight))
     paths = interchange_files(args.data)[:args.num_samples]
     res = evaluate_precomputed(sr, paths, args.gt, args.standard, num_aug=args.num_aug, class_id=args.class_id,
                                th_factor=args.th_factor, img_size=IMG_SIZE, out_dir=out_dir, rank=rank, world=world,

@@ -37,6 +37,11 @@ parser.add_argument("--th_factor", type=float, default=0.65)
 parser.add_argument("--num_iter", type=int, default=300)
 parser.add_argument("--df_loss", choices=["l2", "l1", "huber"], default="l2", help="data term of the iterative solve: l2 (the reference's), l1, or huber with threshold --df_delta")
 parser.add_argument("--df_delta", type=float, default=0.1, help="Huber threshold, in units of the stacks (normalised to [0, 1]); finite, > 0")
+parser.add_argument("--sr_reweight", choices=["cauchy", "hard"], default=None,
+                    help="down-weight whole unreliable copies inside the iterative solve: each copy's residual energy against --sr_reweight_kappa times the median over the copies")
+parser.add_argument("--sr_reweight_kappa", type=float, default=None, help="a copy at this many times the median energy gets weight 1/2 (cauchy) or is the last kept (hard); finite, > 0 (default 2)")
+parser.add_argument("--sr_reweight_every", type=int, default=None, help="reweight every this many iterations (default 10)")
+parser.add_argument("--sr_reweight_start", type=int, default=None, help="first reweighting iteration (default 10)")
 parser.add_argument("--sr_optimizer", choices=["primal_dual"], default=None,
                     help="update rule of the iterative solve: primal_dual needs no learning rate (default: the reference's AMSGrad schedule)")
 parser.add_argument("--pd_bound_iters", type=int, default=None, help="repetitions of the primal-dual step bound, 1..64 (default 6); needs --sr_optimizer primal_dual")
@@ -58,6 +63,18 @@ def main():
         opt = Optimizer.from_flags(HYPER, args.sr_optimizer, args.pd_bound_iters, args.df_loss)
     except ValueError as e:
         parser.error(str(e))
+    rw_flags = {"kappa": args.sr_reweight_kappa, "every": args.sr_reweight_every, "start": args.sr_reweight_start}
+    sr_reweight = None
+    if args.sr_reweight is None:
+        if any(v is not None for v in rw_flags.values()):
+            parser.error("--sr_reweight_kappa, --sr_reweight_every and --sr_reweight_start need --sr_reweight")
+    else:
+        sr_reweight = dict({k: v for k, v in rw_flags.items() if v is not None}, kind=args.sr_reweight)
+        try:
+            from asr_amd.ops import check_sr_reweight
+            check_sr_reweight(sr_reweight, "--sr_reweight_*")
+        except ValueError as e:
+            parser.error(str(e))
     import torch
     from asr_amd import distributed as D
     from asr_amd.evaluation import class_rows, evaluate_classes, write_class_csv
@@ -76,7 +93,8 @@ def main():
     feat = IMG_SIZE[0] // (4 if args.backbone == "xception" else 8)
     sr = Superresolution(lambda_df=HYPER["lambda_df"], lambda_tv=HYPER["lambda_tv"], lambda_L2=HYPER["lambda_L2"],
                          lambda_L1=HYPER["lambda_L1"], num_iter=args.num_iter, num_aug=args.num_aug, optimizer=opt,
-                         feature_size=(feat, feat), output_size=IMG_SIZE, df_loss=args.df_loss, df_delta=args.df_delta)
+                         feature_size=(feat, feat), output_size=IMG_SIZE, df_loss=args.df_loss, df_delta=args.df_delta,
+                         **Superresolution.reweight_keywords(sr_reweight))
     path = HotPath(model, sr, mode=args.mode, th_factor=args.th_factor, batch_size=BATCH_SIZE)
     table, presence = evaluate_classes(path, paths, gts, class_ids, num_aug=args.num_aug, angle_max=args.angle_max,
                                        shift_max=args.shift_max, img_size=IMG_SIZE, rank=rank, world=world, seed=SEED)

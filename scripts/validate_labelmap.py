@@ -128,6 +128,12 @@ parser.add_argument("--sr_stop_tol", type=float, default=None,
 parser.add_argument("--sr_stop_patience", type=int, default=None, help="evaluations in a row without that improvement before a solve stops (default 3)")
 parser.add_argument("--sr_stop_every", type=int, default=None, help="evaluate the loss every this many iterations (default 1)")
 parser.add_argument("--sr_stop_min_iter", type=int, default=None, help="no solve stops before this iteration (default 0)")
+parser.add_argument("--sr_reweight", choices=["cauchy", "hard"], default=None,
+                    help="down-weight whole unreliable copies inside the iterative solve: each copy's residual energy against --sr_reweight_kappa times the median over the copies")
+parser.add_argument("--sr_reweight_kappa", type=float, default=None, help="a copy at this many times the median energy gets weight 1/2 (cauchy) or is the last kept (hard); finite, > 0 (default 2)")
+parser.add_argument("--sr_reweight_every", type=int, default=None, help="reweight every this many iterations (default 10)")
+parser.add_argument("--sr_reweight_start", type=int, default=None, help="first reweighting iteration (default 10)")
+parser.add_argument("--copy_weights_out", default=None, help="CSV file (image, class, copy, weight) of the final weight of every copy in each solve; needs --sr_reweight")
 parser.add_argument("--sr_iters_out", default=None, help="CSV file (image, class, iterations) of the iterations each solve ran; needs --sr_stop_tol")
 parser.add_argument("--sr_optimizer", choices=["primal_dual"], default=None,
                     help="update rule of the iterative solve: primal_dual needs no learning rate (default: the reference's AMSGrad schedule)")
@@ -248,6 +254,18 @@ def main():
                 raise ValueError("--sr_stop_patience must be >= 1")
         except ValueError as e:
             parser.error(f"--sr_stop_*: {e}")
+    rw_flags = {"kappa": args.sr_reweight_kappa, "every": args.sr_reweight_every, "start": args.sr_reweight_start}
+    sr_reweight = None
+    if args.sr_reweight is None:
+        if args.copy_weights_out or any(v is not None for v in rw_flags.values()):
+            parser.error("--sr_reweight_kappa, --sr_reweight_every, --sr_reweight_start and --copy_weights_out need --sr_reweight")
+    else:
+        sr_reweight = dict({k: v for k, v in rw_flags.items() if v is not None}, kind=args.sr_reweight)
+        try:
+            from asr_amd.ops import check_sr_reweight
+            check_sr_reweight(sr_reweight, "--sr_reweight_*")
+        except ValueError as e:
+            parser.error(str(e))
     crf_flags = {"radius": args.crf_radius, "dilation": args.crf_dilation, "w_app": args.crf_w_app, "w_smooth": args.crf_w_smooth,
                  "theta_pos": args.crf_theta_pos, "theta_rgb": args.crf_theta_rgb, "theta_smooth": args.crf_theta_smooth,
                  "tau": args.crf_tau, "standard_conf": args.crf_standard_conf}
@@ -303,6 +321,7 @@ def main():
                          feature_size=(feat, feat), output_size=IMG_SIZE, df_loss=args.df_loss, df_delta=args.df_delta)
     path = HotPath(model, sr, mode=args.mode, th_factor=args.th_factor, batch_size=BATCH_SIZE)
     sr_iters = []
+    copy_weights = []
     out = evaluate_labelmaps(path, paths, gts, class_ids, num_aug=args.num_aug, angle_max=args.angle_max,
                              shift_max=args.shift_max, img_size=IMG_SIZE, rank=rank, world=world, seed=SEED,
                              prune=not args.no_prune, save_dir=args.save_dir, band_widths=bands,
@@ -316,7 +335,8 @@ def main():
                              **(dict(min_region=min_region) if min_region is not None else {}),
                              **(dict(segments=segments) if segments is not None else {}),
                              **(dict(sr_stop=sr_stop, sr_iters=sr_iters) if sr_stop is not None else {}),
-                             **(dict(couple=True) if args.couple_classes else {}))
+                             **(dict(couple=True) if args.couple_classes else {}),
+                             **(dict(sr_reweight=sr_reweight, copy_weights=copy_weights) if sr_reweight is not None else {}))
     rows, counts = out.rows, out.counts
     if args.sr_iters_out:             # every rank holds the solves of its own images
         stem, ext = os.path.splitext(args.sr_iters_out)
@@ -324,6 +344,13 @@ def main():
         os.makedirs(os.path.dirname(os.path.abspath(iters_path)), exist_ok=True)
         write_sr_iters_csv(iters_path, sr_iters)
         print(f"Wrote {iters_path}")
+    if args.copy_weights_out:         # every rank holds the solves of its own images
+        from asr_amd.evaluation import write_copy_weights_csv
+        stem, ext = os.path.splitext(args.copy_weights_out)
+        cw_path = args.copy_weights_out if world == 1 else f"{stem}.rank{rank}{ext}"
+        os.makedirs(os.path.dirname(os.path.abspath(cw_path)), exist_ok=True)
+        write_copy_weights_csv(cw_path, copy_weights)
+        print(f"Wrote {cw_path}")
     if rank == 0:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         write_labelmap_csv(args.out, counts, rows)
