@@ -75,6 +75,8 @@ class SrMonitor(C.Structure):
 RW_CAUCHY, RW_HARD = 0, 1                            # ASR_RW_*
 RW_KINDS = {"cauchy": RW_CAUCHY, "hard": RW_HARD}
 RW_MAX_COPIES = 640                                  # ASR_RW_MAX_COPIES
+ADJ_REGISTERED, ADJ_EXACT = 0, 1                     # ASR_ADJ_*
+ADJOINTS = {"registered": ADJ_REGISTERED, "exact": ADJ_EXACT}
 
 
 class SrReweight(C.Structure):
@@ -133,6 +135,11 @@ SIGNATURES = {
     "asr_sr_apply_copy_weights_f32": (_i, [_vp, _dt, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "asr_sr_solve_workspace_bytes_rw": (_sz, [_i] * 6 + [_cfg, _i]),
     "asr_sr_solve_rw_f32": (_i, [_vp] * 10 + [_i, _vp, _vp, _sz] + [_i] * 6 + [_fl] * 4 + [_cfg, _dt, _mon, _i, _rw, _vp]),
+    "asr_sr_adjoint_flags_i32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp]),
+    "asr_sr_solve_adj_f32": (_i, [_vp] * 10 + [_i, _vp, _vp, _sz] + [_i] * 6 + [_fl] * 4 + [_cfg, _dt, _mon, _i, _rw, _i, _vp]),
+    "asr_sr_data_bound_adj_f32": (_i, [_vp] * 6 + [_i, _i, _vp, _sz] + [_i] * 6 + [_fl, _cfg, _i, _vp]),
+    "asr_sr_backward_adj_workspace_bytes": (_sz, [_i] * 4 + [_cfg]),
+    "asr_sr_backward_adj_f32": (_i, [_vp] * 12 + [_i] * 6 + [_fl] * 4 + [_cfg, _vp, _vp, _i, _i, _vp, _sz, _vp]),
     "asr_sr_data_bound_workspace_bytes": (_sz, [_i] * 6 + [_cfg]),
     "asr_sr_data_bound_f32": (_i, [_vp] * 6 + [_i, _i, _vp, _sz] + [_i] * 6 + [_fl, _cfg, _vp]),
     "asr_realign_max_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),

@@ -61,7 +61,7 @@ ALL_SOURCES = SOURCES + LATER_SOURCES
 # the solver 90.9 -> 87.6 us per iteration against the blanket -packed-fp32-ops).  If an instruction cannot be split safely the
 # unit falls back to NO_PK_F32.  The post-pass needs the ROCm LLVM tools; without them: the same fallback.
 POSTPASS = {"sr.hip"}
-HEADERS = ["asr_common.h", "asr_warp_device.h", "gemm_common.h", "sr_rw_kernels.h", os.path.join("..", "..", "include", "asr_hip.h")]
+HEADERS = ["asr_common.h", "asr_warp_device.h", "gemm_common.h", "sr_rw_kernels.h", "sr_adj_kernels.h", os.path.join("..", "..", "include", "asr_hip.h")]
 COMMON = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function",
           "-x", "hip"]
 

@@ -1919,6 +1919,15 @@ __global__ __launch_bounds__(64) SR_NO_PK_F32 void sr_mon_decide_kernel(SrMonSta
 // kRwMaxCopies live in sr_rw_kernels.h, a section of this translation unit.
 #include "sr_rw_kernels.h"
 
+// ---- exact adjoint (include/asr_hip.h, "exact adjoint": the rule) ------------------------------------------------------------------
+// The flags kernel, the two gather kernels and their launches live in sr_adj_kernels.h, a section of this translation unit.
+#include "sr_adj_kernels.h"
+
+int check_adjoint(const char* fn, int adjoint) {
+    ASR_REQUIRE(adjoint == ASR_ADJ_REGISTERED || adjoint == ASR_ADJ_EXACT, "%s: unknown adjoint %d", fn, adjoint);
+    return ASR_OK;
+}
+
 int check_reweight_rule(const char* fn, int kind, double kappa) {
     ASR_REQUIRE(kind == ASR_RW_CAUCHY || kind == ASR_RW_HARD, "%s: unknown reweighting kind %d", fn, kind);
     ASR_REQUIRE(kappa > 0.0 && kappa < __builtin_inf(), "%s: reweighting kappa=%g must be finite and > 0", fn, kappa);
@@ -1964,7 +1973,9 @@ int sr_solve_impl(const char* fn, float* x, const float* y, const float* rot_tf,
                   double* last_loss_terms, void* workspace, size_t workspace_bytes, int batch, int n, int H, int W, int h, int w,
                   float lambda_df, float lambda_tv, float lambda_l2, float lambda_l1, const asr_sr_config* cfg,
                   const SrTvWArg& wa, asr_stream_t stream, const SrDt* dt = nullptr, const asr_sr_monitor* mon = nullptr,
-                  int group = 0, const asr_sr_reweight* rw = nullptr) {
+                  int group = 0, const asr_sr_reweight* rw = nullptr, int adjoint = ASR_ADJ_REGISTERED) {
+    // adjoint (asr_sr_solve_adj_f32; checked by the entry point): under ASR_ADJ_EXACT the flags launch is sr_adjoint_flags_kernel and
+    // the gather launches are the *_adj kernels, which also read rot_tf; K_fwd, K_gt and everything else are what they were.
     // rw (asr_sr_solve_rw_f32, always with dt; checked by the entry point): on a reweighting iteration K_fwd also writes the raw
     // residual, then the three sr_rw_* launches rewrite the copy weights, w_eff (at the workspace's end) and q; from then on
     // K_fwd and the monitor's term 0 read w_eff where they read the caller's weights.  Under a monitor one more small launch
@@ -2057,7 +2068,11 @@ int sr_solve_impl(const char* fn, float* x, const float* y, const float* rot_tf,
         dtc.w_stride = (int64_t)n * h * w;
         return ASR_OK;
     };
-    if (num_iter > 0) {
+    const bool exact = adjoint == ASR_ADJ_EXACT;
+    if (num_iter > 0 && exact) {
+        rc = sr_adjoint_flags_launch(s, rot_tf, trans_tf, inv_rot_tf, nullptr, affine_flags, batch, n);
+        if (rc != ASR_OK) return rc;
+    } else if (num_iter > 0) {
         hipLaunchKernelGGL(sr_affine_flags_kernel, dim3((unsigned)batch), dim3(64), 0, s, inv_rot_tf, affine_flags, n);
         ASR_LAUNCH_CHECK();
     }
@@ -2123,6 +2138,16 @@ int sr_solve_impl(const char* fn, float* x, const float* y, const float* rot_tf,
                 hipLaunchKernelGGL(gr_mon, gr_grid(d, cn), dim3(64, 4), 0, s, resid, inv_trans_tf, gr, d, 2.0f * lambda_df, n0, cn,
                                    marg);
                 ASR_LAUNCH_CHECK();
+                if (exact) {
+                    rc = pd ? sr_gather_pd_adj_launch(s, wa.weighted, gather_grid(d), cur, nxt, gr, rot_tf, inv_rot_tf, duals,
+                                                      alphas + (size_t)it * batch, d, lambda_tv, 2.0f * lambda_l2, lambda_l1, xb, acc, n0,
+                                                      cn, affine_flags, tw, marg)
+                            : sr_gather_adj_launch(s, wa.weighted, gather_grid(d), cur, nxt, gr, rot_tf, inv_rot_tf, m, v, vhat,
+                                                   alphas + (size_t)it * batch, nullptr, d, lambda_tv, 2.0f * lambda_l2, lambda_l1, st,
+                                                   xb, acc, n0, cn, affine_flags, tw, marg);
+                    if (rc != ASR_OK) return rc;
+                    continue;
+                }
                 if (pd) {
                     const auto pd_kernel = wa.weighted ? sr_backward_gather_pd_kernel<true, true> : sr_backward_gather_pd_kernel<false, true>;
                     hipLaunchKernelGGL(pd_kernel, gather_grid(d), dim3(64, 4), 0, s, cur, nxt, gr, inv_rot_tf, duals,
@@ -2170,6 +2195,16 @@ int sr_solve_impl(const char* fn, float* x, const float* y, const float* rot_tf,
             hipLaunchKernelGGL(gr_kernel, gr_grid(d, cn), dim3(64, 4), 0, s, resid, inv_trans_tf, gr, d, 2.0f * lambda_df, n0, cn,
                                SrMonArg<false>{});
             ASR_LAUNCH_CHECK();
+            if (exact) {
+                rc = pd ? sr_gather_pd_adj_launch(s, wa.weighted, gather_grid(d), cur, nxt, gr, rot_tf, inv_rot_tf, duals,
+                                                  alphas + (size_t)it * batch, d, lambda_tv, 2.0f * lambda_l2, lambda_l1, xb, acc, n0, cn,
+                                                  affine_flags, tw, SrMonArg<false>{})
+                        : sr_gather_adj_launch(s, wa.weighted, gather_grid(d), cur, nxt, gr, rot_tf, inv_rot_tf, m, v, vhat,
+                                               alphas + (size_t)it * batch, nullptr, d, lambda_tv, 2.0f * lambda_l2, lambda_l1, st, xb,
+                                               acc, n0, cn, affine_flags, tw, SrMonArg<false>{});
+                if (rc != ASR_OK) return rc;
+                continue;
+            }
             if (pd) {
                 const auto pd_kernel = wa.weighted ? sr_backward_gather_pd_kernel<true> : sr_backward_gather_pd_kernel<false>;
                 hipLaunchKernelGGL(pd_kernel, gather_grid(d), dim3(64, 4), 0, s, cur, nxt, gr, inv_rot_tf, duals,
@@ -2277,9 +2312,11 @@ int sr_solve_dt_entry(const char* fn, float* x, const float* y, const float* rot
                       double* last_loss_terms, void* workspace, size_t workspace_bytes, int batch, int n, int H, int W, int h, int w,
                       float lambda_df, float lambda_tv, float lambda_l2, float lambda_l1, const asr_sr_config* cfg,
                       const asr_sr_data_term* dt, const asr_sr_monitor* mon, bool monitored, int group, asr_stream_t stream,
-                      const asr_sr_reweight* rw = nullptr) {
+                      const asr_sr_reweight* rw = nullptr, int adjoint = ASR_ADJ_REGISTERED) {
+    int rc = check_adjoint(fn, adjoint);
+    if (rc != ASR_OK) return rc;
     SrDt a;
-    int rc = make_data_term(fn, dt, n, h, w, &a);
+    rc = make_data_term(fn, dt, n, h, w, &a);
     if (rc != ASR_OK) return rc;
     if (rw) {
         rc = check_reweight_rule(fn, rw->kind, rw->kappa);
@@ -2302,7 +2339,7 @@ int sr_solve_dt_entry(const char* fn, float* x, const float* y, const float* rot
     const SrTvWArg wa = {dt->wy, dt->wx, dt->tv_shared, dt->wy != nullptr};
     return sr_solve_impl(fn, x, y, rot_tf, trans_tf, inv_rot_tf, inv_trans_tf, m, v, vhat, alphas, num_iter, last_loss_terms,
                          workspace, workspace_bytes, batch, n, H, W, h, w, lambda_df, lambda_tv, lambda_l2, lambda_l1, cfg, wa,
-                         stream, &a, monitored ? mon : nullptr, group, rw);
+                         stream, &a, monitored ? mon : nullptr, group, rw, adjoint);
 }
 }  // namespace
 
@@ -2408,6 +2445,93 @@ extern "C" int asr_sr_solve_rw_f32(float* x, const float* y, const float* rot_tf
                              lambda_l1, cfg, dt, mon, mon != nullptr, group, stream, rw);
 }
 
+// ---- exact adjoint: the entry points (include/asr_hip.h, "exact adjoint") ---------------------------------------------------------
+extern "C" int asr_sr_solve_adj_f32(float* x, const float* y, const float* rot_tf, const float* trans_tf,
+                                    const float* inv_rot_tf, const float* inv_trans_tf, float* m, float* v, float* vhat,
+                                    const float* alphas, int num_iter, double* last_loss_terms, void* workspace,
+                                    size_t workspace_bytes, int batch, int n, int H, int W, int h, int w, float lambda_df,
+                                    float lambda_tv, float lambda_l2, float lambda_l1, const asr_sr_config* cfg,
+                                    const asr_sr_data_term* dt, const asr_sr_monitor* mon, int group,
+                                    const asr_sr_reweight* rw, int adjoint, asr_stream_t stream) {
+    return sr_solve_dt_entry("asr_sr_solve_adj_f32", x, y, rot_tf, trans_tf, inv_rot_tf, inv_trans_tf, m, v, vhat, alphas, num_iter,
+                             last_loss_terms, workspace, workspace_bytes, batch, n, H, W, h, w, lambda_df, lambda_tv, lambda_l2,
+                             lambda_l1, cfg, dt, mon, mon != nullptr, group, stream, rw, adjoint);
+}
+
+extern "C" int asr_sr_adjoint_flags_i32(const float* rot_tf, const float* trans_tf, const float* inv_rot_tf, int* flags, int batch,
+                                        int n, asr_stream_t stream) {
+    ASR_REQUIRE(rot_tf && trans_tf && inv_rot_tf && flags, "asr_sr_adjoint_flags_i32: null pointer");
+    ASR_REQUIRE(batch > 0 && n > 0, "asr_sr_adjoint_flags_i32: bad shape batch=%d n=%d", batch, n);
+    return sr_adjoint_flags_launch(asr_stream(stream), rot_tf, trans_tf, inv_rot_tf, flags, nullptr, batch, n);
+}
+
+namespace {
+// the running data-term sum [batch, H, W] + the G_R planes of a chunk + one mode word per image
+size_t sr_backward_adj_bytes(int batch, int H, int W, int chunk) {
+    return sizeof(float) * ((size_t)batch * H * W + (size_t)batch * chunk * sr_gr_plane_elems(H, W)) + sizeof(int) * (size_t)batch;
+}
+}  // namespace
+
+extern "C" size_t asr_sr_backward_adj_workspace_bytes(int batch, int n, int H, int W, const asr_sr_config* cfg) {
+    if (batch <= 0 || n <= 0 || H <= 0 || W <= 0) return 0;
+    return sr_backward_adj_bytes(batch, H, W, sr_plane_chunk(batch, n, H, W, cfg ? cfg->plane_chunk : 0));
+}
+
+extern "C" int asr_sr_backward_adj_f32(const float* x, float* x_new, const float* resid, const float* rot_tf, const float* trans_tf,
+                                       const float* inv_rot_tf, const float* inv_trans_tf, float* m, float* v, float* vhat,
+                                       const float* alphas, float* grad_out, int batch, int n, int H, int W, int h, int w,
+                                       float lambda_df, float lambda_tv, float lambda_l2, float lambda_l1, const asr_sr_config* cfg,
+                                       const float* wy, const float* wx, int w_shared, int adjoint, void* workspace,
+                                       size_t workspace_bytes, asr_stream_t stream) {
+    const char* fn = "asr_sr_backward_adj_f32";
+    int rc = check_adjoint(fn, adjoint);
+    if (rc != ASR_OK) return rc;
+    ASR_REQUIRE((wy == nullptr) == (wx == nullptr), "%s: null pointer (wy, wx: both or neither)", fn);
+    const SrTvWArg wa = {wy, wx, w_shared, wy != nullptr};
+    if (adjoint == ASR_ADJ_REGISTERED)      // the fused one-launch kernel of asr_sr_backward_wtv_f32 / _cfg_f32; no workspace
+        return sr_backward_impl(fn, x, x_new, resid, inv_rot_tf, inv_trans_tf, m, v, vhat, alphas, grad_out, batch, n, H, W, h, w,
+                                lambda_df, lambda_tv, lambda_l2, lambda_l1, cfg, wa, stream);
+    ASR_REQUIRE(x && resid && rot_tf && trans_tf && inv_rot_tf && inv_trans_tf && workspace, "%s: null pointer", fn);
+    ASR_REQUIRE(x_new || grad_out, "%s: need x_new and/or grad_out", fn);
+    ASR_REQUIRE(!x_new || alphas, "%s: alphas required with x_new", fn);
+    ASR_REQUIRE(x != x_new, "%s: x_new must not alias x (the priors read neighbours)", fn);
+    SrDims d;
+    rc = check_dims(fn, batch, n, H, W, h, w, &d);
+    if (rc != ASR_OK) return rc;
+    SrStep st;
+    rc = make_step(fn, cfg, x_new != nullptr, m, v, vhat, &st);
+    if (rc != ASR_OK) return rc;
+    SrTvW tw;
+    rc = make_tv_weights(fn, cfg, wa, H, W, &tw);
+    if (rc != ASR_OK) return rc;
+    ASR_REQUIRE(cfg->plane_chunk >= 0, "%s: plane_chunk %d < 0", fn, cfg->plane_chunk);
+    const int chunk = sr_plane_chunk(batch, n, H, W, cfg->plane_chunk);
+    ASR_REQUIRE((int64_t)batch * chunk <= 65535, "%s: batch*chunk=%lld exceeds 65535 (grid.z)", fn, (long long)batch * chunk);
+    const size_t need = sr_backward_adj_bytes(batch, H, W, chunk);
+    if (workspace_bytes < need) {
+        asr_set_error("%s: workspace %zu < required %zu bytes", fn, workspace_bytes, need);
+        return ASR_ERR_WORKSPACE;
+    }
+    hipStream_t s = asr_stream(stream);
+    float* const acc = static_cast<float*>(workspace);
+    float* const gr = acc + (size_t)batch * H * W;
+    int* const mode = reinterpret_cast<int*>(gr + (size_t)batch * chunk * sr_gr_plane_elems(H, W));
+    ASR_HIP_CHECK(hipMemsetAsync(gr, 0, sizeof(float) * (size_t)batch * chunk * sr_gr_plane_elems(H, W), s));   // the borders
+    rc = sr_adjoint_flags_launch(s, rot_tf, trans_tf, inv_rot_tf, nullptr, mode, batch, n);
+    if (rc != ASR_OK) return rc;
+    const SrGradTranslateKernel gr_kernel = sr_grad_translate_kernel_for(d.f);
+    for (int n0 = 0; n0 < n; n0 += chunk) {
+        const int cn = n - n0 < chunk ? n - n0 : chunk;
+        hipLaunchKernelGGL(gr_kernel, gr_grid(d, cn), dim3(64, 4), 0, s, resid, inv_trans_tf, gr, d, 2.0f * lambda_df, n0, cn,
+                           SrMonArg<false>{});
+        ASR_LAUNCH_CHECK();
+        rc = sr_gather_adj_launch(s, wa.weighted, gather_grid(d), x, x_new, gr, rot_tf, inv_rot_tf, m, v, vhat, alphas, grad_out, d,
+                                  lambda_tv, 2.0f * lambda_l2, lambda_l1, st, nullptr, acc, n0, cn, mode, tw, SrMonArg<false>{});
+        if (rc != ASR_OK) return rc;
+    }
+    return ASR_OK;
+}
+
 // ---- the step bound of the primal-dual rule (asr_sr_data_bound_f32; include/asr_hip.h, "primal-dual": the rule) -------------
 // One repetition is one solver iteration on v with measurements of zero -- K_fwd, K_gt and the gather kernel as they are, the
 // gather's gradient output (no prior: every lambda but lambda_df is 0) taken as w = M v -- then the two maxima and v = w / s.
@@ -2473,11 +2597,11 @@ extern "C" size_t asr_sr_data_bound_workspace_bytes(int batch, int n, int H, int
     return sr_bound_workspace_bytes(batch, n, H, W, h, w, sr_plane_chunk(batch, n, H, W, cfg ? cfg->plane_chunk : 0));
 }
 
-extern "C" int asr_sr_data_bound_f32(float* bound, const float* rot_tf, const float* trans_tf, const float* inv_rot_tf,
-                                     const float* inv_trans_tf, const float* weights, int weights_shared, int iters,
-                                     void* workspace, size_t workspace_bytes, int batch, int n, int H, int W, int h, int w,
-                                     float lambda_df, const asr_sr_config* cfg, asr_stream_t stream) {
-    const char* fn = "asr_sr_data_bound_f32";
+namespace {
+int sr_data_bound_impl(const char* fn, float* bound, const float* rot_tf, const float* trans_tf, const float* inv_rot_tf,
+                       const float* inv_trans_tf, const float* weights, int weights_shared, int iters, void* workspace,
+                       size_t workspace_bytes, int batch, int n, int H, int W, int h, int w, float lambda_df, const asr_sr_config* cfg,
+                       int adjoint, asr_stream_t stream) {
     ASR_REQUIRE(bound && rot_tf && trans_tf && inv_rot_tf && inv_trans_tf && workspace, "%s: null pointer", fn);
     ASR_REQUIRE(iters >= 1 && iters <= kBoundMaxIters, "%s: iters=%d outside [1, %d]", fn, iters, kBoundMaxIters);
     ASR_REQUIRE(lambda_df >= 0.0f && lambda_df < __builtin_inff(), "%s: lambda_df=%g must be finite and >= 0", fn, (double)lambda_df);
@@ -2507,8 +2631,14 @@ extern "C" int asr_sr_data_bound_f32(float* bound, const float* rot_tf, const fl
     ASR_HIP_CHECK(hipMemsetAsync(zero_y, 0, sizeof(float) * lr, s));
     ASR_HIP_CHECK(hipMemsetAsync(gr, 0, sizeof(float) * ((size_t)batch * chunk + batch) * pe, s));
     ASR_HIP_CHECK(hipMemsetAsync(maxima, 0, sizeof(unsigned) * 2 * (size_t)iters * batch, s));
-    hipLaunchKernelGGL(sr_affine_flags_kernel, dim3((unsigned)batch), dim3(64), 0, s, inv_rot_tf, affine_flags, n);
-    ASR_LAUNCH_CHECK();
+    const bool exact = adjoint == ASR_ADJ_EXACT;
+    if (exact) {
+        rc = sr_adjoint_flags_launch(s, rot_tf, trans_tf, inv_rot_tf, nullptr, affine_flags, batch, n);
+        if (rc != ASR_OK) return rc;
+    } else {
+        hipLaunchKernelGGL(sr_affine_flags_kernel, dim3((unsigned)batch), dim3(64), 0, s, inv_rot_tf, affine_flags, n);
+        ASR_LAUNCH_CHECK();
+    }
     SrDt dt;
     dt.loss = ASR_DF_L2; dt.delta = 0.0f; dt.w = weights; dt.w_stride = weights_shared ? 0 : (int64_t)n * h * w; dt.r_out = nullptr;
     SrStep st = {};
@@ -2527,6 +2657,12 @@ extern "C" int asr_sr_data_bound_f32(float* bound, const float* rot_tf, const fl
             hipLaunchKernelGGL(gr_kernel, gr_grid(d, cn), dim3(64, 4), 0, s, resid, inv_trans_tf, gr, d, 2.0f * lambda_df, n0, cn,
                                SrMonArg<false>{});
             ASR_LAUNCH_CHECK();
+            if (exact) {
+                rc = sr_gather_adj_launch(s, false, gather_grid(d), vcur, nullptr, gr, rot_tf, inv_rot_tf, nullptr, nullptr, nullptr,
+                                          nullptr, wv, d, 0.0f, 0.0f, 0.0f, st, nullptr, acc, n0, cn, affine_flags, tw, SrMonArg<false>{});
+                if (rc != ASR_OK) return rc;
+                continue;
+            }
             hipLaunchKernelGGL(sr_backward_gather_kernel<false>, gather_grid(d), dim3(64, 4), 0, s, vcur, (float*)nullptr, gr, inv_rot_tf,
                                (float*)nullptr, (float*)nullptr, (float*)nullptr, (const float*)nullptr, wv, d, 0.0f, 0.0f, 0.0f, st,
                                (float*)nullptr, acc, n0, cn, affine_flags, tw, SrMonArg<false>{});
@@ -2539,6 +2675,25 @@ extern "C" int asr_sr_data_bound_f32(float* bound, const float* rot_tf, const fl
                        bound, batch);
     ASR_LAUNCH_CHECK();
     return ASR_OK;
+}
+}  // namespace
+
+extern "C" int asr_sr_data_bound_f32(float* bound, const float* rot_tf, const float* trans_tf, const float* inv_rot_tf,
+                                     const float* inv_trans_tf, const float* weights, int weights_shared, int iters,
+                                     void* workspace, size_t workspace_bytes, int batch, int n, int H, int W, int h, int w,
+                                     float lambda_df, const asr_sr_config* cfg, asr_stream_t stream) {
+    return sr_data_bound_impl("asr_sr_data_bound_f32", bound, rot_tf, trans_tf, inv_rot_tf, inv_trans_tf, weights, weights_shared, iters,
+                              workspace, workspace_bytes, batch, n, H, W, h, w, lambda_df, cfg, ASR_ADJ_REGISTERED, stream);
+}
+
+extern "C" int asr_sr_data_bound_adj_f32(float* bound, const float* rot_tf, const float* trans_tf, const float* inv_rot_tf,
+                                         const float* inv_trans_tf, const float* weights, int weights_shared, int iters,
+                                         void* workspace, size_t workspace_bytes, int batch, int n, int H, int W, int h, int w,
+                                         float lambda_df, const asr_sr_config* cfg, int adjoint, asr_stream_t stream) {
+    const int rc = check_adjoint("asr_sr_data_bound_adj_f32", adjoint);
+    if (rc != ASR_OK) return rc;
+    return sr_data_bound_impl("asr_sr_data_bound_adj_f32", bound, rot_tf, trans_tf, inv_rot_tf, inv_trans_tf, weights, weights_shared,
+                              iters, workspace, workspace_bytes, batch, n, H, W, h, w, lambda_df, cfg, adjoint, stream);
 }
 
 extern "C" int asr_sr_solve_f32(float* x, const float* y, const float* rot_tf, const float* trans_tf,

@@ -193,10 +193,38 @@ def check_pd(bound_iters=6, dual_ratio=PD_DUAL_RATIO, name="primal-dual"):
     return int(bound_iters), float(dual_ratio)
 
 
-def sr_data_bound(rot_tf, trans_tf, inv_rot_tf, inv_trans_tf, out_hw, lr_hw, lambda_df, weights=None, iters=6, cfg=None):
+def check_adjoint(name, what="adjoint"):
+    """The data-term gradient's form -> ASR_ADJ_* code: "registered" (None too: TensorFlow's registered gradient of the rotate,
+    an inverse warp) or "exact" (the transpose of the forward rotate; include/asr_hip.h, "exact adjoint").  Host check, before
+    any launch."""
+    if name is None:
+        return _lib.ADJ_REGISTERED
+    if not isinstance(name, str) or name.lower() not in _lib.ADJOINTS:
+        raise ValueError(f"{what}: must be one of {sorted(_lib.ADJOINTS)}, got {name!r}")
+    return _lib.ADJOINTS[name.lower()]
+
+
+def sr_adjoint_flags(rot_tf, trans_tf, inv_rot_tf):
+    """device int32 [B]: 1 where the exact adjoint applies to the image (affine rotations, pure translations, a window the
+    kernel serves), 0 where adjoint="exact" takes the registered statements (include/asr_hip.h, "exact adjoint")."""
+    if rot_tf.dim() != 3 or rot_tf.shape[-1] != 8:
+        raise AsrError(f"sr_adjoint_flags: transforms must be [B,N,8], got {tuple(rot_tf.shape)}")
+    b, n = rot_tf.shape[:2]
+    for t, name in ((rot_tf, "rot_tf"), (trans_tf, "trans_tf"), (inv_rot_tf, "inv_rot_tf")):
+        _check_tf(t, b, n, name)
+    flags = torch.empty((b,), dtype=torch.int32, device=rot_tf.device)
+    call("asr_sr_adjoint_flags_i32", ptr(rot_tf), ptr(trans_tf), ptr(inv_rot_tf), ptr(flags, torch.int32), b, n, stream_ptr())
+    return flags
+
+
+def sr_data_bound(rot_tf, trans_tf, inv_rot_tf, inv_trans_tf, out_hw, lr_hw, lambda_df, weights=None, iters=6, cfg=None,
+                  adjoint=None):
     """device [B]: an upper bound on the spectral radius of the data term's gradient map, the step bound of the primal-dual
     rule (include/asr_hip.h, "primal-dual").  The transforms [B,N,8] of the solve, out_hw = (H, W), lr_hw = (h, w); weights:
-    the data term's, [N,h,w] shared or [B,N,h,w]; cfg: its plane_chunk alone is read.  Nothing is read back."""
+    the data term's, [N,h,w] shared or [B,N,h,w]; cfg: its plane_chunk alone is read.  Nothing is read back.
+    adjoint="exact": the map of the exact gradient, symmetric, for which the bound is a bound (asr_sr_data_bound_adj_f32);
+    None: the call below, unchanged."""
+    adj = check_adjoint(adjoint, "sr_data_bound: adjoint") if adjoint is not None else None
     iters, _ = check_pd(iters, name="sr_data_bound")
     if rot_tf.dim() != 3 or rot_tf.shape[-1] != 8:
         raise AsrError(f"sr_data_bound: transforms must be [B,N,8], got {tuple(rot_tf.shape)}")
@@ -215,6 +243,11 @@ def sr_data_bound(rot_tf, trans_tf, inv_rot_tf, inv_trans_tf, out_hw, lr_hw, lam
     ws_bytes = _lib.load().asr_sr_data_bound_workspace_bytes(b, n, H, W, h, w, C.byref(cfg))
     ws = torch.empty((ws_bytes + 3) // 4, dtype=f32, device=rot_tf.device)
     bound = torch.empty((b,), dtype=f32, device=rot_tf.device)
+    if adj is not None:
+        call("asr_sr_data_bound_adj_f32", ptr(bound), ptr(rot_tf), ptr(trans_tf), ptr(inv_rot_tf), ptr(inv_trans_tf),
+             ptr(weights, allow_none=True), shared, iters, ptr(ws), C.c_size_t(ws_bytes), b, n, H, W, h, w, float(lambda_df),
+             C.byref(cfg), adj, stream_ptr())
+        return bound
     call("asr_sr_data_bound_f32", ptr(bound), ptr(rot_tf), ptr(trans_tf), ptr(inv_rot_tf), ptr(inv_trans_tf),
          ptr(weights, allow_none=True), shared, iters, ptr(ws), C.c_size_t(ws_bytes), b, n, H, W, h, w, float(lambda_df),
          C.byref(cfg), stream_ptr())
@@ -275,11 +308,21 @@ def _tv_weights(tv_weights, x, name):
     return wy, wx, int(wy.dim() == 2)
 
 
-def sr_backward(x, resid, inv_rot_tf, inv_trans_tf, lambdas, cfg, state=None, want_grad=False, tv_weights=None):
+def sr_backward(x, resid, inv_rot_tf, inv_trans_tf, lambdas, cfg, state=None, want_grad=False, tv_weights=None, rot_tf=None,
+                trans_tf=None, adjoint=None):
     """One step with the update rule / prior of cfg.  state = dict(m, v, vhat, alphas[B]) (slots the optimizer
     does not use may be None) or None for the gradient only.  tv_weights = (wy, wx): the edge-weighted TV prior
-    (tv_edge_weights, or any finite weights >= 0).  Returns (x_new | None, grad | None)."""
+    (tv_edge_weights, or any finite weights >= 0).  Returns (x_new | None, grad | None).
+    adjoint ("registered" / "exact", with rot_tf and trans_tf [B,N,8]): the call goes through asr_sr_backward_adj_f32, whose
+    exact form takes the data-term gradient as the transpose of the forward rotate (include/asr_hip.h, "exact adjoint").
+    None: the calls below, unchanged."""
     b, n, H, W, h, w = _sr_dims(x, resid)
+    adj = check_adjoint(adjoint, "sr_backward: adjoint") if adjoint is not None else None
+    if adj is not None:
+        if rot_tf is None or trans_tf is None:
+            raise AsrError("sr_backward: adjoint needs rot_tf and trans_tf")
+        _check_tf(rot_tf, b, n, "rot_tf")
+        _check_tf(trans_tf, b, n, "trans_tf")
     tvw = _tv_weights(tv_weights, x, "sr_backward") if tv_weights is not None else None
     _check_tf(inv_rot_tf, b, n, "inv_rot_tf")
     _check_tf(inv_trans_tf, b, n, "inv_trans_tf")
@@ -296,6 +339,13 @@ def sr_backward(x, resid, inv_rot_tf, inv_trans_tf, lambdas, cfg, state=None, wa
             ptr(inv_trans_tf), ptr(st.get("m"), allow_none=True), ptr(st.get("v"), allow_none=True),
             ptr(st.get("vhat"), allow_none=True), ptr(st.get("alphas"), allow_none=True), ptr(grad, allow_none=True),
             b, n, H, W, h, w, float(lambdas[0]), float(lambdas[1]), float(lambdas[2]), float(lambdas[3]), C.byref(cfg))
+    if adj is not None:
+        ws_bytes = _lib.load().asr_sr_backward_adj_workspace_bytes(b, n, H, W, C.byref(cfg)) if adj == _lib.ADJ_EXACT else 0
+        ws = torch.empty((ws_bytes + 3) // 4, dtype=f32, device=x.device) if ws_bytes else None
+        call("asr_sr_backward_adj_f32", *args[:3], ptr(rot_tf), ptr(trans_tf), *args[3:],
+             ptr(tvw[0]) if tvw else None, ptr(tvw[1]) if tvw else None, tvw[2] if tvw else 0, adj,
+             ptr(ws, allow_none=True), C.c_size_t(ws_bytes), stream_ptr())
+        return x_new, grad
     if tvw is None:
         call("asr_sr_backward_cfg_f32", *args, stream_ptr())
     else:
@@ -530,7 +580,7 @@ def sr_apply_copy_weights(r, c, data_term=None, weights=None):
 
 def sr_solve(x, y, rot_tf, trans_tf, inv_rot_tf, inv_trans_tf, alphas, lambdas, one_minus_beta1=None, one_minus_beta2=None,
              epsilon=None, amsgrad=False, want_loss=True, cfg=None, slot_init=None, state=None, tv_weights=None,
-             data_term=None, weights=None, monitor=None, coupling=None, reweight=None):
+             data_term=None, weights=None, monitor=None, coupling=None, reweight=None, adjoint=None):
     """Runs alphas.shape[0] iterations in place on x.  alphas [num_iter, B] (device).  Either the Adam
     hyper-parameters (asr_sr_solve_f32) or cfg (+ slot_init = {"m"/"v"/"vhat": initial value}) for
     asr_sr_solve_cfg_f32.  state: a dict that carries the optimiser slots and the workspace from one call to the next --
@@ -549,15 +599,19 @@ def sr_solve(x, y, rot_tf, trans_tf, inv_rot_tf, inv_trans_tf, alphas, lambdas, 
     reweight (check_sr_reweight's dict, or a kind name): every `every` iterations from `start` each copy's residual energy is
     compared with the median over the copies of its image and the whole copy is scaled by a robust weight, on top of `weights`
     (include/asr_hip.h, "copy reweighting"; asr_sr_solve_rw_f32); combines with everything above.  The return value gains one
-    last element, an SrCopyWeights.  None: the calls below and their return values, unchanged."""
+    last element, an SrCopyWeights.  None: the calls below and their return values, unchanged.
+    adjoint ("registered" / "exact"): the solve goes through asr_sr_solve_adj_f32; "exact" takes the data-term gradient as the
+    transpose of the forward rotate instead of TensorFlow's registered inverse warp (include/asr_hip.h, "exact adjoint") and
+    combines with everything above; return values are those of the same call without it.  None: the calls below, unchanged."""
     b, n, H, W, h, w = _sr_dims(x, y)
+    adj = check_adjoint(adjoint, "sr_solve: adjoint") if adjoint is not None else None
     rwp = check_sr_reweight(reweight, "sr_solve: reweight") if reweight is not None else None
     if rwp is not None and n > _lib.RW_MAX_COPIES:
         raise AsrError(f"sr_solve: reweight ranks at most {_lib.RW_MAX_COPIES} copies, got {n}")
     group = None if coupling is None else check_coupling(coupling, b, cfg, "sr_solve: coupling")
     mon = check_sr_monitor(monitor, "sr_solve: monitor") if monitor is not None else None
     tvw = _tv_weights(tv_weights, x, "sr_solve") if tv_weights is not None else None
-    dt = _data_term(data_term, weights, y, tvw, "sr_solve", always=mon is not None or group is not None or rwp is not None)
+    dt = _data_term(data_term, weights, y, tvw, "sr_solve", always=mon is not None or group is not None or rwp is not None or adj is not None)
     if (tvw is not None or dt is not None) and cfg is None:
         cfg = _adam_config(one_minus_beta1, one_minus_beta2, epsilon, amsgrad)
     for t, name in ((rot_tf, "rot_tf"), (trans_tf, "trans_tf"), (inv_rot_tf, "inv_rot_tf"), (inv_trans_tf, "inv_trans_tf")):
@@ -595,12 +649,22 @@ def sr_solve(x, y, rot_tf, trans_tf, inv_rot_tf, inv_trans_tf, alphas, lambdas, 
         ms = _lib.SrMonitor(mon["every"], mon["rel_tol"], mon["patience"], mon["min_iter"],
                             history.data_ptr() if history is not None and history.numel() else None, ptr(iters_done, torch.int32))
         trace = SrTrace(history, eval_iters, iters_done)
+    rs = cw = cw_hist = rw_iters = None
     if rwp is not None:
         rw_iters = sr_reweight_iters(rwp, num_iter)
         cw = torch.empty((b, n), dtype=f32, device=x.device)
         cw_hist = torch.empty((len(rw_iters), b, n), dtype=f32, device=x.device) if rwp["history"] else None
         rs = _lib.SrReweight(_lib.RW_KINDS[rwp["kind"]], rwp["kappa"], rwp["every"], rwp["start"], ptr(cw),
                              cw_hist.data_ptr() if cw_hist is not None and cw_hist.numel() else None)
+    if adj is not None:
+        call("asr_sr_solve_adj_f32", ptr(x), ptr(y), ptr(rot_tf), ptr(trans_tf), ptr(inv_rot_tf), ptr(inv_trans_tf), ptr(m),
+             ptr(v), ptr(vhat), ptr(alphas), num_iter, ptr(terms, torch.float64, allow_none=True), ptr(ws),
+             C.c_size_t(ws_bytes), b, n, H, W, h, w, float(lambdas[0]), float(lambdas[1]), float(lambdas[2]),
+             float(lambdas[3]), C.byref(cfg), C.byref(dt), C.byref(ms) if ms is not None else None,
+             group if group is not None else 0, C.byref(rs) if rs is not None else None, adj, stream_ptr())
+        out = (x, terms) if trace is None else (x, terms, trace)
+        return out + (SrCopyWeights(cw, cw_hist, rw_iters),) if rs is not None else out
+    if rwp is not None:
         call("asr_sr_solve_rw_f32", ptr(x), ptr(y), ptr(rot_tf), ptr(trans_tf), ptr(inv_rot_tf), ptr(inv_trans_tf), ptr(m),
              ptr(v), ptr(vhat), ptr(alphas), num_iter, ptr(terms, torch.float64, allow_none=True), ptr(ws),
              C.c_size_t(ws_bytes), b, n, H, W, h, w, float(lambdas[0]), float(lambdas[1]), float(lambdas[2]),

@@ -29,6 +29,10 @@ mask it solves (ops.sr_data_bound, ops.pd_steps).  It refuses ``use_BTV`` and ``
 ``reweight_every`` iterations from ``reweight_start`` each copy's residual energy against ``reweight_kappa`` times the median over
 the copies of its image (include/asr_hip.h, "copy reweighting"); ``last_copy_weights`` then holds the ops.SrCopyWeights of the
 last solve.  It multiplies ``df_weights`` and combines with every option above.
+
+``adjoint`` (not in the reference) chooses the data-term gradient of the solves: "registered" is the reference's, TensorFlow's
+registered gradient of the rotate (an inverse warp, not a gradient of the loss); "exact" is the transpose of the forward rotate
+(include/asr_hip.h, "exact adjoint"), under which the primal-dual step bound is a true bound.  It combines with every option above.
 """
 from __future__ import annotations
 
@@ -90,7 +94,12 @@ class Superresolution:
                  optimizer: Optimizer = None, feature_size=(64, 64), output_size=(512, 512), use_BTV=False,
                  verbose=False, copy_dropout=0.0, trim=0.1, cover="frame", cov_min=0.5, valid_min=0.5, tv_beta=100.0,
                  df_loss="l2", df_delta=0.1, stop_rel_tol=None, stop_patience=3, stop_every=1, stop_min_iter=0,
-                 keep_history=False, reweight=None, reweight_kappa=2.0, reweight_every=10, reweight_start=10):
+                 keep_history=False, reweight=None, reweight_kappa=2.0, reweight_every=10, reweight_start=10,
+                 adjoint="registered"):
+        # the data-term gradient of the solves: "registered" (the reference's: TensorFlow's registered gradient of the rotate, an
+        # inverse warp; the calls and launches that always ran) or "exact" (its transpose; include/asr_hip.h, "exact adjoint")
+        ops.check_adjoint(adjoint, "Superresolution: adjoint")
+        self.adjoint = "registered" if adjoint is None else adjoint.lower()
         self.tv_beta = ops.check_tv_beta(tv_beta, "Superresolution: tv_beta")
         # the convergence monitor (include/asr_hip.h): with stop_rel_tol each image of a solve stops by itself once its loss
         # has not improved by that relative amount for stop_patience evaluations in a row (one every stop_every iterations,
@@ -389,7 +398,7 @@ class Superresolution:
             if self.df_loss == "l1":
                 raise ValueError("Superresolution: primal_dual needs a smooth data term (df_loss 'l2' or 'huber')")
             bound = ops.sr_data_bound(rot, tr, irot, itr, self.output_size, (h, w), self.lambda_df, weights=wts,
-                                      iters=state.bound_iters)
+                                      iters=state.bound_iters, adjoint="exact" if self.adjoint == "exact" else None)
             alphas_dev = ops.pd_steps(bound, self.lambda_L2, self.num_iter)
         else:
             alphas_dev = ops.to_device(alphas, device=dev)
@@ -400,6 +409,8 @@ class Superresolution:
             kw.update(data_term=self._data_term(), weights=wts)
         if coupling is not None:
             kw["coupling"] = coupling
+        if self.adjoint == "exact":                          # "registered": no keyword, the calls that always ran
+            kw["adjoint"] = "exact"
         if self.reweight is not None:
             out = ops.sr_solve(x, copies, rot, tr, irot, itr, alphas_dev, self._lambdas, monitor=self.monitor,
                                reweight=self.reweight, **kw)

@@ -378,8 +378,10 @@ int asr_sr_solve_mon_f32(float* x, const float* y, const float* rot_tf, const fl
  *     to call, alone or in any batch, for any plane_chunk.  A repetition costs one solver iteration; no y is needed.
  *     With tau = 1 / (bound + 2*lambda_l2) and c0 = 1/16:  1/tau - 8*sigma = (bound + 2*lambda_l2) / 2, the Condat-Vu
  *     condition for a smooth part with that Lipschitz constant and a difference operator of squared norm <= 8.  The
- *     theorem assumes the data gradient is a true gradient (M symmetric); the registered gradient of the projective
- *     transform is an inverse warp, not the adjoint, so the step is a heuristic and the monitor is the guard.
+ *     theorem assumes the data gradient is a true gradient (M symmetric).  Under ASR_ADJ_REGISTERED the registered gradient of
+ *     the projective transform is an inverse warp, not the adjoint: the step is a heuristic and the monitor is the guard.  Under
+ *     ASR_ADJ_EXACT ("exact adjoint" below; asr_sr_data_bound_adj_f32) M = 2*lambda_df * A^T W A is symmetric and non-negative,
+ *     the theorem's assumption holds and the bound is a bound.
  *     Refusals: null pointers (weights may be NULL), iters outside 1..64, lambda_df negative or not finite, plane_chunk < 0
  *     -> ASR_ERR_INVALID_ARG; the shape refusals of the solves; a short workspace -> ASR_ERR_WORKSPACE. */
 
@@ -540,6 +542,78 @@ int asr_sr_solve_rw_f32(float* x, const float* y, const float* rot_tf, const flo
                         int h, int w, float lambda_df, float lambda_tv, float lambda_l2, float lambda_l1,
                         const asr_sr_config* cfg, const asr_sr_data_term* dt, const asr_sr_monitor* mon /* may be NULL */,
                         int group, const asr_sr_reweight* rw /* may be NULL */, asr_stream_t stream);
+
+/* --- exact adjoint: the data-term gradient as the true transpose of the forward operator -----------------------------------
+ * Every update rule receives the data-term gradient g_df = sum_n c_n.  Under ASR_ADJ_REGISTERED (what every other entry point
+ * computes) c_n(p) is TensorFlow's registered gradient of the rotate: one bilinear tap of the per-copy plane G_R[n] at R_n^-1 p,
+ * an inverse warp, not the transpose.  The resize gradient is the exact transpose and the translate stage's inverse warp is the
+ * transpose up to the rounding of its tap weights; the defect sits in the rotate alone.  Under ASR_ADJ_EXACT only the gather
+ * changes: the grad-translate kernel writes the same zero-bordered planes G_R, and the tap is replaced by the transpose of the
+ * forward rotate, as a gather (no floating-point atomics).  The rule, for HR pixel p = (X, Y) and copy n with rot_tf[n] = R
+ * (a0 a1 a2 b0 b1 b2) and inv_rot_tf[n] = I (i00 i01 i02 i10 i11 i12), every operation float32 and rounding by itself:
+ *
+ *   Window.  (qx, qy) = (i00*X + i01*Y + i02,  i10*X + i11*Y + i12)          the forward kernels' affine map, with I
+ *       ex = (|i00| + |i01|) + 1/64        ey = (|i10| + |i11|) + 1/64       the margin 1/64: I is a rounded inverse, q is float32
+ *       x positions  ceil(qx - ex) .. floor(qx + ex),   y positions  ceil(qy - ey) .. floor(qy + ey)
+ *     A forward tap of position q touches p only if |R q - p| < 1 on both axes, i.e. |q - R^-1 p| < (|i00|+|i01|, |i10|+|i11|):
+ *     the window holds every q with a non-zero weight.  For a rotation it is at most 3 x 3.  The first position is clamped to
+ *     [-2, size - 1] and the last to [-3, size + 1]: positions outside the image contribute nothing (G_R is 0 there, the plane's
+ *     border), and nothing outside the bordered plane is read, however far outside the image R^-1 p lies.
+ *   Weights.  For a position q = (x, y) of the window:
+ *       ix = a0*x + a1*y + a2      iy = b0*x + b1*y + b2                      the forward kernel's own statements at q
+ *       xf = floor(ix)             wx = (xf == X) ? (xf + 1) - ix : ((xf + 1 == X) ? ix - xf : 0)        wy likewise with iy, Y
+ *     A position too many (a margin, a clamp) has weight 0 and adds +-0: the result does not depend on the window's extent.
+ *   Order.  c_n = 0;  for y rising, for x rising:  c_n = c_n + (wy * wx) * G_R[n][y, x].   g_df = the running sum over the
+ *     copies n = 0 .. N-1 in order, from +0, each c_n added once: the result does not depend on plane_chunk or on the batch.
+ *   Forms.  When ex <= 1.46875 and ey <= 1.46875 for every copy of the image (every rotation: |cos| + |sin| <= 1.4143) the three
+ *     positions ceil(q - e) + {0, 1, 2} per axis cover the window and a branch-free 3 x 3 form runs; otherwise a counted loop.
+ *   Where it applies, per image (one small flags launch per call): every rot_tf and inv_rot_tf of the image affine (c0 == c1 == 0),
+ *     every trans_tf a pure translation (1 0 t 0 1 t 0 0), ex and ey <= 8 and |i02|, |i12| <= 16384 (float32 then keeps q within
+ *     the margin).  An image that fails any of these -- a projective rotation, a non-pure translate, a transform that is not
+ *     finite -- takes the REGISTERED statements for all its copies, bit for bit.  asr_sr_adjoint_flags_i32 reports the choice:
+ *     flags[b] = 1 exact, 0 registered.  inv_rot_tf is used as given, to locate the window only; the weights never read it.
+ *   With angle 0 every R q is an integer position (a shift), the transpose is the single tap the registered form takes, and both
+ *     forms return the same bits.
+ *
+ *   asr_sr_solve_adj_f32: the arguments of asr_sr_solve_rw_f32 and `adjoint`.  ASR_ADJ_REGISTERED: asr_sr_solve_rw_f32, bit for
+ *     bit, the same launches.  ASR_ADJ_EXACT: the flags launch and the gather launches are the exact ones, one for one; the forward
+ *     and grad-translate launches, the monitor, the coupling and the reweighting are unchanged, and so is every workspace size
+ *     (asr_sr_solve_workspace_bytes_rw / _ml / _mon / _dt).  Combines with every optimizer, data term and prior.
+ *   asr_sr_data_bound_adj_f32: asr_sr_data_bound_f32 with the gather chosen by `adjoint`; the same workspace.
+ *   asr_sr_backward_adj_f32: one step, the arguments of asr_sr_backward_wtv_f32 with rot_tf, trans_tf, `adjoint` and a workspace;
+ *     wy == wx == NULL means the unweighted prior (asr_sr_backward_cfg_f32).  ASR_ADJ_REGISTERED: the one launch of the entry point
+ *     it wraps; the workspace is not read (may be NULL).  ASR_ADJ_EXACT: the grad-translate and exact gather launches per chunk of
+ *     cfg->plane_chunk copies, so grad_out is available with x_new == NULL.  asr_sr_backward_adj_workspace_bytes: the running sum
+ *     [batch, H, W] + the planes of a chunk + one int per image; host arithmetic, 0 for a size below 1.
+ *   Refusals, before any launch, outputs untouched: adjoint other than 0 or 1 -> ASR_ERR_INVALID_ARG; every refusal of the
+ *     wrapped entry point; asr_sr_backward_adj_f32 under ASR_ADJ_EXACT also a NULL or short workspace, plane_chunk < 0 and
+ *     batch * chunk > 65535. */
+#define ASR_ADJ_REGISTERED 0
+#define ASR_ADJ_EXACT 1
+
+int asr_sr_adjoint_flags_i32(const float* rot_tf, const float* trans_tf, const float* inv_rot_tf, int* flags /* device [batch] */,
+                             int batch, int n, asr_stream_t stream);
+
+int asr_sr_solve_adj_f32(float* x, const float* y, const float* rot_tf, const float* trans_tf, const float* inv_rot_tf,
+                         const float* inv_trans_tf, float* m, float* v, float* vhat, const float* alphas, int num_iter,
+                         double* last_loss_terms, void* workspace, size_t workspace_bytes, int batch, int n, int H, int W,
+                         int h, int w, float lambda_df, float lambda_tv, float lambda_l2, float lambda_l1,
+                         const asr_sr_config* cfg, const asr_sr_data_term* dt, const asr_sr_monitor* mon /* may be NULL */,
+                         int group, const asr_sr_reweight* rw /* may be NULL */, int adjoint, asr_stream_t stream);
+
+int asr_sr_data_bound_adj_f32(float* bound, const float* rot_tf, const float* trans_tf, const float* inv_rot_tf,
+                              const float* inv_trans_tf, const float* weights, int weights_shared, int iters, void* workspace,
+                              size_t workspace_bytes, int batch, int n, int H, int W, int h, int w, float lambda_df,
+                              const asr_sr_config* cfg, int adjoint, asr_stream_t stream);
+
+size_t asr_sr_backward_adj_workspace_bytes(int batch, int n, int H, int W, const asr_sr_config* cfg /* may be NULL */);
+
+int asr_sr_backward_adj_f32(const float* x, float* x_new, const float* resid, const float* rot_tf, const float* trans_tf,
+                            const float* inv_rot_tf, const float* inv_trans_tf, float* m, float* v, float* vhat,
+                            const float* alphas, float* grad_out, int batch, int n, int H, int W, int h, int w, float lambda_df,
+                            float lambda_tv, float lambda_l2, float lambda_l1, const asr_sr_config* cfg, const float* wy,
+                            const float* wx, int w_shared, int adjoint, void* workspace, size_t workspace_bytes,
+                            asr_stream_t stream);
 
 /* out[b] = max / mean over copies of rotate(translate(resize(y[b,i], (H,W)), trans_tf), rot_tf)
  * -- max_superresolution / mean_superresolution, superresolution.py:139-161 (trans_tf built

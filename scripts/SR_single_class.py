@@ -40,6 +40,8 @@ def main():
     ap.add_argument("--sr_stop_patience", type=int, default=None, help="evaluations in a row without that improvement before a solve stops (default 3)")
     ap.add_argument("--sr_stop_every", type=int, default=None, help="evaluate the loss every this many iterations (default 1)")
     ap.add_argument("--sr_stop_min_iter", type=int, default=None, help="no solve stops before this iteration (default 0)")
+    ap.add_argument("--sr_adjoint", choices=["registered", "exact"], default="registered",
+                    help="the data-term gradient of the iterative solve: TensorFlow's registered gradient of the rotate (the reference's) or its exact transpose")
     ap.add_argument("--sr_reweight", choices=["cauchy", "hard"], default=None,
                     help="down-weight whole unreliable copies inside the iterative solve: each copy's residual energy against --sr_reweight_kappa times the median over the copies")
     ap.add_argument("--sr_reweight_kappa", type=float, default=None, help="a copy at this many times the median energy gets weight 1/2 (cauchy) or is the last kept (hard); finite, > 0 (default 2)")
@@ -94,6 +96,7 @@ def main():
                          lambda_L1=HYPER["lambda_L1"], num_iter=HYPER["num_iter"], num_aug=args.num_aug,
                          optimizer=optimizer_obj, feature_size=(args.feature_size, args.feature_size), trim=args.trim,
                          cover=args.cover, df_loss=args.df_loss, df_delta=args.df_delta, **stop_kw,
+                         **(dict(adjoint="exact") if args.sr_adjoint == "exact" else {}),
                          **Superresolution.reweight_keywords(sr_reweight))
     paths = interchange_files(args.data)[:args.num_samples]
     res = evaluate_precomputed(sr, paths, args.gt, args.standard, num_aug=args.num_aug, class_id=args.class_id,

@@ -37,6 +37,8 @@ parser.add_argument("--th_factor", type=float, default=0.65)
 parser.add_argument("--num_iter", type=int, default=300)
 parser.add_argument("--df_loss", choices=["l2", "l1", "huber"], default="l2", help="data term of the iterative solve: l2 (the reference's), l1, or huber with threshold --df_delta")
 parser.add_argument("--df_delta", type=float, default=0.1, help="Huber threshold, in units of the stacks (normalised to [0, 1]); finite, > 0")
+parser.add_argument("--sr_adjoint", choices=["registered", "exact"], default="registered",
+                    help="the data-term gradient of the iterative solve: TensorFlow's registered gradient of the rotate (the reference's) or its exact transpose")
 parser.add_argument("--sr_reweight", choices=["cauchy", "hard"], default=None,
                     help="down-weight whole unreliable copies inside the iterative solve: each copy's residual energy against --sr_reweight_kappa times the median over the copies")
 parser.add_argument("--sr_reweight_kappa", type=float, default=None, help="a copy at this many times the median energy gets weight 1/2 (cauchy) or is the last kept (hard); finite, > 0 (default 2)")
@@ -94,6 +96,7 @@ def main():
     sr = Superresolution(lambda_df=HYPER["lambda_df"], lambda_tv=HYPER["lambda_tv"], lambda_L2=HYPER["lambda_L2"],
                          lambda_L1=HYPER["lambda_L1"], num_iter=args.num_iter, num_aug=args.num_aug, optimizer=opt,
                          feature_size=(feat, feat), output_size=IMG_SIZE, df_loss=args.df_loss, df_delta=args.df_delta,
+                         **(dict(adjoint="exact") if args.sr_adjoint == "exact" else {}),
                          **Superresolution.reweight_keywords(sr_reweight))
     path = HotPath(model, sr, mode=args.mode, th_factor=args.th_factor, batch_size=BATCH_SIZE)
     table, presence = evaluate_classes(path, paths, gts, class_ids, num_aug=args.num_aug, angle_max=args.angle_max,

@@ -128,6 +128,8 @@ parser.add_argument("--sr_stop_tol", type=float, default=None,
 parser.add_argument("--sr_stop_patience", type=int, default=None, help="evaluations in a row without that improvement before a solve stops (default 3)")
 parser.add_argument("--sr_stop_every", type=int, default=None, help="evaluate the loss every this many iterations (default 1)")
 parser.add_argument("--sr_stop_min_iter", type=int, default=None, help="no solve stops before this iteration (default 0)")
+parser.add_argument("--sr_adjoint", choices=["registered", "exact"], default="registered",
+                    help="the data-term gradient of the iterative solve: TensorFlow's registered gradient of the rotate (the reference's) or its exact transpose")
 parser.add_argument("--sr_reweight", choices=["cauchy", "hard"], default=None,
                     help="down-weight whole unreliable copies inside the iterative solve: each copy's residual energy against --sr_reweight_kappa times the median over the copies")
 parser.add_argument("--sr_reweight_kappa", type=float, default=None, help="a copy at this many times the median energy gets weight 1/2 (cauchy) or is the last kept (hard); finite, > 0 (default 2)")
@@ -318,7 +320,8 @@ def main():
     feat = IMG_SIZE[0] // (4 if args.backbone == "xception" else 8)
     sr = Superresolution(lambda_df=HYPER["lambda_df"], lambda_tv=HYPER["lambda_tv"], lambda_L2=HYPER["lambda_L2"],
                          lambda_L1=HYPER["lambda_L1"], num_iter=args.num_iter, num_aug=args.num_aug, optimizer=opt,
-                         feature_size=(feat, feat), output_size=IMG_SIZE, df_loss=args.df_loss, df_delta=args.df_delta)
+                         feature_size=(feat, feat), output_size=IMG_SIZE, df_loss=args.df_loss, df_delta=args.df_delta,
+                         **(dict(adjoint="exact") if args.sr_adjoint == "exact" else {}))
     path = HotPath(model, sr, mode=args.mode, th_factor=args.th_factor, batch_size=BATCH_SIZE)
     sr_iters = []
     copy_weights = []
