@@ -17,6 +17,7 @@ A case is (shape key, transform kind, data term, weights mode, tv-weights mode, 
   chunk      plane_chunk (0: all copies at once; 2 with n = 5: a last chunk of one copy)
 Every problem has n = 5 copies (copy 3 wholly out of frame, copy 4 turned by pi / 2) and batch 2 with one transform set per
 image: test_gpu_sr_shapes._problem(shape, kind, N_COPIES, SEED), the very problems that suite holds against the oracle."""
+import os
 import re
 from collections import namedtuple
 
@@ -121,7 +122,26 @@ OTHER_KERNELS = frozenset(["sr_init_kernel", "sr_tv_edge_weights_kernel", "sr_re
                            "sr_realign_covered_median_kernel", "sr_realign_moments_kernel<false>",
                            "sr_realign_moments_kernel<true>"])
 
+# the sections of sr.hip that live in files of their own (#include "sr_*_kernels.h"), hand-written like the lists above
+RW_KERNELS = frozenset(["sr_rw_energy_kernel", "sr_rw_weights_kernel", "sr_rw_apply_kernel", "sr_rw_rearm_kernel"])
+ADJ_GATHER_KERNELS = frozenset(f"sr_backward_gather{pd}_adj_kernel<{w},{m}>" for pd in ("", "_pd") for w in ("false", "true")
+                               for m in ("false", "true"))
+ADJ_KERNELS = frozenset(["sr_adjoint_flags_kernel"]) | ADJ_GATHER_KERNELS
+
 _KERNEL = r"sr_[a-z0-9_]+_kernel(?![A-Za-z0-9_])(?:\s*<[^<>()]*>)?"
+
+
+def spliced_source(path):
+    """The text of csrc/sr.hip as the compiler sees its kernels: every `#include "sr_*_kernels.h"` line replaced by the text of
+    that file (looked up beside `path`), so that the kernels and launch selectors of the included sections are read too."""
+    here = os.path.dirname(os.path.abspath(path))
+
+    def section(m):
+        with open(os.path.join(here, m.group(1))) as f:
+            return f.read()
+
+    with open(path) as f:
+        return re.sub(r'^[ \t]*#include[ \t]+"(sr_[a-z0-9_]+_kernels\.h)"[ \t]*$', section, f.read(), flags=re.M)
 
 
 def source_instantiations(text):

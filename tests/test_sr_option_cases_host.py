@@ -1,5 +1,6 @@
 """The case table of tests/sr_option_cases.py without a device: its cases launch every option instantiation that csrc/sr.hip
-has (the list is read from the source text itself, so a template argument added later without a case fails here), its
+has (the list is read from the source text itself, sr.hip with its #include "sr_*_kernels.h" sections spliced in, so a template
+argument added later to any of them without a case fails here; the exact-adjoint forms have their cases in tests/sr_adj_cases.py), its
 transform sets keep the bounds of test_gpu_sr_shapes._transform_set, and the "neutral" values of
 tests/test_gpu_sr_option_shapes.py are neutral in the restatements that suite leans on."""
 import os
@@ -23,14 +24,16 @@ SR_HIP = os.path.join(ROOT, "deeplabv3plus-augmented-superresolution_amd", "csrc
 
 @pytest.fixture(scope="module")
 def in_source():
-    with open(SR_HIP) as f:
-        return T.source_instantiations(f.read())
+    return T.source_instantiations(T.spliced_source(SR_HIP))        # sr.hip with its #include "sr_*_kernels.h" sections in place
 
 
 # ---- 1. coverage ---------------------------------------------------------------------------------------------------------------------
 def test_the_source_holds_the_hand_written_list_and_nothing_else(in_source):
-    known = T.OPTION_KERNELS | T.SOLVER_HELPERS | T.OTHER_KERNELS
-    print("in sr.hip:", len(in_source), "forms;", len(T.OPTION_KERNELS), "option instantiations")
+    known = T.OPTION_KERNELS | T.SOLVER_HELPERS | T.OTHER_KERNELS | T.RW_KERNELS | T.ADJ_KERNELS
+    print("in sr.hip and its sections:", len(in_source), "forms;", len(T.OPTION_KERNELS), "option instantiations")
+    with open(SR_HIP) as f:                                            # the sections are read: sr.hip alone holds fewer forms
+        assert T.source_instantiations(f.read()) < in_source
+    assert len(T.RW_KERNELS) == 4 and len(T.ADJ_KERNELS) == 1 + 8
     assert in_source - known == set(), "launched in sr.hip, in no list of sr_option_cases.py"
     assert known - in_source == set(), "listed in sr_option_cases.py, launched nowhere in sr.hip"
     assert len(T.OPTION_KERNELS) == 5 + 8 + 8 + 4 + 4 + 9
@@ -64,6 +67,28 @@ def test_every_option_instantiation_has_a_case(in_source):
         assert {T.factor(c.shape) for c in by_kernel[k]} >= {8, 6, 4} and {c.kind for c in by_kernel[k]} == {"T0", "T2"}
     stops = [c for c in T.TABLE if c.monitor == "stop" and c.chunk == 2]
     assert {T.factor(c.shape) for c in stops} >= {8, 6}
+
+
+def test_every_exact_adjoint_form_has_a_case_on_rotations_and_on_the_counted_loop(in_source):
+    """The kernels of the included section csrc/sr_adj_kernels.h against the table of tests/sr_adj_cases.py."""
+    import sr_adj_cases as TA
+    by_kernel = {}
+    for case in TA.TABLE:
+        for k in TA.instantiations(case):
+            by_kernel.setdefault(k, []).append(case)
+    assert set(by_kernel) <= in_source
+    assert set(by_kernel) - T.ADJ_KERNELS <= T.OPTION_KERNELS | T.SOLVER_HELPERS        # the unchanged forward / grad-translate forms
+    assert {f"sr_grad_translate_kernel<{L}>" for L in (0, 1, 2, 3)} <= set(by_kernel)
+    for k in sorted(T.ADJ_KERNELS):
+        families = {c.family for c in by_kernel.get(k, [])}
+        print(f"{k}: {len(by_kernel.get(k, []))} cases on {sorted(families)}")
+        assert families, k
+        assert "rotations" in families, k
+        assert families & set(TA.LOOP_FAMILIES), k
+    # the loop families do take the counted loop, rotations the 3 x 3 form (tests/test_sr_adj_cases_host.py holds every problem)
+    for family in TA.FORM_FAMILIES:
+        assert {TA.side(t[2]) for t in TA.problem(TA.FORM_SHAPE, family, TA.FORM_N).tfs} == {TA.FAMILIES[family][1]}
+    assert TA.FAMILIES["rotations"][1] == "fixed" and all(TA.FAMILIES[f][1] == "loop" for f in TA.LOOP_FAMILIES)
 
 
 def test_the_dispatch_restatement():
